@@ -10,12 +10,18 @@ the pixel-shuffle store) over one batch of synthetic frames already resident in 
 BASELINE.json configs[1]: SESR-x2 INT8 1080p -> 4K, one frame per step; the steps rotate over 8 distinct resident
 input frames.  Frames shard across ranks with no data-path collective.  Rank 0 prints ONE JSON line.
 
-The timed region is `--repeats` blocks (default: max(5, ceil(1500 / K))) of exactly K steps, each bracketed by
-synchronize + barrier on both sides; `value` is the MEDIAN block (min / max in `spread`, every block in `blocks_fps`),
-MAX over ranks per block (sesrq/dist.py:run_timed).
+The timed region is exactly K steps, bracketed by synchronize + barrier on both sides; `value` = frames of those K steps / their
+time, MAX over ranks (sesrq/dist.py:run_timed).  Before it, untimed: `--settle` blocks of K steps, each fenced like the timed one
+(default: ceil(SETTLE_STEPS / K) blocks, so that the timed block runs in the steady state of a series of blocks), then the W warm-up
+steps and the host-enqueue sample.  `--repeats R` (opt-in, A/B scripts) times R blocks and reports the median.
+
+    --dump-outputs DIR   after the timed steps, write what the timed path returned in its last step (the int8 output frame of that step,
+                         as float32) to DIR/out_q.npy (DIR/out_q.rank<r>.npy per rank for N > 1): the whole array, or a fixed seeded sample
+                         of it where the whole would exceed DUMP_BYTES.  The inputs are seeded: the same arguments give the same arrays.
 """
 import argparse
 import json
+import math
 import os
 import statistics
 import subprocess
@@ -30,6 +36,10 @@ for p in (ROOT, os.path.join(ROOT, "sesr-pytorch-quantize_amd")):
 HBM_PEAK = 8.0e12            # B/s, MI355X HBM3E spec (/opt/skills/guides/MI355X_MICROARCH.md)
 MFMA_I8_PEAK = 5.0e15     # dense int8 MFMA, ops/s (MI355X_MICROARCH.md: twice the bf16 rate of ~2.5 PFLOP/s)
 POOL = 8                     # distinct resident input frames the steps rotate over
+# untimed steps before the timed block, as blocks of K: block rates climb over the first tens of ms of a series of blocks (round 5, 1080p:
+# a first 200-step block at 16.6 k frames/s, the next ones 17.5-18.2 k; 20-step blocks: ~15.0 k for the first eight, median 15.9 k)
+SETTLE_STEPS = 1500
+DUMP_BYTES = 64_000_000      # --dump-outputs: at most this many bytes of .npy files in all (every rank's file together)
 
 # name: (nets [(bundle fixture, description)], Cin, H, W, frames: ("per_gpu", B) weak | ("total", B) strong, description)
 WORKLOADS = {
@@ -100,16 +110,34 @@ def layerwise_bytes_per_px(bundle, in_f32):
     return sum(launch_bytes_per_px(bundle, k, 1, in_f32) for k in range(bundle.L))
 
 
+def dump_array(path, t, max_values, seed=0):
+    """--dump-outputs: tensor t as a float32 .npy -- whole (its own shape) when it holds at most max_values values, else the values at a
+    fixed seeded sample of max_values flat (C-order) indices, ascending, as a 1-D array.  Returns whether it was sampled."""
+    import numpy as np
+    import torch
+    flat = t.reshape(-1)
+    if flat.numel() <= max_values:
+        np.save(path, t.float().cpu().numpy())
+        return False
+    idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), size=max_values, replace=False))
+    np.save(path, flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy())
+    return True
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=0,
-                    help="timed blocks of exactly --steps steps each; value = the MEDIAN block.  0 = auto: max(5, ceil(1500 / steps)) "
-                         "blocks, i.e. at least ~0.1 s of timed work -- at the onset of load the chip's clock dips for 10-20 ms "
-                         "(blocks_fps shows it: 12.2, 10.5, 10.3, 10.9, 11.7 ... 12.5 k frames/s for 20-step blocks), so five "
-                         "20-step blocks (9 ms in all) would sit entirely inside that transient")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed blocks of exactly --steps steps each; value = the MEDIAN block.  Default 1: --steps is the number of timed "
+                         "steps; more blocks are an opt-in of the A/B scripts (tools/)")
+    ap.add_argument("--settle", type=int, default=-1,
+                    help="untimed blocks of --steps steps before the warm-up, each fenced like the timed block: the rate of such blocks climbs "
+                         "over the first tens of ms of a series.  -1 = auto: ceil(SETTLE_STEPS / steps) blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output the timed path returned in its last step to DIR/out_q.npy (float32; "
+                         "a fixed seeded sample where the whole would exceed DUMP_BYTES)")
     ap.add_argument("--batch", type=int, default=0, help="frames per step per GPU (0 = the workload's own)")
     ap.add_argument("--graph", action="store_true", help="replay each step as a captured HIP graph (Engine.capture): same kernels, one "
                                                          "host call per step instead of one per launch")
@@ -145,8 +173,8 @@ def main():
     ap.add_argument("--no-boundary-legs", action="store_true", help="skip the fp32-output / anchor-add throughput legs (boundary_return)")
     args = ap.parse_args()
 
-    if args.repeats <= 0:
-        args.repeats = max(5, -(-1500 // max(1, args.steps)))
+    if args.steps < 1 or args.repeats < 1:
+        raise SystemExit("bench.py: --steps and --repeats must be at least 1")
     plan_streams, plan_slots_per_cu = PLAN.get(args.workload, PLAN_DEFAULT)
     if args.group <= 0:
         args.group = GROUP.get(args.workload, 1)
@@ -236,7 +264,6 @@ def main():
         raise SystemExit("--submit many: single nets, without --graph (a chain interleaves two nets on each stream)")
     sub = None
     if submit_many:
-        import math
         period = POOL * NS // math.gcd(POOL, NS)
         # output buffers: one per stream as in the per-step path; with --group G the G frames that may share a launch sequence (consecutive
         # frames of one stream) get one each: frame i -> buffer (i % NS, (i // NS) % G)
@@ -381,8 +408,30 @@ def main():
                     os.sched_yield()
         torch.cuda.synchronize()
 
+    # untimed settle: the measurement loop itself, blocks of K steps fenced on both sides, results dropped -- the timed block that follows
+    # runs in the state a long series of such blocks reaches (a fixed count: the frame of every later step is the same from run to run)
+    settle = args.settle if args.settle >= 0 else -(-SETTLE_STEPS // args.steps)
+    if settle:
+        run_timed(grp, step, args.steps, 0, repeats=settle, sync=drain, units_per_step=B, step_many=step_many if sub else None)
+
     res = run_timed(grp, step, args.steps, args.warmup, repeats=args.repeats, sync=drain, units_per_step=B, step_many=step_many if sub else None)
     elapsed_med = statistics.median(res["elapsed"])
+
+    dumped = None
+    if args.dump_outputs and B > 0:
+        # what the caller of the timed path received in the last timed step: the int8 output frame(s) of the last frame index enqueued
+        i = counter[0] - 1
+        if graphs:
+            last_q = graphs[(i % NS, i % POOL)].q
+        elif sub is not None:
+            last_q = sub._keep[1][i % sub.n]
+        else:
+            last_q = outs[i % NS][-1]
+        torch.cuda.synchronize()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        fname = "out_q.npy" if world == 1 else f"out_q.rank{rank}.npy"
+        sampled = dump_array(os.path.join(args.dump_outputs, fname), last_q, DUMP_BYTES // 4 // world - 1024)
+        dumped = {"dir": args.dump_outputs, "file": fname, "shape": list(last_q.shape), "pool_frame": i % POOL, "sampled": sampled}
 
     result = None
     if rank == 0:
@@ -456,6 +505,7 @@ def main():
 
         result = {"metric": "INT8 SESR frames/sec (whole job) + PSNR-vs-ref-sim (bit-exact)", "value": round(fps, 2),
                   "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                  "timed_steps": args.steps * args.repeats, "settle_blocks": settle, "dumped_outputs": dumped,
                   "ms_per_step": round(elapsed_med / args.steps * 1e3, 5), "higher_is_better": True,
                   "scaling": "strong" if mode == "total" else "weak",
                   "vs_baseline": None, "dtype": "i8", "data": "synthetic",

@@ -21,6 +21,8 @@ Usage:  python tests/golden/make_golden.py            # all cases (spawns one pr
                                                                    # (SESR-x2 random-init net, 1x3x1080x1920, dump flags off) + SHA-256 of its
                                                                    # int8 / fp32 output -> reference_x2_1080p.json
         python tests/golden/make_golden.py --case anchor          # AnchorOp (sesr_arch.py:171-205) + the eval loop's x2 add (test.py:148-155)
+        python tests/golden/make_golden.py --case synth_ckpt      # the reference's fold + weight quantiser on seeded synthetic checkpoints
+                                                                   # (synthetic_ckpt.py) -> ckpt/synthetic_folds.npz
         python tests/golden/make_golden.py --case sesr_x4_nat     # round 5: a natural-ish frame (tests/golden/natural.py), CALIBRATED ON IT by the
                                                                    # reference (zero_0 < -128 with its consistent scale): crop with every stage, 80x960
                                                                    # SHAs, and a BASELINE-size frame through the reference's sim path (*.big.json)
@@ -492,6 +494,44 @@ def run_anchor(out_dir: str) -> None:
     print("[anchor]", {k: (v.shape if v.ndim else str(v)) for k, v in d.items()}, flush=True)
 
 
+def run_synthetic_checkpoints(out_dir: str) -> None:
+    """The reference's fold (collapse() of its sim model, QAT layouts prepared first, as load_into above) and weight quantiser
+    (quantize_model_weight) on the seeded synthetic checkpoints of synthetic_ckpt.py -> ckpt/synthetic_folds.npz: {case}__Wf{k} / bf{k} / Wq{k}
+    per conv of the collapsed net.  nrdm_6_qat has no reference integer path; its checkpoint is only loaded and folded by the tests."""
+    sys.dont_write_bytecode = True
+    sys.path.insert(0, REF)
+    import torch
+    from myQL import quan_func as qf
+    from models import sesr_sim, nrdm_3_sim
+    from models import quantize_utils_pt as quantize
+    sys.path.insert(0, HERE)
+    from synthetic_ckpt import CASES as SYN, synthetic_state_dict
+    scratch = tempfile.mkdtemp(prefix="golden_", dir=os.path.join(HERE, "..", "..", ".scratch"))
+    os.chdir(scratch)                       # quantize_model_weight writes its output_pt/ tree into the working directory
+    d = {"meta": np.array(json.dumps({c: dict(mflag=m, qat=q, seed=s) for c, (m, q, s) in SYN.items() if m != 4}))}
+    for case, (mflag, qat, _) in SYN.items():
+        if mflag == 4:
+            continue
+        model = {5: sesr_sim.sesr, 3: nrdm_3_sim.nr}[mflag]()
+        model.train()
+        if qat:
+            quantize.prepare(model, inplace=True, a_bits=8, w_bits=8, q_type=0, q_level="C")
+        sd = synthetic_state_dict(model.state_dict(), case)
+        model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=False)
+        model = model.float()
+        model.collapse()
+        convs = [model.conv_first.conv_expand] + [b.conv_expand for b in model.residual_block] + [model.conv_last.conv_expand]
+        names = [next(n for n, m in model.named_modules() if m is c) for c in convs]
+        qm = dict(qf.quantize_model_weight(model, 8, 1).named_modules())
+        for k, (c, n) in enumerate(zip(convs, names)):
+            d[f"{case}__Wf{k}"] = c.weight.detach().numpy().copy()
+            d[f"{case}__bf{k}"] = c.bias.detach().numpy().copy()
+            d[f"{case}__Wq{k}"] = qm[n].weight.detach().numpy().astype(np.int8)
+        print("[synth_ckpt]", case, len(convs), "convs", flush=True)
+    os.makedirs(os.path.join(out_dir, "ckpt"), exist_ok=True)      # a directory of its own: the tests glob the top level for stage fixtures
+    np.savez_compressed(os.path.join(out_dir, "ckpt", "synthetic_folds.npz"), **d)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default=None)
@@ -505,6 +545,8 @@ def main():
         run_case("sesr_x2_rand", HERE, time_1080p=True)
     elif args.case == "anchor":
         run_anchor(HERE)
+    elif args.case == "synth_ckpt":
+        run_synthetic_checkpoints(HERE)
     elif args.case:
         run_case(args.case, HERE, fuzz=args.fuzz)
     else:
@@ -513,7 +555,7 @@ def main():
         for f in ("rand_SR_Input_80x960", "rand_DM_Input_80x960"):
             t = torch.load(os.path.join(REF, f + ".pt"), weights_only=True, map_location="cpu")
             np.save(os.path.join(HERE, f + ".npy"), t.numpy().astype(np.float32))
-        for c in list(CASES) + ["tables", "anchor", "time_x2_1080p"]:
+        for c in list(CASES) + ["tables", "anchor", "synth_ckpt", "time_x2_1080p"]:
             subprocess.run([sys.executable, os.path.abspath(__file__), "--case", c], check=True)
 
 

@@ -57,15 +57,32 @@ def test_collapse_is_the_same_linear_map():
     assert isinstance(net.conv_first.conv_squeeze, torch.nn.Identity) and net.conv_first.conv_expand.weight.shape == (16, 1, 5, 5)
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/model_params/x4sesr.pth"), reason="reference checkpoint not present")
-def test_collapse_of_reference_checkpoint_matches_golden_float_weights():
-    """Build-container only: my closed-form fold vs the reference's delta-image fold on x4sesr.pth."""
-    m = sim.float_model(5, ckpt="/root/reference/model_params/x4sesr.pth")
-    z = np.load(os.path.join(GOLDEN, "sesr_x4.params.npz"))
+def _synthetic_checkpoint(tmp_path, name, case):
+    """tests/golden/synthetic_ckpt.py: the seeded state dict of `case` in the layout of the reference checkpoint `name` (a QAT one
+    prepared first), written to tmp_path/name.  Returns (MFLAG, path)."""
+    import sys
+    from models import quantize_utils_pt as quantize
+    sys.path.insert(0, GOLDEN)
+    from synthetic_ckpt import CASES as SYN, synthetic_state_dict
+    mflag, qat, _ = SYN[case]
+    m = sim.MODELS[mflag]()
+    if qat:
+        quantize.prepare(m, inplace=True, a_bits=8, w_bits=8, q_type=0, q_level="C")
+    p = tmp_path / name
+    torch.save({k: torch.from_numpy(v) for k, v in synthetic_state_dict(m.state_dict(), case).items()}, p)
+    return mflag, str(p)
+
+
+def test_collapse_of_reference_checkpoint_matches_golden_float_weights(tmp_path):
+    """My closed-form fold vs the reference's delta-image fold of the same SESR-x4 checkpoint (layout of x4sesr.pth, seeded
+    synthetic weights: the reference's own fold of it is tests/golden/ckpt/synthetic_folds.npz)."""
+    mflag, ckpt = _synthetic_checkpoint(tmp_path, "x4sesr.pth", "sesr_x4")
+    m = sim.float_model(mflag, ckpt=ckpt)
+    z = np.load(os.path.join(GOLDEN, "ckpt", "synthetic_folds.npz"))
     convs = [m.conv_first.conv_expand] + [b.conv_expand for b in m.residual_block] + [m.conv_last.conv_expand]
     for k, c in enumerate(convs):
-        np.testing.assert_allclose(c.weight.detach().numpy(), z[f"Wf{k}"], rtol=0, atol=2e-6)
-        np.testing.assert_allclose(c.bias.detach().numpy(), z[f"bf{k}"], rtol=0, atol=1e-7)
+        np.testing.assert_allclose(c.weight.detach().numpy(), z[f"sesr_x4__Wf{k}"], rtol=0, atol=2e-6)
+        np.testing.assert_allclose(c.bias.detach().numpy(), z[f"sesr_x4__bf{k}"], rtol=0, atol=1e-7)
 
 
 def test_error_conventions_of_the_callables():
@@ -208,7 +225,7 @@ def test_calibration_graph_is_recognised_on_cpu():
 
 
 @pytest.mark.gpu
-def test_calibrate_then_infer_end_to_end():
+def test_calibrate_then_infer_end_to_end(tmp_path):
     """test.py-equivalent calibration on the reference's random frame, then sim.py-equivalent inference with
     the calibrated domains: the integer output equals the oracle's for the bundle derived from THIS calibration."""
     import importlib
@@ -229,7 +246,7 @@ def test_calibrate_then_infer_end_to_end():
     np.testing.assert_array_equal(y.cpu().numpy(), O.forward(net, x)["y"])
     # the entropy variant through the same entry (two passes over the frames): ranges inside the min/max ones, so scales
     # not larger; the output domain keeps zero = -128 (min := 0); the bundle file it writes loads and runs
-    out = os.path.join(os.environ.get("TMPDIR", "/tmp"), "sesrq_entropy_bundle.npz")
+    out = str(tmp_path / "sesrq_entropy_bundle.npz")
     s2, z2 = calib.main(["--mflag", "5", "--params", os.path.join(GOLDEN, "sesr_x4.params.npz"), "--frames", frames,
                          "--method", "entropy", "--save-bundle", out])
     assert len(s2) == 6 and z2[5] == -128 and all(a_ <= b_ * (1 + 1e-6) for a_, b_ in zip(s2, scale))
@@ -321,49 +338,52 @@ def test_checkpoint_of_another_net_is_refused(tmp_path):
     sim.float_model(3, ckpt=str(p))                   # the right one loads
 
 
-REF_PARAMS = "/root/reference/model_params"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF_PARAMS), reason="reference checkpoints not present (build container only)")
 @pytest.mark.parametrize("ckpt,mflag,case", [("sr_qat_G.pth", 5, "sesr_x4_qat"), ("nrdm_3_qat_G.pth", 3, "nrdm_3_qat")])
-def test_reference_qat_checkpoint_folds_to_the_golden_weights(ckpt, mflag, case):
-    """BASELINE config 1's checkpoint (sr_qat_G.pth) and nrdm_3_qat_G.pth, --ckpt path end to end on the host: QAT fold ->
-    the collapsed float32 weights the reference itself derived (tests/golden/*_qat.params.npz, written by running the
-    reference: same torch ops on the same shapes, so equal to the BIT) -> weight quantiser -> the reference's Wq."""
+def test_reference_qat_checkpoint_folds_to_the_golden_weights(ckpt, mflag, case, tmp_path):
+    """A checkpoint in the layout of BASELINE config 1's sr_qat_G.pth / of nrdm_3_qat_G.pth (seeded synthetic weights), --ckpt path
+    end to end on the host: QAT fold -> the collapsed float32 weights the reference's own fold gives for it
+    (tests/golden/ckpt/synthetic_folds.npz: same torch ops on the same shapes, so equal to the BIT) -> weight quantiser -> the
+    reference's Wq."""
     STORE.clear()
     fx, meta = load_fixture(os.path.join(GOLDEN, f"{case}.crop.npz"))
     STORE.set_activation_domains(meta["scale"], meta["zero"])
-    fm = sim.float_model(mflag, ckpt=os.path.join(REF_PARAMS, ckpt))
-    z = np.load(os.path.join(GOLDEN, f"{case}.params.npz"))
+    got_mflag, path = _synthetic_checkpoint(tmp_path, ckpt, case)
+    assert got_mflag == mflag
+    fm = sim.float_model(mflag, ckpt=path)
+    z = np.load(os.path.join(GOLDEN, "ckpt", "synthetic_folds.npz"))
     convs = [fm.conv_first.conv_expand] + [b.conv_expand for b in fm.residual_block] + [fm.conv_last.conv_expand]
     for k, c in enumerate(convs):
-        np.testing.assert_array_equal(c.weight.detach().numpy(), z[f"Wf{k}"])
-        np.testing.assert_array_equal(c.bias.detach().numpy(), z[f"bf{k}"])
+        np.testing.assert_array_equal(c.weight.detach().numpy(), z[f"{case}__Wf{k}"])
+        np.testing.assert_array_equal(c.bias.detach().numpy(), z[f"{case}__bf{k}"])
     b = sim.splice(fm).sesrq_bundle()
     for k in range(5):
-        np.testing.assert_array_equal(b.layers[k].wq, fx[f"Wq{k}"])
+        np.testing.assert_array_equal(b.layers[k].wq, z[f"{case}__Wq{k}"])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PARAMS), reason="reference checkpoints not present (build container only)")
-def test_reference_nrdm6_qat_checkpoint_loads_and_folds():
-    """nrdm_6_qat_G.pth (8 convs): loads key for key and folds; no golden (the reference has no integer path at this depth)."""
-    fm = sim.float_model(4, ckpt=os.path.join(REF_PARAMS, "nrdm_6_qat_G.pth"))
+def test_reference_nrdm6_qat_checkpoint_loads_and_folds(tmp_path):
+    """A checkpoint in the layout of nrdm_6_qat_G.pth (8 convs, seeded synthetic weights): loads key for key and folds; no golden
+    (the reference has no integer path at this depth)."""
+    mflag, path = _synthetic_checkpoint(tmp_path, "nrdm_6_qat_G.pth", "nrdm_6_qat")
+    fm = sim.float_model(mflag, ckpt=path)
     assert len(fm.residual_block) == 6 and all(type(b.conv_expand) is torch.nn.Conv2d for b in fm.residual_block)
     assert all(torch.isfinite(b.conv_expand.weight).all() for b in fm.residual_block)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PARAMS), reason="reference checkpoints not present (build container only)")
 @pytest.mark.parametrize("ckpt,mflag,case", [("x4sesr.pth", 5, "sesr_x4"), ("nrdm_3_raw_G.pth", 3, "nrdm_3")])
-def test_reference_float_checkpoint_gives_the_golden_int8_weights(ckpt, mflag, case):
+def test_reference_float_checkpoint_gives_the_golden_int8_weights(ckpt, mflag, case, tmp_path):
     """--ckpt path end to end on the host: load (strict) -> closed-form collapse -> weight quantiser == the Wq the
-    reference produced from the same checkpoint (0 mismatching INT8 weights)."""
+    reference produces from the same checkpoint (layout of x4sesr.pth / nrdm_3_raw_G.pth, seeded synthetic weights; 0
+    mismatching INT8 weights)."""
     STORE.clear()
     fx, meta = load_fixture(os.path.join(GOLDEN, f"{case}.crop.npz"))
     STORE.set_activation_domains(meta["scale"], meta["zero"])
-    model = sim.splice(sim.float_model(mflag, ckpt=os.path.join(REF_PARAMS, ckpt)))
+    got_mflag, path = _synthetic_checkpoint(tmp_path, ckpt, case)
+    assert got_mflag == mflag
+    model = sim.splice(sim.float_model(mflag, ckpt=path))
     b = model.sesrq_bundle()
+    z = np.load(os.path.join(GOLDEN, "ckpt", "synthetic_folds.npz"))
     for k in range(5):
-        np.testing.assert_array_equal(b.layers[k].wq, fx[f"Wq{k}"])
+        np.testing.assert_array_equal(b.layers[k].wq, z[f"{case}__Wq{k}"])
 
 
 def test_registered_torch_op_schema_and_fake_kernel():
