@@ -144,6 +144,7 @@ class Engine:
                                "there is no CPU fallback in this package")
         self.bundle = bundle
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.anchor_add = bool(anchor_add)          # the fp32 output carries the x2 anchor (sesrq.quality.evaluate checks it)
         L = bundle.L
         self._keep = []
         layers = (_lib.LayerDesc * L)()

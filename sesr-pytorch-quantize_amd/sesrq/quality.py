@@ -1,0 +1,161 @@
+"""PSNR / SSIM of output frames on the device: the reference's evaluation loop (test.py:141-183).
+
+ctypes binding of libsesrq_eval.so (C ABI declared in include/sesrq_eval.h), ``score()`` for a batch of frames already on the
+device, and ``evaluate()``: forward + score over a set of frames, one synchronisation at the end.  There is no CPU path: scoring
+needs the device, as the forward does.
+
+The metric form follows the network (MFLAG, reference sim.py ``MODELS``):
+  3, 4  nrdm_small / nrdm_big  RGB   skimage PSNR (data_range 1), SSIM = mean over the three channels
+  5     srx4                   Y255  compute_psnr(255 gt, 255 pred) (eps 1e-8), single-channel SSIM
+  6     srx2                   X2    compute_psnr(rgb_to_yuv(gt), rgb_to_yuv(pred)) on the anchored output, SSIM as RGB
+The prediction is clipped to [0, 1] first; the ground truth is not.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "lib", "libsesrq_eval.so"))
+
+FORM_RGB, FORM_Y255, FORM_X2 = 0, 1, 2
+PRED_F32, PRED_I8 = 0, 1
+FORMS = {3: FORM_RGB, 4: FORM_RGB, 5: FORM_Y255, 6: FORM_X2}
+CHANNELS = {FORM_RGB: 3, FORM_Y255: 1, FORM_X2: 3}
+TASKS = {1: "nr", 2: "dm", 3: "nrdm_small", 4: "nrdm_big", 5: "srx4", 6: "srx2"}     # reference test.py:182
+
+
+class EvalDesc(C.Structure):
+    _fields_ = [("form", C.c_int32), ("pred_dtype", C.c_int32), ("pred_scale", C.c_float), ("pred_zero", C.c_int32)]
+
+
+# every symbol include/sesrq_eval.h declares: name -> (restype, argtypes)
+SYMBOLS = {
+    "sesrq_eval_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sesrq_eval": (C.c_int, [C.POINTER(EvalDesc), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                             C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sesrq_eval_kernel_count": (C.c_int, []),
+    "sesrq_eval_kernel_name": (C.c_char_p, [C.c_int]),
+    "sesrq_eval_kernel_launches": (C.c_longlong, [C.c_int]),
+    "sesrq_eval_last_error": (C.c_char_p, []),
+}
+
+_lib = None
+
+
+def lib() -> C.CDLL:
+    """Load libsesrq_eval.so once and bind every declared symbol; raise loudly when it is absent."""
+    global _lib
+    if _lib is None:
+        if not os.path.isfile(LIB_PATH):
+            raise RuntimeError(f"sesrq.quality: native library not found at {LIB_PATH}. Build it with "
+                               "`make -C sesr-pytorch-quantize_amd/csrc` (or __graft_entry__.build()); there is no fallback path.")
+        try:                      # one HIP runtime per process: torch's, mapped before the library (see _lib.lib())
+            import torch  # noqa: F401
+        except ImportError:
+            pass
+        handle = C.CDLL(LIB_PATH)
+        for name, (res, args) in SYMBOLS.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = res, args
+        _lib = handle
+    return _lib
+
+
+def last_error() -> str:
+    return (lib().sesrq_eval_last_error() or b"").decode()
+
+
+def kernels():
+    """{name: launches so far} of every kernel instantiation libsesrq_eval.so can launch."""
+    l = lib()
+    return {l.sesrq_eval_kernel_name(i).decode(): int(l.sesrq_eval_kernel_launches(i)) for i in range(l.sesrq_eval_kernel_count())}
+
+
+def form_of(mflag: int) -> int:
+    if mflag not in FORMS:
+        raise ValueError(f"MFLAG {mflag}: only 3, 4 (RGB), 5 (srx4) and 6 (srx2) have a metric on the integer path")
+    return FORMS[mflag]
+
+
+def score(pred, gt, mflag: int, scale=None, zero=None, stream=None):
+    """(mse, psnr, ssim) per frame as a device float64 tensor of shape (N, 3), enqueued on `stream` (default: current), not synchronised.
+
+    pred: (N, C, H, W) float32 output frames, or int8 output frames with the net's output domain (scale = f32(input.L.scale),
+    zero = zero[L]), dequantised on the device to the bits of the float output; gt: float32 of the same shape and device.
+    For MFLAG 6, pred is the anchored float output (Engine(..., anchor_add=True))."""
+    import torch
+    form = form_of(mflag)
+    if not isinstance(pred, torch.Tensor) or not isinstance(gt, torch.Tensor):
+        raise ValueError("pred and gt must be torch tensors")
+    if pred.dim() != 4 or tuple(pred.shape) != tuple(gt.shape):
+        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must both be (N, C, H, W) of one shape")
+    N, Ch, H, W = pred.shape
+    if Ch != CHANNELS[form]:
+        raise ValueError(f"MFLAG {mflag} scores {CHANNELS[form]}-channel frames, got {Ch}")
+    if H < 7 or W < 7:
+        raise ValueError(f"frame {H}x{W} is smaller than the 7x7 SSIM window")
+    if N < 1:
+        raise ValueError("no frames")
+    if pred.device.type != "cuda" or gt.device != pred.device:
+        raise ValueError(f"pred ({pred.device}) and gt ({gt.device}) must be on one HIP device")
+    if gt.dtype != torch.float32:
+        raise ValueError("gt must be float32")
+    d = EvalDesc(form=form, pred_dtype=PRED_F32, pred_scale=0.0, pred_zero=0)
+    if pred.dtype == torch.int8:
+        if scale is None or zero is None:
+            raise ValueError("an int8 prediction needs the output domain: scale and zero")
+        if form == FORM_X2:
+            raise ValueError("MFLAG 6 scores the anchored float output; the anchor does not exist in the int8 output")
+        d.pred_dtype, d.pred_scale, d.pred_zero = PRED_I8, float(scale), int(zero)
+    elif pred.dtype != torch.float32:
+        raise ValueError("pred must be float32 or int8")
+    dev = pred.device
+    with torch.cuda.device(dev):
+        pred, gt = pred.contiguous(), gt.contiguous()
+        out = torch.empty((N, 3), dtype=torch.float64, device=dev)
+        ws = torch.empty(max(1, lib().sesrq_eval_workspace_bytes(N, Ch, H, W)), dtype=torch.uint8, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        st = cur if stream is None else stream
+        if st != cur:             # ordered behind the work that produced the frames; the memory stays alive until it has run
+            st.wait_stream(cur)
+            for t in (pred, gt, out, ws):
+                t.record_stream(st)
+        rc = lib().sesrq_eval(C.byref(d), pred.data_ptr(), gt.data_ptr(), N, Ch, H, W, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                              st.cuda_stream)
+    if rc != 0:
+        raise ValueError("sesrq_eval: " + last_error())
+    return out
+
+
+def evaluate(engine, frames, gts, mflag: int):
+    """The reference's dataset loop on the device: per frame a forward and its metrics; one synchronisation at the end.
+
+    frames: iterable of (1, Cin, H, W) float32 input frames (or one (N, Cin, H, W) tensor, taken frame by frame); gts: the matching
+    ground truths of the output shape.  MFLAG 3 / 4 / 5: the forward writes only the int8 output, which is scored in the net's output
+    domain (bundle.scale[L], bundle.zero[L]).  MFLAG 6: the forward writes only the anchored float output; the engine must have
+    been created with anchor_add=True.  Returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
+    import torch
+    form = form_of(mflag)
+    if form == FORM_X2 and not getattr(engine, "anchor_add", False):
+        raise ValueError("MFLAG 6 is scored on the anchored output: create the engine with anchor_add=True")
+    b = engine.bundle
+    L = b.L
+    scale, zero = float(b.scale[L]), int(b.zero[L])
+    dev = engine.device
+    rows = []
+    for x, g in zip(frames, gts):
+        x = x if x.dim() == 4 else x.unsqueeze(0)
+        g = g if g.dim() == 4 else g.unsqueeze(0)
+        x, g = x.to(dev, non_blocking=True), g.to(dev, dtype=torch.float32, non_blocking=True)
+        if form == FORM_X2:
+            _, y = engine.forward(x, want_q=False, want_f=True)
+            rows.append(score(y, g, mflag))
+        else:
+            q, _ = engine.forward(x, want_q=True, want_f=False)
+            rows.append(score(q, g, mflag, scale=scale, zero=zero))
+    if not rows:
+        raise ValueError("no frames")
+    res = torch.cat(rows)
+    torch.cuda.synchronize(dev)
+    return res.cpu().numpy()

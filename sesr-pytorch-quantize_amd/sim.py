@@ -123,6 +123,8 @@ def main(argv=None):
     ap.add_argument("--calib", help="output_pt directory written by the reference's test.py")
     ap.add_argument("--input", required=True, help="frame tensor: .pt (torch) or .npy, shape (N,C,H,W) float32")
     ap.add_argument("--save", help="write the float result here (.npy)")
+    ap.add_argument("--gt", help="ground truth of the output shape (N,Cout,H*r,W*r) float32, .npy or .pt: score the output with the "
+                                 "reference's PSNR / SSIM on the device (test.py:141-183) and print them as its loop does")
     ap.add_argument("--dump", help="write the parameter store as an output_pt-compatible tree here (what the define.py *_W_FLG "
                                    "switches select, plus weights and activation domains); all dump switches are turned on")
     args = ap.parse_args(argv)
@@ -146,7 +148,34 @@ def main(argv=None):
     if args.dump:
         STORE.save_output_pt(args.dump)
         print("dumped:", args.dump)
+    if args.gt:
+        score_against(args.gt, gfake, inps, args.mflag)
     return gfake
+
+
+def load_frames(path):
+    return torch.load(path, weights_only=True, map_location="cpu") if path.endswith(".pt") else torch.from_numpy(np.load(path))
+
+
+def score_against(path, gfake, inps, mflag):
+    """The reference's evaluation loop (test.py:141-183) on the device: anchor for MFLAG 6, clip, PSNR / SSIM per frame; prints each
+    frame's PSNR and the mean line.  Returns the (N, 3) float64 host array of (mse, psnr, ssim)."""
+    from sesrq import quality
+    gts = load_frames(path)
+    if tuple(gts.shape) != tuple(gfake.shape):
+        raise SystemExit(f"sim.py: --gt has shape {tuple(gts.shape)}, the output is {tuple(gfake.shape)}")
+    pred = gfake
+    if mflag == 6:                                  # test.py:149-155: + the nearest-upsampled input
+        x = inps.float().to(gfake.device)
+        pred = gfake + x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
+    res = quality.score(pred, gts.float().to(gfake.device), mflag).cpu().numpy()
+    totalpsnr = totalssim = 0.0
+    for _, psnr, ssim in res:
+        print(float(psnr))
+        totalpsnr += float(psnr)
+        totalssim += float(ssim)
+    print(quality.TASKS[mflag] + ' mean psnr is: ', totalpsnr / len(res), ' ssim is: ', totalssim / len(res))
+    return res
 
 
 if __name__ == "__main__":
