@@ -184,11 +184,14 @@ class Engine:
         if upstream is not None:
             opts.i8_in_scale = float(np.float32(upstream.scale[upstream.L]))
             opts.i8_in_zero = int(upstream.zero[upstream.L])
+        self.exact_div = int(opts.exact_div)         # how x / s0 is formed: the raw route's q0 table forms it the same way
+        self.i8_in_scale = float(opts.i8_in_scale)   # > 0: an int8 input is an upstream net's output, not q0 (forward_raw refuses)
         handle = C.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().sesrq_create(C.byref(desc), C.byref(opts), C.byref(handle)), ValueError)
         self._h = handle
         self._ws: Dict[tuple, torch.Tensor] = {}
+        self._raw_q0: Dict[tuple, torch.Tensor] = {}
 
     def close(self):
         if getattr(self, "_op_id", None):      # registered as a torch.ops.sesrq.forward handle: the C++ side drops its pointer first
@@ -302,6 +305,45 @@ class Engine:
         return out_q, out_f
 
     __call__ = forward
+
+    def forward_raw(self, raw: torch.Tensor, want_q: bool = True, want_f: bool = True, out_q=None, out_f=None, stream=None,
+                    slot: int = 0):
+        """raw: (N, 1, H, W) or (N, H, W) torch.uint16 12-bit RGGB frames on self.device -> (q int8 | None, y float32 | None).
+
+        The frames are unpacked on the device (libsesrq_raw.so, sesrq.raw) into this net's q0 -- a per-(N, H, W, slot) buffer the
+        engine keeps -- and run through the same forward as an int8 q0 input: the results are those of forward() on the reference's
+        fp32 input frame (self_dataset.py TestDataset).  Both launches go to `stream` (default: current), ordered as forward() orders
+        them; give concurrent in-flight frames different slots.  Only for nets with 3 input channels whose int8 input is q0 (no
+        `upstream`) and without the fp32 anchor."""
+        from . import raw as rawmod
+        if self.bundle.in_channels != 3:
+            raise ValueError(f"forward_raw: a raw RGGB frame feeds 3-channel nets; this one takes {self.bundle.in_channels}")
+        if self.i8_in_scale != 0.0:
+            raise ValueError("forward_raw: this engine takes an upstream net's int8 output as input (upstream=...), not q0")
+        if self.anchor_add:
+            raise ValueError("forward_raw: anchor_add needs the fp32 input frame; use raw.unpack(..., want_spread=True) and forward()")
+        if not (want_q or want_f):
+            raise ValueError("forward_raw: ask for the int8 output, the fp32 output or both")
+        raw = rawmod._frames(raw, self.device)
+        N, H, W = raw.shape
+        with torch.cuda.device(self.device):
+            raw = raw.contiguous()
+            key = (N, H, W, slot)
+            q0 = self._raw_q0.get(key)
+            if q0 is None:
+                q0 = self._raw_q0[key] = torch.empty((N, 3, H, W), dtype=torch.int8, device=self.device)
+            shp = self.out_shape(N, H, W)
+            if want_q and out_q is None:
+                out_q = torch.empty(shp, dtype=torch.int8, device=self.device)
+            if want_f and out_f is None:
+                out_f = torch.empty(shp, dtype=torch.float32, device=self.device)
+            ws = self.workspace(N, H, W, slot)
+            st = self._enter_stream(stream, raw, q0, out_q, out_f, ws)
+            rawmod.launch(self.device, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, raw, q0, None, st)
+            rc = _lib.lib().sesrq_forward(self._h, q0.data_ptr(), _lib.I8, out_q.data_ptr() if want_q else None,
+                                          out_f.data_ptr() if want_f else None, N, H, W, ws.data_ptr(), ws.numel(), st.cuda_stream)
+        _lib.check(rc)
+        return (out_q if want_q else None), (out_f if want_f else None)
 
     def submission(self, frames, outs_q, streams, outs_f=None, group: int = 1):
         """A prepared batch of independent forwards for sesrq_forward_many: frame k = frames[k] -> outs_q[k] (/ outs_f[k]; either may be None) on

@@ -159,3 +159,32 @@ def evaluate(engine, frames, gts, mflag: int):
     res = torch.cat(rows)
     torch.cuda.synchronize(dev)
     return res.cpu().numpy()
+
+
+def evaluate_raw(engine, raws, gts_u16, mflag: int):
+    """The reference's MFLAG 3 / 4 loop from raw frames to scores (test.py:30-55 with self_dataset.py TestDataset): per frame the
+    12-bit RGGB raw frame is unpacked on the device into the net's q0 and run forward (Engine.forward_raw), its 16-bit RGB ground
+    truth is mapped to / 4095 and clamped on the device (sesrq.raw.load_gt), and the int8 output is scored as evaluate() scores it.
+
+    raws: iterable of (1, 1, H, W) / (1, H, W) / (H, W) uint16 frames (numpy or torch; uploaded at 2 B/px), or one (N, 1, H, W)
+    tensor taken frame by frame; gts_u16: the matching (3, H, W) / (1, 3, H, W) uint16 RGB frames.  One synchronisation at the end;
+    returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
+    import numpy as np
+    import torch
+    from . import raw as rawmod
+    if form_of(mflag) != FORM_RGB:
+        raise ValueError(f"MFLAG {mflag}: raw RGGB frames feed the denoise / demosaic nets (MFLAG 3, 4)")
+    b = engine.bundle
+    scale, zero = float(b.scale[b.L]), int(b.zero[b.L])
+    dev = engine.device
+    rows = []
+    for r, g in zip(raws, gts_u16):
+        r = torch.from_numpy(np.ascontiguousarray(r)) if isinstance(r, np.ndarray) else r
+        r = r.to(dev, non_blocking=True)
+        q, _ = engine.forward_raw(r, want_q=True, want_f=False)
+        rows.append(score(q, rawmod.load_gt(g, dev), mflag, scale=scale, zero=zero))
+    if not rows:
+        raise ValueError("no frames")
+    res = torch.cat(rows)
+    torch.cuda.synchronize(dev)
+    return res.cpu().numpy()

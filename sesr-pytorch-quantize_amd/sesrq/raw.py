@@ -1,0 +1,208 @@
+"""12-bit RGGB Bayer raw frames into the 3-channel nets: the input side of the reference's evaluation loop.
+
+The reference (self_dataset.py TestDataset.__getitem__) reads ``<name>_<rows>_<cols>.raw`` (uint16, row-major), spreads it into a
+sparse 3-channel RGGB mosaic (R at (even, even), G at (even, odd) and (odd, even), B at (odd, odd), zeros elsewhere), divides by
+2**12 - 1 in fp32 and clamps to [0, 1]; its ground truth is a 16-bit RGB image treated the same way.  Here the raw frame goes to
+the device as it is (2 B/px) and libsesrq_raw.so (C ABI include/sesrq_raw.h) turns it into the net's q0 -- the int8 input of
+sesrq_forward -- and, when asked, into the reference's fp32 ``inp``, bit for bit.  There is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "lib", "libsesrq_raw.so"))
+
+CODES = 4096
+WHITE = CODES - 1           # 2**12 - 1
+
+# every symbol include/sesrq_raw.h declares: name -> (restype, argtypes)
+SYMBOLS = {
+    "sesrq_raw_table": (C.c_int, [C.c_float, C.c_int, C.c_int, C.c_void_p]),
+    "sesrq_raw_create": (C.c_int, [C.c_float, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "sesrq_raw_destroy": (None, [C.c_void_p]),
+    "sesrq_raw_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "sesrq_raw_instance_count": (C.c_int, []),
+    "sesrq_raw_instance_name": (C.c_char_p, [C.c_int]),
+    "sesrq_raw_instance_launches": (C.c_longlong, [C.c_int]),
+    "sesrq_raw_last_error": (C.c_char_p, []),
+}
+
+_lib = None
+_ctx = {}                   # (device index, f32 scale bits, zero, exact_div) -> context handle; lives as long as the process
+
+
+def lib() -> C.CDLL:
+    """Load libsesrq_raw.so once and bind every declared symbol; raise loudly when it is absent."""
+    global _lib
+    if _lib is None:
+        if not os.path.isfile(LIB_PATH):
+            raise RuntimeError(f"sesrq.raw: native library not found at {LIB_PATH}. Build it with "
+                               "`make -C sesr-pytorch-quantize_amd/csrc` (or __graft_entry__.build()); there is no fallback path.")
+        try:                      # one HIP runtime per process: torch's, mapped before the library (see _lib.lib())
+            import torch  # noqa: F401
+        except ImportError:
+            pass
+        handle = C.CDLL(LIB_PATH)
+        for name, (res, args) in SYMBOLS.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = res, args
+        _lib = handle
+    return _lib
+
+
+def last_error() -> str:
+    return (lib().sesrq_raw_last_error() or b"").decode()
+
+
+def instances():
+    """{name: launches so far} of every kernel instantiation libsesrq_raw.so can launch."""
+    l = lib()
+    return {l.sesrq_raw_instance_name(i).decode(): int(l.sesrq_raw_instance_launches(i)) for i in range(l.sesrq_raw_instance_count())}
+
+
+def table(scale_in: float, zero_in: int, exact_div: int = 0) -> np.ndarray:
+    """q0 of every code 0 .. 4095 (host): clamp8(rint(x / s0 + z0)) with x = clamp(fl32(code) / 4095, 0, 1).  exact_div as
+    sesrq_options.exact_div (0 / 1: the true quotient, 2: x * fl(1 / s0))."""
+    out = np.empty(CODES, np.int8)
+    if lib().sesrq_raw_table(float(np.float32(scale_in)), int(zero_in), int(exact_div), out.ctypes.data) != 0:
+        raise ValueError(last_error())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ files
+def raw_size(path: str):
+    """(rows, cols) from a reference raw file name ``<name>_<rows>_<cols>.raw``: the basename's last two '_' fields."""
+    base = os.path.basename(path)
+    stem, ext = os.path.splitext(base)
+    parts = stem.split("_")
+    if ext.lower() != ".raw" or len(parts) < 3:
+        raise ValueError(f"{path}: a raw frame is named <name>_<rows>_<cols>.raw")
+    try:
+        rows, cols = int(parts[-2]), int(parts[-1])
+    except ValueError:
+        raise ValueError(f"{path}: rows / cols in <name>_<rows>_<cols>.raw are not integers") from None
+    if rows < 1 or cols < 1:
+        raise ValueError(f"{path}: empty frame {rows} x {cols}")
+    return rows, cols
+
+
+def load_raw(path: str) -> np.ndarray:
+    """A reference raw frame as a (rows, cols) uint16 array (little-endian file, row-major, as np.fromfile reads it there)."""
+    rows, cols = raw_size(path)
+    nbytes = os.path.getsize(path)
+    if nbytes != 2 * rows * cols:
+        raise ValueError(f"{path}: {nbytes} bytes, a {rows} x {cols} uint16 frame has {2 * rows * cols}")
+    return np.fromfile(path, dtype="<u2").reshape(rows, cols).astype(np.uint16, copy=False)
+
+
+_levels = {}
+
+
+def load_gt(array_u16, device=None):
+    """Ground truth of the raw route: a 16-bit RGB frame (N, 3, H, W) or (3, H, W), numpy or torch uint16, as device fp32 (N, 3, H, W)
+    = clamp(fl32(v) / 4095, 0, 1), the reference's true fp32 quotient (self_dataset.py:235-243): codes are uploaded at 2 B/px and mapped
+    on the device through the 4096 quotients formed on the host (a GPU tensor / scalar division would multiply by fl(1 / 4095))."""
+    import torch
+    g = torch.from_numpy(np.ascontiguousarray(array_u16)) if isinstance(array_u16, np.ndarray) else array_u16
+    if not isinstance(g, torch.Tensor) or g.dtype != torch.uint16:
+        raise ValueError("load_gt: the ground truth must be a uint16 array or tensor")
+    if g.dim() == 3:
+        g = g.unsqueeze(0)
+    if g.dim() != 4 or g.shape[1] != 3:
+        raise ValueError(f"load_gt: expected an RGB frame (N, 3, H, W), got {tuple(g.shape)}")
+    dev = torch.device(device) if device is not None else (g.device if g.device.type == "cuda" else
+                                                           torch.device("cuda", torch.cuda.current_device()))
+    lv = _levels.get(dev)
+    if lv is None:
+        codes = np.arange(CODES, dtype=np.float32)
+        lv = _levels[dev] = torch.from_numpy(np.clip(codes / np.float32(WHITE), np.float32(0), np.float32(1))).to(dev)
+    idx = g.to(dev, non_blocking=True).to(torch.int32).clamp_(max=WHITE)
+    return lv[idx.long()]
+
+
+# ------------------------------------------------------------------------------------------------------------------ device
+def _handle(device, scale_in, zero_in, exact_div):
+    import torch
+    key = (device.index, np.float32(scale_in).tobytes(), int(zero_in), int(exact_div))
+    h = _ctx.get(key)
+    if h is None:
+        h = C.c_void_p()
+        with torch.cuda.device(device):
+            if lib().sesrq_raw_create(float(np.float32(scale_in)), int(zero_in), int(exact_div), C.byref(h)) != 0:
+                raise ValueError(last_error())
+        _ctx[key] = h
+    return h
+
+
+def _frames(raw, device):
+    """(N, H, W) view of a (N, 1, H, W) / (N, H, W) / (H, W) uint16 device tensor."""
+    import torch
+    if not isinstance(raw, torch.Tensor) or raw.dtype != torch.uint16:
+        raise ValueError("a raw frame must be a torch.uint16 tensor (N, 1, H, W) or (N, H, W)")
+    if raw.dim() == 4:
+        if raw.shape[1] != 1:
+            raise ValueError(f"a raw frame has one channel, got {tuple(raw.shape)}")
+        raw = raw.reshape(raw.shape[0], raw.shape[2], raw.shape[3])
+    elif raw.dim() == 2:
+        raw = raw.unsqueeze(0)
+    if raw.dim() != 3 or min(raw.shape) < 1:
+        raise ValueError(f"a raw frame is (N, 1, H, W) or (N, H, W), got {tuple(raw.shape)}")
+    if raw.device != device:
+        raise ValueError(f"raw frame is on {raw.device}, expected {device}")
+    return raw
+
+
+def launch(device, scale_in, zero_in, exact_div, raw, q0, spread, stream):
+    """Enqueue one unpack of the (N, H, W) contiguous uint16 `raw` into caller-owned q0 / spread (either may be None) on `stream`."""
+    N, H, W = raw.shape
+    h = _handle(device, scale_in, zero_in, exact_div)
+    rc = lib().sesrq_raw_unpack(h, raw.data_ptr(), q0.data_ptr() if q0 is not None else None,
+                                spread.data_ptr() if spread is not None else None, N, H, W, stream.cuda_stream)
+    if rc != 0:
+        raise ValueError(last_error())
+
+
+def unpack(engine_or_bundle, raw, want_q: bool = True, want_spread: bool = False, stream=None):
+    """raw: (N, 1, H, W) or (N, H, W) torch.uint16 on a HIP device -> (q0 int8 (N, 3, H, W) | None, spread fp32 (N, 3, H, W) | None).
+
+    q0 is in the input domain of the net (engine.bundle or the bundle itself: scale[0], zero[0]; an Engine also fixes how x / s0 is
+    formed, its exact_div); spread is the reference's fp32 input frame (engine_or_bundle may be None when only spread is asked for).  Enqueued on `stream` (default: current), not synchronised."""
+    import torch
+    from .bundle import Bundle
+    if not (want_q or want_spread):
+        raise ValueError("unpack: ask for q0, spread or both")
+    if engine_or_bundle is None:          # the fp32 frame alone: no input domain involved
+        if want_q:
+            raise ValueError("unpack: q0 needs the net's input domain (an Engine or a Bundle)")
+        scale_in, zero_in, exact_div = 1.0, 0, 0
+        dev = raw.device if isinstance(raw, torch.Tensor) else None
+    else:
+        if isinstance(engine_or_bundle, Bundle):
+            b, exact_div = engine_or_bundle, 0
+            dev = raw.device if isinstance(raw, torch.Tensor) else None
+        else:
+            b, exact_div, dev = engine_or_bundle.bundle, engine_or_bundle.exact_div, engine_or_bundle.device
+        if b.in_channels != 3:
+            raise ValueError(f"a raw RGGB frame feeds 3-channel nets; this one takes {b.in_channels}")
+        scale_in, zero_in = b.scale[0], b.zero[0]
+    raw = _frames(raw, dev)
+    if dev is None or dev.type != "cuda":
+        raise ValueError("the raw frame must be on a HIP device")
+    N, H, W = raw.shape
+    with torch.cuda.device(dev):
+        raw = raw.contiguous()
+        q0 = torch.empty((N, 3, H, W), dtype=torch.int8, device=dev) if want_q else None
+        sp = torch.empty((N, 3, H, W), dtype=torch.float32, device=dev) if want_spread else None
+        cur = torch.cuda.current_stream(dev)
+        st = cur if stream is None else stream
+        if st != cur:             # ordered behind the work that produced the frame; the memory stays alive until it has run
+            st.wait_stream(cur)
+            for t in (raw, q0, sp):
+                if t is not None:
+                    t.record_stream(st)
+        launch(dev, scale_in, zero_in, exact_div, raw, q0, sp, st)
+    return q0, sp

@@ -121,10 +121,13 @@ def main(argv=None):
     ap.add_argument("--ckpt", help="reference float checkpoint (.pth state_dict)")
     ap.add_argument("--params", help=".npz with collapsed float convs (+ calibrated domains)")
     ap.add_argument("--calib", help="output_pt directory written by the reference's test.py")
-    ap.add_argument("--input", required=True, help="frame tensor: .pt (torch) or .npy, shape (N,C,H,W) float32")
+    ap.add_argument("--input", required=True, help="frame tensor: .pt (torch) or .npy, shape (N,C,H,W) float32; or a 12-bit RGGB raw frame "
+                                                   "<name>_<rows>_<cols>.raw (uint16), spread on the device into the reference's "
+                                                   "3-channel input (self_dataset.py TestDataset)")
     ap.add_argument("--save", help="write the float result here (.npy)")
     ap.add_argument("--gt", help="ground truth of the output shape (N,Cout,H*r,W*r) float32, .npy or .pt: score the output with the "
-                                 "reference's PSNR / SSIM on the device (test.py:141-183) and print them as its loop does")
+                                 "reference's PSNR / SSIM on the device (test.py:141-183) and print them as its loop does; a uint16 "
+                                 "(N,3,H,W) RGB ground truth is taken / 4095 and clamped, as the reference's TestDataset does")
     ap.add_argument("--dump", help="write the parameter store as an output_pt-compatible tree here (what the define.py *_W_FLG "
                                    "switches select, plus weights and activation domains); all dump switches are turned on")
     args = ap.parse_args(argv)
@@ -135,10 +138,14 @@ def main(argv=None):
     if args.calib:
         STORE.load_output_pt(args.calib)
     model = splice(float_model(args.mflag, args.ckpt, args.params))
-    inps = torch.load(args.input, weights_only=True, map_location="cpu") if args.input.endswith(".pt") else \
-        torch.from_numpy(np.load(args.input))
+    if not args.input.endswith(".raw"):
+        inps = torch.load(args.input, weights_only=True, map_location="cpu") if args.input.endswith(".pt") else \
+            torch.from_numpy(np.load(args.input))
     if not torch.cuda.is_available():
         raise SystemExit("sim.py: the integer path needs a HIP device (no CPU fallback)")
+    if args.input.endswith(".raw"):         # the reference's loop: raw frame -> sparse RGGB mosaic / 4095, clamped -> model(inps)
+        from sesrq import raw
+        _, inps = raw.unpack(None, torch.from_numpy(raw.load_raw(args.input)).cuda(), want_q=False, want_spread=True)
     gfake = model(inps.float().cuda())
     torch.cuda.synchronize()
     banner(args.mflag)
@@ -164,6 +171,9 @@ def score_against(path, gfake, inps, mflag):
     gts = load_frames(path)
     if tuple(gts.shape) != tuple(gfake.shape):
         raise SystemExit(f"sim.py: --gt has shape {tuple(gts.shape)}, the output is {tuple(gfake.shape)}")
+    if gts.dtype == torch.uint16:                   # 16-bit RGB ground truth: / 4095, clamped (self_dataset.py:235-243)
+        from sesrq import raw
+        gts = raw.load_gt(gts, gfake.device)
     pred = gfake
     if mflag == 6:                                  # test.py:149-155: + the nearest-upsampled input
         x = inps.float().to(gfake.device)
