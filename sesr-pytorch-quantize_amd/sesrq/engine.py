@@ -192,6 +192,7 @@ class Engine:
         self._h = handle
         self._ws: Dict[tuple, torch.Tensor] = {}
         self._raw_q0: Dict[tuple, torch.Tensor] = {}
+        self._img_in: Dict[tuple, torch.Tensor] = {}
 
     def close(self):
         if getattr(self, "_op_id", None):      # registered as a torch.ops.sesrq.forward handle: the C++ side drops its pointer first
@@ -342,6 +343,53 @@ class Engine:
             rawmod.launch(self.device, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, raw, q0, None, st)
             rc = _lib.lib().sesrq_forward(self._h, q0.data_ptr(), _lib.I8, out_q.data_ptr() if want_q else None,
                                           out_f.data_ptr() if want_f else None, N, H, W, ws.data_ptr(), ws.numel(), st.cuda_stream)
+        _lib.check(rc)
+        return (out_q if want_q else None), (out_f if want_f else None)
+
+    def forward_image(self, img_u8: torch.Tensor, form=None, order: str = "rgb", want_q: bool = True, want_f: bool = True, out_q=None,
+                      out_f=None, stream=None, slot: int = 0):
+        """img_u8: (N, H, W, 3) or (H, W, 3) torch.uint8 images on self.device, interleaved in `order` ("rgb" or "bgr") ->
+        (q int8 | None, y float32 | None).
+
+        form: "y" (SESR-x4, MFLAG 5: the float64 luma) or "rgb" (SESR-x2, MFLAG 6); None takes the one that fits the net's input
+        channels.  The images are decoded on the device (libsesrq_image.so, sesrq.image) into this net's q0 -- a per-(N, H, W, slot)
+        buffer the engine keeps -- and run through the same forward as an int8 q0 input: the results are those of forward() on the
+        reference's fp32 input frame (self_dataset_sr.py TestDataset).  An anchor_add engine needs the fp32 frame for its anchor: the
+        images are decoded into the fp32 frame instead (a kept buffer too) and run through the fp32 forward.  Both launches go to
+        `stream` (default: current), ordered as forward() orders them; give concurrent in-flight frames different slots.  Not for
+        engines whose int8 input is an upstream net's output."""
+        from . import image as imgmod
+        cin = self.bundle.in_channels
+        f = imgmod._form(form if form is not None else ("y" if cin == 1 else "rgb"))
+        if imgmod.CHANNELS[f] != cin:
+            raise ValueError(f"forward_image: the {'Y' if f == imgmod.Y else 'RGB'} form gives {imgmod.CHANNELS[f]} channel(s); "
+                             f"this net takes {cin}")
+        if self.i8_in_scale != 0.0:
+            raise ValueError("forward_image: this engine takes an upstream net's int8 output as input (upstream=...), not an image")
+        if not (want_q or want_f):
+            raise ValueError("forward_image: ask for the int8 output, the fp32 output or both")
+        imgmod._order(order)
+        img = imgmod._images(img_u8, self.device)
+        N, H, W, _ = img.shape
+        with torch.cuda.device(self.device):
+            img = img.contiguous()
+            key = (N, H, W, slot)
+            buf = self._img_in.get(key)
+            if buf is None:     # q0, or the fp32 frame an anchored forward adds back
+                buf = self._img_in[key] = torch.empty((N, cin, H, W), dtype=torch.float32 if self.anchor_add else torch.int8,
+                                                      device=self.device)
+            shp = self.out_shape(N, H, W)
+            if want_q and out_q is None:
+                out_q = torch.empty(shp, dtype=torch.int8, device=self.device)
+            if want_f and out_f is None:
+                out_f = torch.empty(shp, dtype=torch.float32, device=self.device)
+            ws = self.workspace(N, H, W, slot)
+            st = self._enter_stream(stream, img, buf, out_q, out_f, ws)
+            q0, x = (None, buf) if self.anchor_add else (buf, None)
+            imgmod.launch(self.device, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, img, f, order, q0, x, st)
+            rc = _lib.lib().sesrq_forward(self._h, buf.data_ptr(), _lib.F32 if self.anchor_add else _lib.I8,
+                                          out_q.data_ptr() if want_q else None, out_f.data_ptr() if want_f else None, N, H, W,
+                                          ws.data_ptr(), ws.numel(), st.cuda_stream)
         _lib.check(rc)
         return (out_q if want_q else None), (out_f if want_f else None)
 

@@ -188,3 +188,39 @@ def evaluate_raw(engine, raws, gts_u16, mflag: int):
     res = torch.cat(rows)
     torch.cuda.synchronize(dev)
     return res.cpu().numpy()
+
+
+def evaluate_image(engine, lr_imgs, hr_imgs, mflag: int, order: str = "rgb"):
+    """The reference's MFLAG 5 / 6 loop from 8-bit images to scores (self_dataset_sr.py TestDataset): per frame the uint8 LR image is
+    uploaded at 3 B/px, decoded on the device and run forward (Engine.forward_image), its uint8 HR image is decoded into the
+    reference's fp32 gt (sesrq.image.load_gt), and the output is scored as evaluate() scores it -- MFLAG 5 the int8 output, MFLAG 6
+    the anchored fp32 output (the engine must have been created with anchor_add=True).
+
+    lr_imgs / hr_imgs: iterables of (H, W, 3) / (1, H, W, 3) uint8 images (numpy or torch), in `order`.  One synchronisation at the
+    end; returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
+    import numpy as np
+    import torch
+    from . import image as imgmod
+    form = form_of(mflag)
+    imgmod.form_of(mflag)
+    if form == FORM_X2 and not getattr(engine, "anchor_add", False):
+        raise ValueError("MFLAG 6 is scored on the anchored output: create the engine with anchor_add=True")
+    b = engine.bundle
+    scale, zero = float(b.scale[b.L]), int(b.zero[b.L])
+    dev = engine.device
+    rows = []
+    for lr, hr in zip(lr_imgs, hr_imgs):
+        lr = torch.from_numpy(np.ascontiguousarray(lr)) if isinstance(lr, np.ndarray) else lr
+        lr = lr.to(dev, non_blocking=True)
+        g = imgmod.load_gt(hr, mflag, dev, order=order)
+        if form == FORM_X2:
+            _, y = engine.forward_image(lr, order=order, want_q=False, want_f=True)
+            rows.append(score(y, g, mflag))
+        else:
+            q, _ = engine.forward_image(lr, order=order, want_q=True, want_f=False)
+            rows.append(score(q, g, mflag, scale=scale, zero=zero))
+    if not rows:
+        raise ValueError("no frames")
+    res = torch.cat(rows)
+    torch.cuda.synchronize(dev)
+    return res.cpu().numpy()

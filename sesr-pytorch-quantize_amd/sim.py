@@ -9,6 +9,7 @@ test.py produced (an ``output_pt`` directory) or from a bundle/fixture file.
 
     python sim.py --mflag 5 --ckpt x4sesr.pth --calib output_pt --input rand_SR_Input_80x960.pt
     python sim.py --mflag 5 --params tests/golden/sesr_x4.params.npz --input tests/golden/rand_SR_Input_80x960.npy
+    python sim.py --mflag 6 --params ... --input LR.png --gt HR.png --save-png SR.png      # 8-bit images (MFLAG 5 / 6)
 """
 import argparse
 import json
@@ -123,11 +124,19 @@ def main(argv=None):
     ap.add_argument("--calib", help="output_pt directory written by the reference's test.py")
     ap.add_argument("--input", required=True, help="frame tensor: .pt (torch) or .npy, shape (N,C,H,W) float32; or a 12-bit RGGB raw frame "
                                                    "<name>_<rows>_<cols>.raw (uint16), spread on the device into the reference's "
-                                                   "3-channel input (self_dataset.py TestDataset)")
+                                                   "3-channel input (self_dataset.py TestDataset); or an 8-bit LR image (.png, or a "
+                                                   "uint8 .npy with --image), decoded on the device as self_dataset_sr.py does "
+                                                   "(MFLAG 5: luma, 6: RGB)")
+    ap.add_argument("--image", action="store_true", help="--input / --gt .npy files are uint8 (H, W, 3) or (N, H, W, 3) images, taken "
+                                                         "as *.png inputs are (MFLAG 5 / 6)")
+    ap.add_argument("--order", choices=("rgb", "bgr"), default="rgb", help="byte order of uint8 .npy images (PNGs are read as RGB)")
+    ap.add_argument("--save-png", help="write the output as an 8-bit PNG here (the reference's export: clip to [0, 1], * 255, "
+                                       "truncate; MFLAG 6 the anchored output); frame k of a batch goes to <stem>_<k>.png")
     ap.add_argument("--save", help="write the float result here (.npy)")
     ap.add_argument("--gt", help="ground truth of the output shape (N,Cout,H*r,W*r) float32, .npy or .pt: score the output with the "
                                  "reference's PSNR / SSIM on the device (test.py:141-183) and print them as its loop does; a uint16 "
-                                 "(N,3,H,W) RGB ground truth is taken / 4095 and clamped, as the reference's TestDataset does")
+                                 "(N,3,H,W) RGB ground truth is taken / 4095 and clamped, as the reference's TestDataset does; an "
+                                 "8-bit HR image (.png, or a uint8 .npy with --image) is formed as self_dataset_sr.py forms its gt")
     ap.add_argument("--dump", help="write the parameter store as an output_pt-compatible tree here (what the define.py *_W_FLG "
                                    "switches select, plus weights and activation domains); all dump switches are turned on")
     args = ap.parse_args(argv)
@@ -138,7 +147,8 @@ def main(argv=None):
     if args.calib:
         STORE.load_output_pt(args.calib)
     model = splice(float_model(args.mflag, args.ckpt, args.params))
-    if not args.input.endswith(".raw"):
+    as_image = is_image(args.input, args.image)
+    if not args.input.endswith(".raw") and not as_image:
         inps = torch.load(args.input, weights_only=True, map_location="cpu") if args.input.endswith(".pt") else \
             torch.from_numpy(np.load(args.input))
     if not torch.cuda.is_available():
@@ -146,6 +156,11 @@ def main(argv=None):
     if args.input.endswith(".raw"):         # the reference's loop: raw frame -> sparse RGGB mosaic / 4095, clamped -> model(inps)
         from sesrq import raw
         _, inps = raw.unpack(None, torch.from_numpy(raw.load_raw(args.input)).cuda(), want_q=False, want_spread=True)
+    elif as_image:                          # self_dataset_sr.py: uint8 LR image / 255 (MFLAG 5: the float64 luma) -> model(inps)
+        from sesrq import image
+        form = image.form_of(args.mflag)
+        _, inps = image.decode(None, torch.from_numpy(image.load_image(args.input)).cuda(), form, order=args.order, want_q=False,
+                               want_f=True)
     gfake = model(inps.float().cuda())
     torch.cuda.synchronize()
     banner(args.mflag)
@@ -156,28 +171,56 @@ def main(argv=None):
         STORE.save_output_pt(args.dump)
         print("dumped:", args.dump)
     if args.gt:
-        score_against(args.gt, gfake, inps, args.mflag)
+        gts = None
+        if is_image(args.gt, args.image):   # the HR image: the reference's gt formed on the device
+            from sesrq import image
+            gts = image.load_gt(image.load_image(args.gt), args.mflag, gfake.device, order=args.order)
+        score_against(args.gt, gfake, inps, args.mflag, gts=gts)
+    if args.save_png:
+        save_png(args.save_png, gfake, inps, args.mflag)
     return gfake
+
+
+def is_image(path, image_flag):
+    return path.lower().endswith(".png") or (image_flag and path.endswith(".npy"))
+
+
+def anchored(gfake, inps, mflag):
+    """test.py:149-155: MFLAG 6 is judged (and exported) with the nearest-upsampled input added."""
+    if mflag != 6:
+        return gfake
+    x = inps.float().to(gfake.device)
+    return gfake + x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
+
+
+def save_png(path, gfake, inps, mflag):
+    """The reference's PNG export (sim.py:163-169) on the device: clip to [0, 1], * 255 in fp32, truncate to uint8; PIL takes RGB
+    bytes, so no channel flip."""
+    from sesrq import image
+    u8 = image.export(anchored(gfake, inps, mflag), order="rgb").cpu().numpy()
+    stem, ext = os.path.splitext(path)
+    for k in range(u8.shape[0]):
+        image.save_png(path if u8.shape[0] == 1 else f"{stem}_{k}{ext or '.png'}", u8[k])
+    print("png:", path, tuple(u8.shape))
 
 
 def load_frames(path):
     return torch.load(path, weights_only=True, map_location="cpu") if path.endswith(".pt") else torch.from_numpy(np.load(path))
 
 
-def score_against(path, gfake, inps, mflag):
+def score_against(path, gfake, inps, mflag, gts=None):
     """The reference's evaluation loop (test.py:141-183) on the device: anchor for MFLAG 6, clip, PSNR / SSIM per frame; prints each
-    frame's PSNR and the mean line.  Returns the (N, 3) float64 host array of (mse, psnr, ssim)."""
+    frame's PSNR and the mean line.  gts: the ground truth already formed (an 8-bit HR image's), else read from `path`.  Returns the
+    (N, 3) float64 host array of (mse, psnr, ssim)."""
     from sesrq import quality
-    gts = load_frames(path)
+    if gts is None:
+        gts = load_frames(path)
     if tuple(gts.shape) != tuple(gfake.shape):
         raise SystemExit(f"sim.py: --gt has shape {tuple(gts.shape)}, the output is {tuple(gfake.shape)}")
     if gts.dtype == torch.uint16:                   # 16-bit RGB ground truth: / 4095, clamped (self_dataset.py:235-243)
         from sesrq import raw
         gts = raw.load_gt(gts, gfake.device)
-    pred = gfake
-    if mflag == 6:                                  # test.py:149-155: + the nearest-upsampled input
-        x = inps.float().to(gfake.device)
-        pred = gfake + x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
+    pred = anchored(gfake, inps, mflag)             # test.py:149-155: MFLAG 6 + the nearest-upsampled input
     res = quality.score(pred, gts.float().to(gfake.device), mflag).cpu().numpy()
     totalpsnr = totalssim = 0.0
     for _, psnr, ssim in res:
