@@ -125,6 +125,17 @@ typedef struct sesrq_net sesrq_net;
  * is current is refused).  Replaces quantize_model_weight's file output + every torch.load of
  * the output_pt/ tree inside the five callables. */
 int sesrq_create(const sesrq_net_desc *desc, const sesrq_options *opts, sesrq_net **out);
+/* The same at activation / weight width b = quan_bits (define.py QUAN_BIT, 2..8; sesrq_create is b = 8).  Every activation clamp of the
+ * path becomes clamp_b = clamp(., -2^(b-1), 2^(b-1) - 1): the input quantiser, the hidden and output requants and the residual merge,
+ * whose offsets become 2^(b-1) and 2^b (myQL/quan_func.py:201-207,218-225,250-252,270,280,585).  Not width-dependent, as in the reference:
+ * the PE pad / zero-offset rule max(zero, -128) (quan_func.py:290-291), the PE / adder / bias clamps and (M, n).  Validation at b: every
+ * weight in [-2^(b-1), 2^(b-1) - 1], zero[k] <= 2^(b-1) - 1.  A net with b < 8 runs every layer on the dot4 kernels whatever the engine
+ * option (no MFMA kernel, no fused trio, no grouping in sesrq_forward_many), the reduced requant forms are off, sesrq_layer_engine names
+ * carry a "-q<b>" suffix; per-channel requant constants and an int8 upstream hand-off (i8_in_scale > 0) are refused.  An SESRQ_I8 q0
+ * input is clamped to the width's range while it is staged. */
+int sesrq_create_q(const sesrq_net_desc *desc, const sesrq_options *opts, int quan_bits, sesrq_net **out);
+/* The width b the net was created with (8 for sesrq_create), 0 for a NULL net. */
+int sesrq_net_quan_bits(const sesrq_net *net);
 void sesrq_destroy(sesrq_net *net);
 /* 1 if sesrq_create proved (exhaustively, on the device) that the 3-instruction reciprocal form of
  * the input quantiser's x / scale_in is bit-identical for this net; 0 = IEEE division is used. */
@@ -267,6 +278,9 @@ typedef struct sesrq_calib_conv_desc {
 /* out = act(conv) (+ skip, the float long residual added after the activation; may be NULL) */
 int sesrq_calib_conv(const sesrq_calib_conv_desc *d, const float *in, const float *skip, float *out,
                      int N, int H, int W, void *stream);
+/* The same at activation width quan_bits (2..8): the input fake-quantiser clamps to [-2^(b-1), 2^(b-1) - 1] (quan_func.py:201-207) */
+int sesrq_calib_conv_q(const sesrq_calib_conv_desc *d, const float *in, const float *skip, float *out,
+                       int N, int H, int W, int quan_bits, void *stream);
 /* min and max of a device fp32 tensor -> out_min_max[0..1] (device); scratch8: 8 bytes of device scratch */
 int sesrq_calib_minmax(const float *x, size_t n, float *out_min_max, void *scratch8, void *stream);
 /* Entropy (KL) calibration variant -- no reference counterpart: the reference's test.py keeps min/max only; BASELINE's north
@@ -276,6 +290,8 @@ int sesrq_calib_minmax(const float *x, size_t n, float *out_min_max, void *scrat
 int sesrq_calib_histogram(const float *x, size_t n, float lo, float hi, int bins, uint32_t *hist, void *stream);
 /* (clamp8(rint(x/scale + zero)) - zero) * scale  (quan_func.py:207,215) */
 int sesrq_calib_fakequant(const float *in, float *out, size_t n, float scale, int zero, void *stream);
+/* (clamp_b(rint(x/scale + zero)) - zero) * scale at width quan_bits (2..8) */
+int sesrq_calib_fakequant_q(const float *in, float *out, size_t n, float scale, int zero, int quan_bits, void *stream);
 
 /* ---- host scalar code of the path (load time) -------------------------------------- */
 

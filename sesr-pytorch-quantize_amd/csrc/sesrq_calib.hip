@@ -5,7 +5,8 @@
 //
 // Per conv (reference: quantize_asymmetrical_by_tensor mode 0 -> reshape_input_for_hardware_pe -> Conv2d
 // with Wq*sw -> PEs_and_bias_adder mode 0 -> activation), with this batch's (scale, zero) of the input:
-//   q      = clamp8(rint(x/scale + zero)) - zero             integer; outside the frame 0     (quan_func.py:207,215)
+//   q      = clamp_b(rint(x/scale + zero)) - zero            integer; outside the frame 0     (quan_func.py:207,215)
+//            (clamp_b = clamp(., -2^(b-1), 2^(b-1) - 1), the width b of sesrq_calib_conv_q; b = 8 for sesrq_calib_conv)
 //   pe_p   = sum_{ic = p mod 4, taps} Wq * q                  exact in int32                   (quan_func.py:298-318)
 //   v_p    = clamp(f32(pe_p) * f32(scale*sw), fmin18, fmax18)                                  (quan_func.py:330-333)
 //   v      = clamp(v_0 + v_1 + v_2 + v_3, fmin20, fmax20) + bias_q * f32(scale*sw)             (quan_func.py:431-434,459)
@@ -27,6 +28,7 @@ struct CalibArgs {
     const float *qbias;     // [oc]  bias_q * f32(scale*sw)
     int N, H, W, ic, oc;
     float scale, zero;      // this batch's input domain
+    float qlo, qhi;         // activation range of the width: -2^(b-1), 2^(b-1) - 1
     float ss;               // f32(scale * sw)
     float acc_lo, acc_hi, add_lo, add_hi;
     int relu;
@@ -45,7 +47,7 @@ __global__ __launch_bounds__(256) void calib_conv_kernel(const CalibArgs a) {
             int q = 0;
             if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) {
                 const float xv = a.in[((size_t)n * a.ic + c) * HW + (size_t)gy * a.W + gx];
-                const float r = fminf(fmaxf(rintf(__fadd_rn(__fdiv_rn(xv, a.scale), a.zero)), -128.f), 127.f);
+                const float r = fminf(fmaxf(rintf(__fadd_rn(__fdiv_rn(xv, a.scale), a.zero)), a.qlo), a.qhi);
                 q = (int)(r - a.zero);
             }
             tile[c][i] = (short)q;
@@ -92,10 +94,10 @@ __global__ void calib_minmax_finish(const unsigned *mm, float *out) {
         out[i] = __builtin_bit_cast(float, u);
     }
 }
-__global__ void calib_fakequant_kernel(const float *in, float *out, size_t n, float scale, float zero) {
+__global__ void calib_fakequant_kernel(const float *in, float *out, size_t n, float scale, float zero, float qlo, float qhi) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
-        const float q = fminf(fmaxf(rintf(__fadd_rn(__fdiv_rn(in[i], scale), zero)), -128.f), 127.f);
+        const float q = fminf(fmaxf(rintf(__fadd_rn(__fdiv_rn(in[i], scale), zero)), qlo), qhi);
         out[i] = __fmul_rn(q - zero, scale);
     }
 }
@@ -138,7 +140,9 @@ int sesrq_calib_minmax(const float *x, size_t n, float *out_min_max, void *scrat
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
-int sesrq_calib_conv(const sesrq_calib_conv_desc *d, const float *in, const float *skip, float *out, int N, int H, int W, void *stream) {
+int sesrq_calib_conv_q(const sesrq_calib_conv_desc *d, const float *in, const float *skip, float *out, int N, int H, int W, int quan_bits,
+                       void *stream) {
+    if (quan_bits < 2 || quan_bits > 8) { set_error("sesrq_calib_conv_q: quan_bits must be 2..8"); return 1; }
     if (!d || !in || !out || !d->w || !d->qbias) { set_error("sesrq_calib_conv: null argument"); return 1; }
     if ((d->k != 3 && d->k != 5) || d->ic < 1 || d->ic > SESRQ_MAX_CH || d->oc < 1 || d->oc > SESRQ_MAX_CH) { set_error("sesrq_calib_conv: unsupported layer shape"); return 1; }
     if (N < 1 || H < 1 || W < 1 || !(d->in_scale > 0.f)) { set_error("sesrq_calib_conv: bad size or scale"); return 1; }
@@ -146,12 +150,17 @@ int sesrq_calib_conv(const sesrq_calib_conv_desc *d, const float *in, const floa
     a.in = in; a.skip = skip; a.out = out; a.w = d->w; a.qbias = d->qbias;
     a.N = N; a.H = H; a.W = W; a.ic = d->ic; a.oc = d->oc;
     a.scale = d->in_scale; a.zero = (float)d->in_zero; a.ss = d->ss;
+    a.qlo = -(float)(1 << (quan_bits - 1)); a.qhi = (float)((1 << (quan_bits - 1)) - 1);
     a.acc_lo = d->acc_lo; a.acc_hi = d->acc_hi; a.add_lo = d->add_lo; a.add_hi = d->add_hi; a.relu = d->relu;
     dim3 grid((W + 31) / 32, (H + 7) / 8, N);
     if (d->k == 3) launch_kernel<calib_conv_kernel<3>>(grid, dim3(256), 0, (hipStream_t)stream, a);
     else launch_kernel<calib_conv_kernel<5>>(grid, dim3(256), 0, (hipStream_t)stream, a);
     if (hipGetLastError() != hipSuccess) { set_error("sesrq_calib_conv: launch failed"); return 1; }
     return 0;
+}
+
+int sesrq_calib_conv(const sesrq_calib_conv_desc *d, const float *in, const float *skip, float *out, int N, int H, int W, void *stream) {
+    return sesrq_calib_conv_q(d, in, skip, out, N, H, W, 8, stream);
 }
 
 int sesrq_calib_histogram(const float *x, size_t n, float lo, float hi, int bins, uint32_t *hist, void *stream) {
@@ -165,10 +174,16 @@ int sesrq_calib_histogram(const float *x, size_t n, float lo, float hi, int bins
     return 0;
 }
 
-int sesrq_calib_fakequant(const float *in, float *out, size_t n, float scale, int zero, void *stream) {
+int sesrq_calib_fakequant_q(const float *in, float *out, size_t n, float scale, int zero, int quan_bits, void *stream) {
     if (!in || !out || n == 0 || !(scale > 0.f)) { set_error("sesrq_calib_fakequant: bad argument"); return 1; }
-    launch_kernel<calib_fakequant_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, out, n, scale, (float)zero);
+    if (quan_bits < 2 || quan_bits > 8) { set_error("sesrq_calib_fakequant_q: quan_bits must be 2..8"); return 1; }
+    const float qlo = -(float)(1 << (quan_bits - 1)), qhi = (float)((1 << (quan_bits - 1)) - 1);
+    launch_kernel<calib_fakequant_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, out, n, scale, (float)zero, qlo, qhi);
     return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int sesrq_calib_fakequant(const float *in, float *out, size_t n, float scale, int zero, void *stream) {
+    return sesrq_calib_fakequant_q(in, out, n, scale, zero, 8, stream);
 }
 
 }  // extern "C"

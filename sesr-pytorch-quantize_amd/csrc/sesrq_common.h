@@ -191,6 +191,10 @@ struct ConvArgs {
     int add_const[SESRQ_MAX_CH];
     const float2 *mn_oc;     // dot4 kernels: per-output-channel ((float)M, 2^-n) [oc] of a per-channel layer (sesrq_layer_desc.M_oc), or NULL
     FrameTable ft;           // MFMA first / last layer kernels only (ft.n == 0: one contiguous batch at in / out_q / out_f)
+    // activation width b (sesrq_create_q; dot4 kernels only -- a net with b < 8 runs no other kernel): every activation clamp is
+    // clamp(., qlo, qhi) = [-2^(b-1), 2^(b-1) - 1], the residual merge offsets are qhalf = 2^(b-1) and qspan = 2^b (quan_func.py:250-252).
+    // b = 8: [-128, 127], 128, 256 -- the constants the MFMA kernels and the trio keep as literals
+    float qlo, qhi, qhalf, qspan;
 };
 
 // fused hidden trio (sesrq_trio.hip): three consecutive 3x3 16->16 merged layers in one launch
@@ -287,6 +291,7 @@ struct sesrq_net {
     int *d_merge_lut = nullptr;         // device: 512-byte table of the residual merge (see TrioArgs::merge_lut)
     std::vector<int> trio_len;          // trio_len[k] == 3: layers k..k+2 are eligible for the fused hidden trio
     int device = 0;
-    bool rc_separate = false;   // zero[1] != -128 -> layer 0 writes its own rc tensor
+    int quan_bits = 8;          // activation / weight width b (sesrq_create_q), 2..8
+    bool rc_separate = false;   // zero[1] != -2^(b-1) -> layer 0 writes its own rc tensor
     sesrq::FastDiv fd = {0, 0.f, 0.f, 0.f, 0.f};
 };

@@ -178,9 +178,16 @@ void sesrq_default_options(sesrq_options *o) {
     o->reduced_forms = -1;
 }
 
-int sesrq_create(const sesrq_net_desc *d, const sesrq_options *opts, sesrq_net **out) {
+int sesrq_create(const sesrq_net_desc *d, const sesrq_options *opts, sesrq_net **out) { return sesrq_create_q(d, opts, 8, out); }
+
+int sesrq_create_q(const sesrq_net_desc *d, const sesrq_options *opts, int quan_bits, sesrq_net **out) {
     if (!d || !out) { set_error("sesrq_create: null argument"); return 1; }
     *out = nullptr;
+    if (quan_bits < 2 || quan_bits > 8) { set_error("sesrq_create: quan_bits must be 2..8 (define.py QUAN_BIT)"); return 1; }
+    // width b: activations and weights live in [qlo, qhi] (myQL/quan_func.py:67-70,201-202,218-219); b < 8 runs every layer on the dot4 kernels
+    // (their clamps are runtime arguments; the MFMA kernels and the fused trio keep the 8-bit literals)
+    const int qlo = -(1 << (quan_bits - 1)), qhi = (1 << (quan_bits - 1)) - 1;
+    const bool narrow = quan_bits < 8;
     sesrq_options o;
     sesrq_default_options(&o);
     if (opts) o = *opts;
@@ -196,13 +203,18 @@ int sesrq_create(const sesrq_net_desc *d, const sesrq_options *opts, sesrq_net *
     if (d->M_res >= (1u << 16) || d->n_res > 32) { set_error("sesrq_create: residual requant constant out of range"); return 1; }
     if (!(d->scale_in > 0.f) || !(d->scale_out > 0.f)) { set_error("sesrq_create: scales must be positive"); return 1; }
     for (int k = 0; k <= L; ++k)
-        if (d->zero[k] < -32768 || d->zero[k] > 127) { set_error("sesrq_create: zero point out of range [-32768,127]"); return 1; }
+        if (d->zero[k] < -32768 || d->zero[k] > qhi) {
+            set_error("sesrq_create: zero point out of range [-32768," + std::to_string(qhi) + "]"); return 1;
+        }
     for (int k = 0; k < L; ++k) {
         const sesrq_layer_desc &l = d->layers[k];
         if (l.k != 3 && l.k != 5) { set_error("sesrq_create: kernel size must be 3 or 5"); return 1; }
         if (l.ic < 1 || l.ic > SESRQ_MAX_CH || l.oc < 1 || l.oc > SESRQ_MAX_CH) { set_error("sesrq_create: channels must be 1..16"); return 1; }
         if (!l.w || !l.add_const) { set_error("sesrq_create: null weight/add_const"); return 1; }
+        for (size_t i = 0, nw = (size_t)l.oc * l.ic * l.k * l.k; narrow && i < nw; ++i)
+            if (l.w[i] < qlo || l.w[i] > qhi) { set_error("sesrq_create: weight outside the " + std::to_string(quan_bits) + "-bit range"); return 1; }
         if (l.M >= (1u << 16) || l.n > 32) { set_error("sesrq_create: requant constant out of range (M < 2^16, n <= 32)"); return 1; }
+        if (narrow && l.M_oc) { set_error("sesrq_create: per-channel requant constants need quan_bits == 8"); return 1; }
         if ((l.M_oc != nullptr) != (l.n_oc != nullptr)) { set_error("sesrq_create: per-channel requant constants need both M_oc and n_oc"); return 1; }
         for (int o = 0; l.M_oc && o < l.oc && o < SESRQ_MAX_CH; ++o)
             if (l.M_oc[o] >= (1u << 16) || l.n_oc[o] > 32) { set_error("sesrq_create: per-channel requant constant out of range (M < 2^16, n <= 32)"); return 1; }
@@ -227,7 +239,8 @@ int sesrq_create(const sesrq_net_desc *d, const sesrq_options *opts, sesrq_net *
     net->ps = d->pixel_shuffle;
     net->acc_bits = d->pe_acc_bits;
     net->add_bits = d->pe_add_bits;
-    net->rc_separate = (d->zero[1] != -128);
+    net->quan_bits = quan_bits;
+    net->rc_separate = (d->zero[1] != qlo);      // layer 0's output IS the residual operand only in the domain zero[1] == -2^(b-1)
     net->engine = o.engine;
     net->force_general = o.force_general ? 1 : 0;
     if (o.exact_div < 0 || o.exact_div > 2) { set_error("sesrq_create: exact_div must be 0, 1 or 2"); delete net; return 1; }
@@ -243,6 +256,7 @@ int sesrq_create(const sesrq_net_desc *d, const sesrq_options *opts, sesrq_net *
     }
     // the int8 hand-off domain is an upstream net's OUTPUT domain (scale_L, zero[L]): an int8-range zero point
     if (!(o.i8_in_scale >= 0.f) || o.i8_in_zero < -128 || o.i8_in_zero > 127) { set_error("sesrq_create: bad int8 input domain (zero point must be in [-128, 127])"); delete net; return 1; }
+    if (narrow && o.i8_in_scale > 0.f) { set_error("sesrq_create: an int8 upstream hand-off needs quan_bits == 8"); delete net; return 1; }
     net->i8_in_scale = o.i8_in_scale;
     net->i8_in_zero = o.i8_in_zero;
     if (o.anchor_add && d->layers[0].ic * d->pixel_shuffle * d->pixel_shuffle != d->layers[L - 1].oc) {
@@ -269,7 +283,8 @@ int sesrq_create(const sesrq_net_desc *d, const sesrq_options *opts, sesrq_net *
             return 1;
         }
         lp.mfma_kind = MFMA_NONE;
-        if (l.M_oc) {      // per-output-channel requant constants: a device table for the dot4 kernels; no MFMA kernel, no trio, no grouping
+        if (narrow) {}     // width b < 8: the dot4 kernels only (their clamps are runtime arguments), like the per-channel layers below
+        else if (l.M_oc) {      // per-output-channel requant constants: a device table for the dot4 kernels; no MFMA kernel, no trio, no grouping
             float2 mn[SESRQ_MAX_CH];
             for (int o = 0; o < SESRQ_MAX_CH; ++o) mn[o] = o < l.oc ? make_float2((float)l.M_oc[o], ldexpf(1.0f, -(int)l.n_oc[o])) : make_float2(0.f, 0.f);
             if (hipMalloc((void **)&lp.d_mn_oc, sizeof(mn)) != hipSuccess || hipMemcpy(lp.d_mn_oc, mn, sizeof(mn), hipMemcpyHostToDevice) != hipSuccess) {
@@ -354,7 +369,8 @@ int sesrq_create(const sesrq_net_desc *d, const sesrq_options *opts, sesrq_net *
             }
             a.Cs = a.Cd - 128.f;
         }
-        if (l.M_oc) a.direct = 0;
+        if (l.M_oc || narrow) a.direct = 0;      // the reduced forms are proven for the 8-bit clamp only
+        a.qlo = (float)qlo; a.qhi = (float)qhi; a.qhalf = (float)(1 << (quan_bits - 1)); a.qspan = (float)(1 << quan_bits);
         a.mn_oc = lp.d_mn_oc;
         a.Mres = (float)d->M_res; a.shres = ldexpf(1.0f, -(int)d->n_res);
         a.z_merge = (float)d->zero[L - 1];
@@ -362,7 +378,8 @@ int sesrq_create(const sesrq_net_desc *d, const sesrq_options *opts, sesrq_net *
         a.s_out = d->scale_out; a.z_out = (float)d->zero[L];
         a.ps = d->pixel_shuffle;
         for (int o = 0; o < l.oc; ++o) a.add_const[o] = l.add_const[o];
-        lp.engine_dot4 = std::string(lp.general ? "dot4-general" : "dot4-merged") + (l.M_oc ? "-perchannel" : "");
+        lp.engine_dot4 = std::string(lp.general ? "dot4-general" : "dot4-merged") + (l.M_oc ? "-perchannel" : "") +
+                         (narrow ? "-q" + std::to_string(quan_bits) : "");
         static const char *kn[] = {"", "mfma-h3", "mfma-h5", "mfma-f5"};
         const bool hyb = lp.general && __builtin_popcount(lp.risky_mask) == 1 && d->pe_acc_bits == 18 && d->pe_add_bits == 20;
         lp.engine_mfma = lp.mfma_kind == MFMA_NONE ? lp.engine_dot4 : std::string(kn[lp.mfma_kind]) + (hyb ? "-hybrid" : (lp.general ? "-general" : "-merged"));
@@ -396,6 +413,8 @@ int sesrq_create(const sesrq_net_desc *d, const sesrq_options *opts, sesrq_net *
             return 1;
         }
     }
+    // The proof compares clamp8(rint(.)) of the two quotient forms; it holds for every width b <= 8 as it stands, because
+    // clamp_b(v) = clamp_b(clamp8(v)): two forms that agree after clamp8 agree after clamp_b.
     net->fd_proof = prove_fastdiv(d->scale_in, d->zero[0]);
     net->fd = net->fd_proof;
     if (net->div_mode == 1) net->fd.ok = 0;

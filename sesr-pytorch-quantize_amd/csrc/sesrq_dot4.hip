@@ -13,11 +13,12 @@
 //   20-bit clamp, + add constant       myQL/quan_func.py:437,491
 //   t = f32(acc*M) * 2^-n              myQL/quan_func.py:529,560,584,605   (fp32 product rounding kept)
 //   ReLU                               models/model_utils_pt.py:24-26
-//   q = clamp8(rint(t + zero_next))    myQL/quan_func.py:280
+//   q = clamp_b(rint(t + zero_next))   myQL/quan_func.py:280
 //   residual merge                     myQL/quan_func.py:249-270
 //   output requant + dequant + shuffle myQL/quan_func.py:584-594, models/sesr_sim.py:49
-// and, for layer 0, the input quantiser  q0 = clamp8(rint(x/s0 + z0))  (quan_func.py:225)
-// fused into the LDS staging.
+// and, for layer 0, the input quantiser  q0 = clamp_b(rint(x/s0 + z0))  (quan_func.py:225)
+// fused into the LDS staging.  clamp_b = clamp(., a.qlo, a.qhi): the activation width b is a runtime argument
+// (sesrq_create_q; [-128, 127] at b = 8), as are the residual merge's offsets 2^(b-1) and 2^b.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off   (no fast-math: the fp32
 // multiply-then-add sequence of the reference must not be contracted).
@@ -29,7 +30,7 @@ constexpr int TW = 32;   // output tile width  (lanes 0..31 of a half-wave row)
 constexpr int TH = 8;    // output tile height (256 threads = 4 waves, 2 rows per wave)
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-__device__ __forceinline__ float q8f(float v) { return fminf(fmaxf(rintf(v), -128.f), 127.f); }
+__device__ __forceinline__ float qbf(float v, float lo, float hi) { return fminf(fmaxf(rintf(v), lo), hi); }
 
 template <int K, int IN_DW, bool GENERAL, int EPI, int OCP, int SRC>
 __global__ __launch_bounds__(256) void conv_dot4_kernel(const ConvArgs a) {
@@ -64,12 +65,12 @@ __global__ __launch_bounds__(256) void conv_dot4_kernel(const ConvArgs a) {
                     int q;
                     if constexpr (SRC == SRC_F32) {
                         const float xv = reinterpret_cast<const float *>(a.in)[off];
-                        q = (int)q8f(__fadd_rn((fd_reciprocal(a.fd) ? __fmul_rn(xv, a.fd.r) : __fdiv_rn(xv, a.s_in)), a.z_in));
+                        q = (int)qbf(__fadd_rn((fd_reciprocal(a.fd) ? __fmul_rn(xv, a.fd.r) : __fdiv_rn(xv, a.s_in)), a.z_in), a.qlo, a.qhi);
                     } else if constexpr (SRC == SRC_I8D) {
                         const float xv = __fmul_rn((float)(int)reinterpret_cast<const signed char *>(a.in)[off] - a.z_prev, a.s_prev);
-                        q = (int)q8f(__fadd_rn((fd_reciprocal(a.fd) ? __fmul_rn(xv, a.fd.r) : __fdiv_rn(xv, a.s_in)), a.z_in));
-                    } else {
-                        q = reinterpret_cast<const signed char *>(a.in)[off];
+                        q = (int)qbf(__fadd_rn((fd_reciprocal(a.fd) ? __fmul_rn(xv, a.fd.r) : __fdiv_rn(xv, a.s_in)), a.z_in), a.qlo, a.qhi);
+                    } else {      // q0 as handed over, clamped to the net's width (a no-op at b = 8)
+                        q = clampi(reinterpret_cast<const signed char *>(a.in)[off], (int)a.qlo, (int)a.qhi);
                     }
                     word |= (q & 0xff) << (8 * c);
                 }
@@ -180,14 +181,14 @@ __global__ __launch_bounds__(256) void conv_dot4_kernel(const ConvArgs a) {
             float q;
             if constexpr (EPI == EPI_PRERES) {
                 const float rc = (float)(signed char)((rcw[p] >> (8 * j)) & 0xff);
-                const float ic = q8f(__fadd_rn(t[o], -128.f));
+                const float ic = qbf(__fadd_rn(t[o], -a.qhalf), a.qlo, a.qhi);
                 if (a.dbg_ic && o < a.oc) a.dbg_ic[((size_t)n * a.oc + o) * HW + (size_t)gy * W + gx] = (signed char)(int)ic;      // input.4.spcial.pt (quan_func.py:250,254)
-                const float u = rc + ic + 256.f;
+                const float u = rc + ic + a.qspan;
                 const float v = __fmul_rn(u, a.Mres) * a.shres;
-                q = q8f(__fadd_rn(v, a.z_merge));
+                q = qbf(__fadd_rn(v, a.z_merge), a.qlo, a.qhi);
             } else {
-                q = q8f(__fadd_rn(t[o], a.z_next));
-                if (a.rc_out) rw[p] |= (((int)q8f(__fadd_rn(t[o], -128.f))) & 0xff) << (8 * j);
+                q = qbf(__fadd_rn(t[o], a.z_next), a.qlo, a.qhi);
+                if (a.rc_out) rw[p] |= (((int)qbf(__fadd_rn(t[o], -a.qhalf), a.qlo, a.qhi)) & 0xff) << (8 * j);
             }
             ow[p] |= (((int)q) & 0xff) << (8 * j);
         }
@@ -203,7 +204,7 @@ __global__ __launch_bounds__(256) void conv_dot4_kernel(const ConvArgs a) {
 #pragma unroll
         for (int o = 0; o < OCP; ++o) {
             if (o < a.oc) {
-                const float q = q8f(__fadd_rn(t[o], a.z_out));
+                const float q = qbf(__fadd_rn(t[o], a.z_out), a.qlo, a.qhi);
                 const int c = o / r2, rem = o - c * r2, i = rem / r, j = rem - i * r;
                 const size_t off = (((size_t)n * cout + c) * Ho + (size_t)gy * r + i) * Wo + (size_t)gx * r + j;
                 if (a.out_q) reinterpret_cast<signed char *>(a.out_q)[off] = (signed char)(int)q;

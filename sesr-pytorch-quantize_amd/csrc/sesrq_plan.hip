@@ -44,6 +44,8 @@ extern "C" {
 
 int sesrq_fast_division_proven(const sesrq_net *net) { return net ? net->fd_proof.ok : 0; }
 
+int sesrq_net_quan_bits(const sesrq_net *net) { return net ? net->quan_bits : 0; }
+
 const char *sesrq_layer_engine(const sesrq_net *net, int k) {
     if (!net || k < 0 || k >= net->L) return "";
     for (int j = std::max(1, k - 2); j <= k; ++j)

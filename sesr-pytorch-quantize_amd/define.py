@@ -17,7 +17,7 @@ TEST_RAW_ADD_NOISE = False
 # hardware model: four processing elements, channel c is handled by PE c % 4
 PE = 4
 
-QUAN_BIT = 8          # activations and weights
+QUAN_BIT = 8          # activations and weights, 2..8 (b < 8 runs on the dot4 kernels; sim.py / test.py --quan-bit)
 BIAS_BIT = 16         # bias constant  clamp16(bias_q - zero * sum(W))
 PE_ACC_BIT = 18       # each PE's accumulator saturates here
 PE_ADD_BIT = 20       # the 4-input adder tree saturates here
@@ -49,8 +49,8 @@ def check():
     """Reject configurations the device engine cannot honour (mirrors sesrq_create's checks)."""
     if PE != 4:
         raise ValueError("only PE == 4 is supported")
-    if QUAN_BIT != 8:
-        raise ValueError("only QUAN_BIT == 8 is supported")
+    if not (isinstance(QUAN_BIT, int) and 2 <= QUAN_BIT <= 8):
+        raise ValueError("QUAN_BIT must be an integer in 2..8 (activations are stored as int8)")
     if not (REQUAN_BIT < REQUAN_N_MAX <= 32) or REQUAN_BIT > 16:
         raise ValueError("need REQUAN_BIT <= 16 < REQUAN_N_MAX <= 32")
     if not (8 < PE_ACC_BIT <= PE_ADD_BIT < 32):

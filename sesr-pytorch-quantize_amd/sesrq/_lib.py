@@ -58,6 +58,8 @@ class Taps(C.Structure):
 SYMBOLS = {
     "sesrq_default_options": (None, [C.POINTER(Options)]),
     "sesrq_create": (C.c_int, [C.POINTER(NetDesc), C.POINTER(Options), C.POINTER(C.c_void_p)]),
+    "sesrq_create_q": (C.c_int, [C.POINTER(NetDesc), C.POINTER(Options), C.c_int, C.POINTER(C.c_void_p)]),
+    "sesrq_net_quan_bits": (C.c_int, [C.c_void_p]),
     "sesrq_destroy": (None, [C.c_void_p]),
     "sesrq_launch_plan": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sesrq_fast_division_proven": (C.c_int, [C.c_void_p]),
@@ -81,8 +83,11 @@ SYMBOLS = {
     "sesrq_layer_engine": (C.c_char_p, [C.c_void_p, C.c_int]),
     "sesrq_calib_conv": (C.c_int, [C.POINTER(CalibConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p]),
+    "sesrq_calib_conv_q": (C.c_int, [C.POINTER(CalibConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                     C.c_int, C.c_void_p]),
     "sesrq_calib_minmax": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sesrq_calib_fakequant": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int, C.c_void_p]),
+    "sesrq_calib_fakequant_q": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int, C.c_int, C.c_void_p]),
     "sesrq_calib_histogram": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "sesrq_requant_const": (C.c_int, [C.c_double, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "sesrq_quantize_weight": (C.c_int, [C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_int8),

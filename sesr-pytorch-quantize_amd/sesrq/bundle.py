@@ -40,6 +40,7 @@ class Bundle:
     pe_acc_bits: int = 18
     pe_add_bits: int = 20
     name: str = ""
+    quan_bits: int = 8      # define.py QUAN_BIT: width of weights and activations (sesrq_create_q)
 
     @property
     def L(self) -> int:
@@ -58,7 +59,7 @@ class Bundle:
         meta = dict(scale=self.scale, zero=self.zero, M=[l.M for l in self.layers], n=[l.n for l in self.layers],
                     relu=[bool(l.relu) for l in self.layers], w_scale=[l.w_scale for l in self.layers],
                     M_res=self.M_res, n_res=self.n_res, pixel_shuffle=self.pixel_shuffle, pe_num=self.pe_num,
-                    pe_acc_bits=self.pe_acc_bits, pe_add_bits=self.pe_add_bits, name=self.name)
+                    pe_acc_bits=self.pe_acc_bits, pe_add_bits=self.pe_add_bits, name=self.name, quan_bits=self.quan_bits)
         arrs = {f"Wq{k}": l.wq for k, l in enumerate(self.layers)}
         arrs.update({f"add_const{k}": l.add_const for k, l in enumerate(self.layers)})
         for k, l in enumerate(self.layers):
@@ -84,7 +85,8 @@ class Bundle:
         return Bundle(layers=layers, scale=[float(s) for s in m["scale"]], zero=[int(v) for v in m["zero"]],
                       M_res=int(m["M_res"]), n_res=int(m["n_res"]), pixel_shuffle=int(ps),
                       pe_num=int(m.get("pe_num", 4)), pe_acc_bits=int(m.get("pe_acc_bits", 18)),
-                      pe_add_bits=int(m.get("pe_add_bits", 20)), name=m.get("name", m.get("case", "")))
+                      pe_add_bits=int(m.get("pe_add_bits", 20)), name=m.get("name", m.get("case", "")),
+                      quan_bits=int(m.get("quan_bits", 8)))        # bundles written before the width existed are 8-bit
 
 
 # ---- load-time derivation through the library's host-scalar entry points -----------------
@@ -147,22 +149,29 @@ def derive_bundle(weights: Sequence[np.ndarray], biases: Sequence[np.ndarray], s
     per_channel: one weight scale per OUTPUT channel instead of the reference's one per tensor (parity unpinned).
 
     Layer roles by position, as in myQL/quan_func.py:523-609: layers 0 and L-2 requantise into
-    domain 1, layer L-1 into domain L, the rest into k+1; residual multiplier s_1/s_{L-1}."""
+    domain 1, layer L-1 into domain L, the rest into k+1; residual multiplier s_1/s_{L-1}.
+    quan_bit: define.py QUAN_BIT, the width of the weights (quantised here) and of the activations (recorded in the bundle)."""
     quantised = [(quantize_weight_per_channel if per_channel else quantize_weight)(w, quan_bit) for w in weights]
     return derive_bundle_from_quantized([q for q, _ in quantised], [s for _, s in quantised], biases, scale, zero,
                                         pixel_shuffle, name=name, bias_bit=bias_bit, requan_bit=requan_bit,
                                         requan_n_max=requan_n_max, pe_num=pe_num, pe_acc_bits=pe_acc_bits,
-                                        pe_add_bits=pe_add_bits)
+                                        pe_add_bits=pe_add_bits, quan_bit=quan_bit)
 
 
 def derive_bundle_from_quantized(wqs: Sequence[np.ndarray], w_scales: Sequence[float], biases: Sequence[np.ndarray],
                                  scale: Sequence[float], zero: Sequence[int], pixel_shuffle: int, name: str = "",
                                  bias_bit: int = 16, requan_bit: int = 16, requan_n_max: int = 32, pe_num: int = 4,
-                                 pe_acc_bits: int = 18, pe_add_bits: int = 20) -> Bundle:
+                                 pe_acc_bits: int = 18, pe_add_bits: int = 20, quan_bit: int = 8) -> Bundle:
     """Same as derive_bundle for weights that quantize_model_weight already turned into integers."""
     L = len(wqs)
     if len(scale) != L + 1 or len(zero) != L + 1:
         raise ValueError("derive_bundle: need L+1 scales and zeros")
+    if not 2 <= int(quan_bit) <= 8:
+        raise ValueError("derive_bundle: quan_bit must be 2..8")
+    lo, hi = -(1 << (quan_bit - 1)), (1 << (quan_bit - 1)) - 1
+    for k, w in enumerate(wqs):
+        if np.min(w) < lo or np.max(w) > hi:
+            raise ValueError(f"derive_bundle: conv {k} weights are not {quan_bit}-bit integers")
     layers = []
     for k in range(L):
         wq = np.ascontiguousarray(wqs[k], dtype=np.int8)
@@ -181,4 +190,5 @@ def derive_bundle_from_quantized(wqs: Sequence[np.ndarray], w_scales: Sequence[f
                                   M=M, n=n, relu=(k != L - 1), w_scale=sw))
     M_res, n_res = requant_const(scale[1] / scale[L - 1], requan_bit, requan_n_max)
     return Bundle(layers=layers, scale=[float(s) for s in scale], zero=[int(z) for z in zero], M_res=M_res, n_res=n_res,
-                  pixel_shuffle=pixel_shuffle, pe_num=pe_num, pe_acc_bits=pe_acc_bits, pe_add_bits=pe_add_bits, name=name)
+                  pixel_shuffle=pixel_shuffle, pe_num=pe_num, pe_acc_bits=pe_acc_bits, pe_add_bits=pe_add_bits, name=name,
+                  quan_bits=int(quan_bit))

@@ -86,12 +86,16 @@ def entropy_range(hist: np.ndarray, lo: float, hi: float, levels: int = 256, str
 class Calibrator:
     def __init__(self, weights: Sequence[np.ndarray], biases: Sequence[np.ndarray], pixel_shuffle: int = 1,
                  device: Optional[torch.device] = None, pe_acc_bits: int = 18, pe_add_bits: int = 20, bias_bits: int = 16,
-                 quantized=None, method: str = "minmax", bins: int = 2048):
+                 quantized=None, method: str = "minmax", bins: int = 2048, quan_bits: int = 8):
         """weights: float collapsed convs (quantised here), or None with `quantized` = [(Wq int8, weight scale)]
-        when quantize_model_weight already did it."""
+        when quantize_model_weight already did it.  quan_bits: define.py QUAN_BIT, the width b of weights and activations
+        (scale = range / (2^b - 1), zero = -2^(b-1) - round(min / scale), clamps to [-2^(b-1), 2^(b-1) - 1]; test.py:189-215)."""
         if not torch.cuda.is_available():
             raise RuntimeError("sesrq.Calibrator needs a HIP device (no CPU fallback)")
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        if not 2 <= int(quan_bits) <= 8:
+            raise ValueError("Calibrator: quan_bits must be 2..8")
+        self.quan_bits = int(quan_bits)
         self.L = len(biases)
         self.pixel_shuffle = int(pixel_shuffle)
         self.acc_bits, self.add_bits, self.bias_bits = pe_acc_bits, pe_add_bits, bias_bits
@@ -99,7 +103,7 @@ class Calibrator:
         self.biases_f = [np.asarray(b, np.float32) for b in biases]
         self.wq, self.sw, self._wdev = [], [], []
         if quantized is None:
-            quantized = [quantize_weight(w) for w in self.weights_f]
+            quantized = [quantize_weight(w, self.quan_bits) for w in self.weights_f]
         for q, s in quantized:
             q = np.ascontiguousarray(q, dtype=np.int8)
             self.wq.append(q)
@@ -156,8 +160,8 @@ class Calibrator:
             if self.run_min[k] is None or self.run_min[k] > mn:
                 self.run_min[k] = mn
         assert mx != mn, "Input tensor is all equal,{}".format(k)
-        scale = (mx - mn) / 255
-        zero = -128 - round(mn / scale)
+        scale = (mx - mn) / ((1 << self.quan_bits) - 1)
+        zero = -(1 << (self.quan_bits - 1)) - round(mn / scale)
         self.last_scale[k], self.last_zero[k] = scale, int(zero)
         return scale, int(zero)
 
@@ -190,15 +194,16 @@ class Calibrator:
                                       relu=int(k != L - 1))
             out = torch.empty((N, oc, H, W), dtype=torch.float32, device=self.device)
             skip = first if k == L - 2 else None          # long skip: x_{L-1} = a_{L-2} + a_0 (float AddOp)
-            _lib.check(lib.sesrq_calib_conv(C.byref(desc), a.data_ptr(), skip.data_ptr() if skip is not None else None,
-                                            out.data_ptr(), N, H, W, st))
+            _lib.check(lib.sesrq_calib_conv_q(C.byref(desc), a.data_ptr(), skip.data_ptr() if skip is not None else None,
+                                              out.data_ptr(), N, H, W, self.quan_bits, st))
             if k == 0:
                 first = out
             a = out
         if self.pixel_shuffle > 1:
             scale, zero = self._observe(L, a)                 # quantiser in front of PixelShuffle (test.py:90-91)
             fq = torch.empty_like(a)
-            _lib.check(lib.sesrq_calib_fakequant(a.data_ptr(), fq.data_ptr(), a.numel(), float(np.float32(scale)), zero, st))
+            _lib.check(lib.sesrq_calib_fakequant_q(a.data_ptr(), fq.data_ptr(), a.numel(), float(np.float32(scale)), zero,
+                                                   self.quan_bits, st))
             return torch.nn.functional.pixel_shuffle(fq, self.pixel_shuffle)
         self._observe(L, a)                                   # nets without PixelShuffle: range of the last conv's output (quan_func.py:460-479)
         return a
@@ -217,9 +222,9 @@ class Calibrator:
             mn, mx = self.run_min[k], self.run_max[k]
             if self.method == "entropy":
                 lo32, hi32 = float(np.float32(mn)), float(np.float32(mx))       # the edges the histogram kernel used
-                mn, mx = entropy_range(self.hist[k].cpu().numpy().astype(np.int64), lo32, hi32)
+                mn, mx = entropy_range(self.hist[k].cpu().numpy().astype(np.int64), lo32, hi32, levels=1 << self.quan_bits)
             self.ranges.append((mn, mx))
-            s, z = calib_scale_zero(0.0 if k == self.L else mn, mx)
+            s, z = calib_scale_zero(0.0 if k == self.L else mn, mx, self.quan_bits)
             scale.append(s)
             zero.append(z)
         return scale, zero
@@ -228,17 +233,21 @@ class Calibrator:
         from .bundle import derive_bundle_from_quantized
         scale, zero = self.finalize()
         return derive_bundle_from_quantized(self.wq, self.sw, self.biases_f, scale, zero, self.pixel_shuffle, name=name,
-                                            pe_acc_bits=self.acc_bits, pe_add_bits=self.add_bits, bias_bit=self.bias_bits)
+                                            pe_acc_bits=self.acc_bits, pe_add_bits=self.add_bits, bias_bit=self.bias_bits,
+                                            quan_bit=self.quan_bits)
 
 
-def finish_calibration(store, L: int):
+def finish_calibration(store, L: int, quan_bits: Optional[int] = None):
     """The tail of the reference's test.py (:185-217): running input.K.{min,max}_val -> final
-    input.K.{scale,zero} for K = 0..L, output domain with min := 0."""
+    input.K.{scale,zero} for K = 0..L, output domain with min := 0, at width quan_bits (None: define.QUAN_BIT)."""
     from .bundle import calib_scale_zero
+    if quan_bits is None:
+        import define
+        quan_bits = int(define.QUAN_BIT)
     scale, zero = [], []
     for k in range(L + 1):
         mn = 0.0 if k == L else float(store[f"input/input.{k}.min_val"])
-        s, z = calib_scale_zero(mn, float(store[f"input/input.{k}.max_val"]))
+        s, z = calib_scale_zero(mn, float(store[f"input/input.{k}.max_val"]), quan_bits)
         scale.append(s)
         zero.append(z)
     store.set_activation_domains(scale, zero)

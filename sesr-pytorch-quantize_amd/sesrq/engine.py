@@ -18,6 +18,8 @@ class GraphedForward:
     def __init__(self, engine, x, want_q, want_f, slot, downstream):
         if downstream and not want_q:
             raise ValueError("a chain hands the int8 output on: want_q must be True")
+        if downstream and any(e.quan_bits != 8 for e in (engine,) + tuple(downstream)):
+            raise ValueError("chained engines need 8-bit nets")
         dt = engine._check_in(x)
         del dt
         if not x.is_contiguous():
@@ -144,6 +146,12 @@ class Engine:
                                "there is no CPU fallback in this package")
         self.bundle = bundle
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        # define.py QUAN_BIT of the bundle: b < 8 is created by sesrq_create_q and runs on the dot4 kernels
+        self.quan_bits = int(getattr(bundle, "quan_bits", 8))
+        if self.quan_bits != 8 and upstream is not None:
+            raise ValueError(f"chained engines (upstream=) need 8-bit nets; this bundle is {self.quan_bits}-bit")
+        if upstream is not None and int(getattr(upstream, "quan_bits", 8)) != 8:
+            raise ValueError(f"chained engines (upstream=) need 8-bit nets; the upstream bundle is {upstream.quan_bits}-bit")
         self.anchor_add = bool(anchor_add)          # the fp32 output carries the x2 anchor (sesrq.quality.evaluate checks it)
         L = bundle.L
         self._keep = []
@@ -188,7 +196,10 @@ class Engine:
         self.i8_in_scale = float(opts.i8_in_scale)   # > 0: an int8 input is an upstream net's output, not q0 (forward_raw refuses)
         handle = C.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().sesrq_create(C.byref(desc), C.byref(opts), C.byref(handle)), ValueError)
+            if self.quan_bits == 8:
+                _lib.check(_lib.lib().sesrq_create(C.byref(desc), C.byref(opts), C.byref(handle)), ValueError)
+            else:
+                _lib.check(_lib.lib().sesrq_create_q(C.byref(desc), C.byref(opts), self.quan_bits, C.byref(handle)), ValueError)
         self._h = handle
         self._ws: Dict[tuple, torch.Tensor] = {}
         self._raw_q0: Dict[tuple, torch.Tensor] = {}
@@ -315,7 +326,8 @@ class Engine:
         engine keeps -- and run through the same forward as an int8 q0 input: the results are those of forward() on the reference's
         fp32 input frame (self_dataset.py TestDataset).  Both launches go to `stream` (default: current), ordered as forward() orders
         them; give concurrent in-flight frames different slots.  Only for nets with 3 input channels whose int8 input is q0 (no
-        `upstream`) and without the fp32 anchor."""
+        `upstream`) and without the fp32 anchor.  A net narrower than 8 bits takes the unpack's fp32 frame and the fp32 forward (the
+        unpack's q0 is 8-bit): the same bits as forward() on that frame."""
         from . import raw as rawmod
         if self.bundle.in_channels != 3:
             raise ValueError(f"forward_raw: a raw RGGB frame feeds 3-channel nets; this one takes {self.bundle.in_channels}")
@@ -330,9 +342,10 @@ class Engine:
         with torch.cuda.device(self.device):
             raw = raw.contiguous()
             key = (N, H, W, slot)
+            narrow = self.quan_bits != 8
             q0 = self._raw_q0.get(key)
-            if q0 is None:
-                q0 = self._raw_q0[key] = torch.empty((N, 3, H, W), dtype=torch.int8, device=self.device)
+            if q0 is None:      # q0, or the fp32 frame of a narrow net
+                q0 = self._raw_q0[key] = torch.empty((N, 3, H, W), dtype=torch.float32 if narrow else torch.int8, device=self.device)
             shp = self.out_shape(N, H, W)
             if want_q and out_q is None:
                 out_q = torch.empty(shp, dtype=torch.int8, device=self.device)
@@ -340,8 +353,9 @@ class Engine:
                 out_f = torch.empty(shp, dtype=torch.float32, device=self.device)
             ws = self.workspace(N, H, W, slot)
             st = self._enter_stream(stream, raw, q0, out_q, out_f, ws)
-            rawmod.launch(self.device, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, raw, q0, None, st)
-            rc = _lib.lib().sesrq_forward(self._h, q0.data_ptr(), _lib.I8, out_q.data_ptr() if want_q else None,
+            rawmod.launch(self.device, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, raw, None if narrow else q0,
+                          q0 if narrow else None, st)
+            rc = _lib.lib().sesrq_forward(self._h, q0.data_ptr(), _lib.F32 if narrow else _lib.I8, out_q.data_ptr() if want_q else None,
                                           out_f.data_ptr() if want_f else None, N, H, W, ws.data_ptr(), ws.numel(), st.cuda_stream)
         _lib.check(rc)
         return (out_q if want_q else None), (out_f if want_f else None)
@@ -357,7 +371,8 @@ class Engine:
         reference's fp32 input frame (self_dataset_sr.py TestDataset).  An anchor_add engine needs the fp32 frame for its anchor: the
         images are decoded into the fp32 frame instead (a kept buffer too) and run through the fp32 forward.  Both launches go to
         `stream` (default: current), ordered as forward() orders them; give concurrent in-flight frames different slots.  Not for
-        engines whose int8 input is an upstream net's output."""
+        engines whose int8 input is an upstream net's output.  A net narrower than 8 bits takes the fp32 frame too (the decoder's q0
+        is 8-bit): the same bits as forward() on that frame."""
         from . import image as imgmod
         cin = self.bundle.in_channels
         f = imgmod._form(form if form is not None else ("y" if cin == 1 else "rgb"))
@@ -374,9 +389,10 @@ class Engine:
         with torch.cuda.device(self.device):
             img = img.contiguous()
             key = (N, H, W, slot)
+            fp = self.anchor_add or self.quan_bits != 8
             buf = self._img_in.get(key)
-            if buf is None:     # q0, or the fp32 frame an anchored forward adds back
-                buf = self._img_in[key] = torch.empty((N, cin, H, W), dtype=torch.float32 if self.anchor_add else torch.int8,
+            if buf is None:     # q0, or the fp32 frame an anchored forward adds back / a narrow net quantises itself
+                buf = self._img_in[key] = torch.empty((N, cin, H, W), dtype=torch.float32 if fp else torch.int8,
                                                       device=self.device)
             shp = self.out_shape(N, H, W)
             if want_q and out_q is None:
@@ -385,9 +401,9 @@ class Engine:
                 out_f = torch.empty(shp, dtype=torch.float32, device=self.device)
             ws = self.workspace(N, H, W, slot)
             st = self._enter_stream(stream, img, buf, out_q, out_f, ws)
-            q0, x = (None, buf) if self.anchor_add else (buf, None)
+            q0, x = (None, buf) if fp else (buf, None)
             imgmod.launch(self.device, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, img, f, order, q0, x, st)
-            rc = _lib.lib().sesrq_forward(self._h, buf.data_ptr(), _lib.F32 if self.anchor_add else _lib.I8,
+            rc = _lib.lib().sesrq_forward(self._h, buf.data_ptr(), _lib.F32 if fp else _lib.I8,
                                           out_q.data_ptr() if want_q else None, out_f.data_ptr() if want_f else None, N, H, W,
                                           ws.data_ptr(), ws.numel(), st.cuda_stream)
         _lib.check(rc)

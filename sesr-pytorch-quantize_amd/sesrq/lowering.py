@@ -40,6 +40,8 @@ def lower(gm: torch.fx.GraphModule, store=STORE) -> Bundle:
     wq, wsc, biases, relu = [], [], [], []
     widths = None
     prev_tail = None
+    import define
+    qb = int(define.QUAN_BIT)          # the width the graph was spliced for (sim.py passes define.QUAN_BIT to every quantiser)
     for k, c in enumerate(convs):
         # ---- stages in front of the conv
         r = c.args[0]
@@ -49,8 +51,8 @@ def lower(gm: torch.fx.GraphModule, store=STORE) -> Bundle:
         q = r.args[0]
         if _fname(q) != _STAGE_ORDER_IN[0]:
             raise RuntimeError(f"sesrq lowering: conv {k} lacks quantize_asymmetrical_by_tensor in front of the PE split")
-        if q.kwargs.get("exe_mode") != 1 or q.kwargs.get("func_id") != k or q.kwargs.get("width") != 8:
-            raise RuntimeError(f"sesrq lowering: conv {k}: quantiser must be exe_mode=1, width=8, func_id={k} "
+        if q.kwargs.get("exe_mode") != 1 or q.kwargs.get("func_id") != k or q.kwargs.get("width") != qb:
+            raise RuntimeError(f"sesrq lowering: conv {k}: quantiser must be exe_mode=1, width={qb} (define.QUAN_BIT), func_id={k} "
                                f"(got {dict(q.kwargs)}); exe_mode 0 (calibration) is not lowered")
         if int(r.kwargs.get("pe_num", 4)) != 4:
             raise RuntimeError("sesrq lowering: pe_num must be 4")
@@ -90,9 +92,9 @@ def lower(gm: torch.fx.GraphModule, store=STORE) -> Bundle:
                 or mod.padding != (mod.kernel_size[0] // 2,) * 2:
             raise RuntimeError(f"sesrq lowering: conv {k} must be stride-1 'same' k x k")
         wt = mod.weight.detach().cpu().numpy()
-        if not np.array_equal(wt, np.rint(wt)) or wt.min() < -128 or wt.max() > 127:
-            raise RuntimeError(f"sesrq lowering: conv {k} weights are not INT8-valued; run "
-                               "quantize_model_weight(model, 8, 1) before splicing (sim.py:85)")
+        if not np.array_equal(wt, np.rint(wt)) or wt.min() < -(1 << (qb - 1)) or wt.max() > (1 << (qb - 1)) - 1:
+            raise RuntimeError(f"sesrq lowering: conv {k} weights are not {qb}-bit integers; run "
+                               f"quantize_model_weight(model, {qb}, 1) before splicing (sim.py:85)")
         wq.append(wt.astype(np.int8))
         sc_k = store[f"weight/conv.weight.{k}.scale"]
         # a scalar (the reference) or, with define.WEIGHT_PER_CHANNEL, an [OC] tensor: per-channel requant constants for this layer
@@ -112,7 +114,7 @@ def lower(gm: torch.fx.GraphModule, store=STORE) -> Bundle:
     import define
     return derive_bundle_from_quantized(wq, wsc, biases, scale, zero, ps, name=type(gm).__name__, bias_bit=bias_w,
                                         requan_bit=define.REQUAN_BIT, requan_n_max=define.REQUAN_N_MAX, pe_num=pe_num,
-                                        pe_acc_bits=pe_acc, pe_add_bits=pe_add)
+                                        pe_acc_bits=pe_acc, pe_add_bits=pe_add, quan_bit=int(define.QUAN_BIT))
 
 
 def graph_mode(gm: torch.fx.GraphModule) -> int:
@@ -152,8 +154,9 @@ def lower_calibration(gm: torch.fx.GraphModule, device, store=STORE):
     for n in gm.graph.nodes:
         if n.op == "call_module" and isinstance(modules[n.target], nn.PixelShuffle):
             ps = int(modules[n.target].upscale_factor)
+    import define
     return Calibrator(None, biases, ps, device, pe_acc_bits=widths[1], pe_add_bits=widths[0], bias_bits=widths[2],
-                      quantized=quantized)
+                      quantized=quantized, quan_bits=int(define.QUAN_BIT))
 
 
 class SesrqGraphModule(torch.fx.GraphModule):

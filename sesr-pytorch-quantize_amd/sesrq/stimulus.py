@@ -161,6 +161,7 @@ def write_all(bundle, taps: Dict[str, np.ndarray], root: str = "output_txt", end
     pe_out{k} (4,OC,H,W), pe_add{k} (1,OC,H,W) as returned by Engine.forward_debug (frame 0).  Writes the
     reference's output_txt/ tree and returns the list of files."""
     L = bundle.L
+    qb = int(getattr(bundle, "quan_bits", 8))      # define.py QUAN_BIT: the hex width of weights and activations
     written = []
 
     def put(rel, text):
@@ -171,14 +172,14 @@ def write_all(bundle, taps: Dict[str, np.ndarray], root: str = "output_txt", end
         written.append(path)
 
     for k, l in enumerate(bundle.layers):
-        put(f"weight/conv.weight.{k}.txt", weight_txt(l.wq))
+        put(f"weight/conv.weight.{k}.txt", weight_txt(l.wq, qb))
     ks = [0] + [int(l.wq.shape[2]) for l in bundle.layers]
     acts = [np.asarray(taps[f"input{k}"]) for k in range(L + 1)]
     if end2end:
-        put("input/input.0.txt", end2end_txt(acts[0]))
-        put(f"input/input.{L}.txt", end2end_txt(acts[L]))
+        put("input/input.0.txt", end2end_txt(acts[0], qb))
+        put(f"input/input.{L}.txt", end2end_txt(acts[L], qb))
     else:
-        for k, text in enumerate(input_tiles_txt(acts, ks)):
+        for k, text in enumerate(input_tiles_txt(acts, ks, qb)):
             put(f"input/input.{k}.txt", text)
     put("bias/param_buf.txt", param_buf_txt([l.add_const for l in bundle.layers], [l.M for l in bundle.layers], bundle.M_res))
     for k in range(L):

@@ -90,13 +90,13 @@ def load_checkpoint(model, ckpt, mflag):
 
 def splice(model, qmode=1):
     """The four graph rewrites of the reference, in the reference's order (sim.py:85-114)."""
-    model = quantize_model_weight(model, QUAN_BIT, qmode)
+    model = quantize_model_weight(model, define.QUAN_BIT, qmode)
 
     def one(fn, kw):
         m = NodeInsertMapping()
         m.add_config(NodeInsertMappingElement(torch.nn.Conv2d, FunctionPackage(fn, kw)))
         return m
-    model = insert_before(model_input=model, insert_mapping=one(quantize_asymmetrical_by_tensor, {"width": QUAN_BIT, "exe_mode": qmode}),
+    model = insert_before(model_input=model, insert_mapping=one(quantize_asymmetrical_by_tensor, {"width": define.QUAN_BIT, "exe_mode": qmode}),
                           has_func_id=True)
     model = insert_before(model_input=model, insert_mapping=one(reshape_input_for_hardware_pe, {"pe_num": PE}))
     model = insert_after(model_input=model, insert_mapping=one(requan_conv2d_output, {"exe_mode": qmode}))
@@ -108,7 +108,7 @@ def splice(model, qmode=1):
 
 def banner(mflag):
     print("SIM_mflag:", mflag)
-    print("QUAN_BIT:", QUAN_BIT)
+    print("QUAN_BIT:", define.QUAN_BIT)
     print("BIAS_BIT:", BIAS_BIT)
     print("PE_ACC_BIT:", PE_ACC_BIT)
     print("PE_ADD_BIT:", PE_ADD_BIT)
@@ -139,7 +139,11 @@ def main(argv=None):
                                  "8-bit HR image (.png, or a uint8 .npy with --image) is formed as self_dataset_sr.py forms its gt")
     ap.add_argument("--dump", help="write the parameter store as an output_pt-compatible tree here (what the define.py *_W_FLG "
                                    "switches select, plus weights and activation domains); all dump switches are turned on")
+    ap.add_argument("--quan-bit", type=int, default=None, help="define.py QUAN_BIT for this run (2..8; default: define.QUAN_BIT): "
+                                                               "the width of weights and activations")
     args = ap.parse_args(argv)
+    if args.quan_bit is not None:
+        define.QUAN_BIT = args.quan_bit
     define.check()
     if args.dump:
         for n in ("WEIGHT_W_FLG", "INPUT_W_FLG", "BIAS_W_FLG", "BIAS_QUAN_W_FLG", "OUTPUT_PE_W_FLG", "OUTPUT_PE_ADD_W_FLG", "REQUAN_FACTOR_W_FLG"):

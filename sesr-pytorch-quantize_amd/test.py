@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 import define
-from define import QUAN_BIT, PE, BIAS_BIT, PE_ACC_BIT, PE_ADD_BIT
+from define import PE, BIAS_BIT, PE_ACC_BIT, PE_ADD_BIT
 from myQL.quan_func import quantize_model_weight, quantize_asymmetrical_by_tensor, reshape_input_for_hardware_pe, PEs_and_bias_adder
 from myQL.quan_classes import NodeInsertMapping, FunctionPackage, NodeInsertMappingElement
 from myQL.graph_modify import insert_before, insert_bias_bypass
@@ -23,9 +23,9 @@ import sim
 def splice_calibration(model):
     """The three graph rewrites of the reference's calibration script, qmode = 0 (test.py:79-106)."""
     qmode = 0
-    model = quantize_model_weight(model, QUAN_BIT, qmode)
+    model = quantize_model_weight(model, define.QUAN_BIT, qmode)
     mapping = NodeInsertMapping()
-    quan = FunctionPackage(quantize_asymmetrical_by_tensor, {"width": QUAN_BIT, "exe_mode": qmode})
+    quan = FunctionPackage(quantize_asymmetrical_by_tensor, {"width": define.QUAN_BIT, "exe_mode": qmode})
     mapping.add_config(NodeInsertMappingElement(torch.nn.Conv2d, quan))
     mapping.add_config(NodeInsertMappingElement(torch.nn.PixelShuffle, quan))
     model = insert_before(model_input=model, insert_mapping=mapping, has_func_id=True)
@@ -51,8 +51,13 @@ def main(argv=None):
     ap.add_argument("--bins", type=int, default=2048, help="histogram bins of --method entropy")
     ap.add_argument("--save-bundle")
     ap.add_argument("--save-output-pt", help="directory to write input.K.{min_val,max_val,scale,zero}.pt like the reference")
+    ap.add_argument("--quan-bit", type=int, default=None, help="define.py QUAN_BIT for this run (2..8; default: define.QUAN_BIT): "
+                                                               "the width the activation domains are calibrated for")
     args = ap.parse_args(argv)
+    if args.quan_bit is not None:
+        define.QUAN_BIT = args.quan_bit
     define.check()
+    print("QUAN_BIT:", define.QUAN_BIT)
     STORE.clear()
     model = splice_calibration(sim.float_model(args.mflag, args.ckpt, args.params))
     frames = torch.load(args.frames, weights_only=True, map_location="cpu") if args.frames.endswith(".pt") else torch.from_numpy(np.load(args.frames))
@@ -77,7 +82,7 @@ def main(argv=None):
         print("scale:", s)
         print("zero:", z)
     print("calibrate end")
-    print("bit:", QUAN_BIT)
+    print("bit:", define.QUAN_BIT)
     if args.save_output_pt:
         STORE.save_output_pt(args.save_output_pt)
     if args.save_bundle:
