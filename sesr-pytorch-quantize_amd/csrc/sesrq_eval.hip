@@ -15,13 +15,11 @@
 // pair gives 1.0.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 
 #include "sesrq_eval.h"
+#include "sesrq_side.h"
 
 namespace sesrq_evalk {
 
@@ -265,16 +263,7 @@ __global__ __launch_bounds__(FIN_THREADS) void eval_finish(const double *part, i
 enum { K_F32_RGB, K_I8_RGB, K_F32_Y255, K_I8_Y255, K_F32_X2, K_FINISH, K_COUNT };
 static const char *const kNames[K_COUNT] = {"eval_tile<f32,rgb>", "eval_tile<i8,rgb>", "eval_tile<f32,y255>",
                                             "eval_tile<i8,y255>", "eval_tile<f32,x2>", "eval_finish"};
-static std::atomic<long long> g_launches[K_COUNT];
-static thread_local char g_err[512];
-
-static int fail(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return 1;
-}
+static Counters<K_COUNT> g_count{kNames};
 
 static int expected_channels(int form) { return form == SESRQ_EVAL_Y255 ? 1 : 3; }
 
@@ -340,18 +329,18 @@ extern "C" int sesrq_eval(const sesrq_eval_desc *d, const void *pred, const floa
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail("sesrq_eval: tile kernel launch: %s", hipGetErrorString(e));
-    ++g_launches[k];
+    ++g_count.launches[k];
     eval_finish<<<N, FIN_THREADS, 0, st>>>(a.part, g.ntiles, d->form, C, H, W, out);
     e = hipGetLastError();
     if (e != hipSuccess) return fail("sesrq_eval: finish kernel launch: %s", hipGetErrorString(e));
-    ++g_launches[K_FINISH];
+    ++g_count.launches[K_FINISH];
     return 0;
 }
 
-extern "C" int sesrq_eval_kernel_count(void) { return K_COUNT; }
+extern "C" int sesrq_eval_kernel_count(void) { return g_count.count(); }
 
-extern "C" const char *sesrq_eval_kernel_name(int i) { return i >= 0 && i < K_COUNT ? kNames[i] : nullptr; }
+extern "C" const char *sesrq_eval_kernel_name(int i) { return g_count.name(i); }
 
-extern "C" long long sesrq_eval_kernel_launches(int i) { return i >= 0 && i < K_COUNT ? g_launches[i].load() : -1; }
+extern "C" long long sesrq_eval_kernel_launches(int i) { return g_count.get(i); }
 
 extern "C" const char *sesrq_eval_last_error(void) { return g_err; }

@@ -18,13 +18,11 @@
 // them interleaved as whole 16-byte words (48 bytes for C = 3, 16 for C = 1).
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 
 #include "sesrq_image.h"
+#include "sesrq_side.h"
 
 namespace sesrq_imgk {
 
@@ -250,43 +248,17 @@ __global__ __launch_bounds__(THREADS) void image_export(ExportArgs a) {
 using namespace sesrq_imgk;
 
 struct sesrq_image_ctx_s {
-    Tables *tab;       // device
-    int device;
-    int num_cu;
-    float s0, r0, z0;
-    int recip;
+    DeviceTable t;     // Tables
+    InQuant q;
 };
 
 enum { K_YQ = 0, K_YF, K_YQF, K_RQ, K_RF, K_RQF, K_EF1, K_EF3, K_EQ1, K_EQ3, K_COUNT };
 static const char *const kNames[K_COUNT] = {
     "image_decode<Y,q0>", "image_decode<Y,x>", "image_decode<Y,q0,x>", "image_decode<RGB,q0>", "image_decode<RGB,x>",
     "image_decode<RGB,q0,x>", "image_export<f32,C1>", "image_export<f32,C3>", "image_export<i8,C1>", "image_export<i8,C3>"};
-static std::atomic<long long> g_launches[K_COUNT];
-static thread_local char g_err[512];
+static Counters<K_COUNT> g_count{kNames};
 
-static int fail(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return 1;
-}
-
-static int check_domain(const char *who, float scale_in, int zero_in, int exact_div) {
-    if (!(scale_in > 0.f) || !std::isfinite(scale_in)) return fail("%s: scale_in must be positive and finite", who);
-    if (zero_in < -(1 << 24) || zero_in > (1 << 24)) return fail("%s: zero_in %d is not exact in fp32", who, zero_in);
-    if (exact_div < 0 || exact_div > 2) return fail("%s: exact_div %d (0, 1 or 2)", who, exact_div);
-    return 0;
-}
-
-static int8_t host_quant(float x, float s0, float r0, float z0, int recip) {
-    const float t = recip ? x * r0 : x / s0;              // true IEEE quotient, as torch's CPU tensor / scalar
-    const float q = rintf(t + z0);                        // round half to even, as torch.round
-    return (int8_t)fminf(fmaxf(q, -128.f), 127.f);
-}
-
-static void build(float s0, int z0, int exact_div, Tables &t) {
-    const volatile float r = 1.0f / s0;                   // exact_div 2: fl(1 / s0), formed once
+static void build(const InQuant &q, Tables &t) {
     for (int v = 0; v < CODES; ++v) {
         const volatile double d = (double)v / 255.0;      // d(v), correctly rounded
         t.y[0][v] = 65.481 * d;
@@ -294,7 +266,7 @@ static void build(float s0, int z0, int exact_div, Tables &t) {
         t.y[2][v] = 24.966 * d;
         const float x = fminf(fmaxf((float)d, 0.f), 1.f);
         t.x[v] = x;
-        t.q[v] = host_quant(x, s0, r, (float)z0, exact_div == 2);
+        t.q[v] = host_quant(x, q);
     }
 }
 
@@ -303,7 +275,7 @@ extern "C" int sesrq_image_table(float scale_in, int zero_in, int exact_div, int
     if (!q || !x) return fail("sesrq_image_table: q or x is NULL");
     if (check_domain("sesrq_image_table", scale_in, zero_in, exact_div)) return 1;
     static thread_local Tables t;
-    build(scale_in, zero_in, exact_div, t);
+    build(in_quant(scale_in, zero_in, exact_div), t);
     for (int v = 0; v < CODES; ++v) {
         q[v] = t.q[v];
         x[v] = t.x[v];
@@ -316,20 +288,13 @@ extern "C" int sesrq_image_create(float scale_in, int zero_in, int exact_div, se
     if (!out) return fail("sesrq_image_create: ctx is NULL");
     *out = nullptr;
     if (check_domain("sesrq_image_create", scale_in, zero_in, exact_div)) return 1;
-    Tables *host = new Tables();
-    build(scale_in, zero_in, exact_div, *host);
     auto *c = new sesrq_image_ctx_s();
-    c->s0 = scale_in;
-    c->r0 = 1.0f / scale_in;
-    c->z0 = (float)zero_in;
-    c->recip = exact_div == 2;
-    hipError_t e = hipGetDevice(&c->device);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&c->num_cu, hipDeviceAttributeMultiprocessorCount, c->device);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->tab), sizeof(Tables));
-    if (e == hipSuccess) e = hipMemcpy(c->tab, host, sizeof(Tables), hipMemcpyHostToDevice);
+    c->q = in_quant(scale_in, zero_in, exact_div);
+    Tables *host = new Tables();
+    build(c->q, *host);
+    const hipError_t e = table_create(c->t, host, sizeof(Tables));
     delete host;
     if (e != hipSuccess) {
-        if (c->tab) (void)hipFree(c->tab);
         delete c;
         return fail("sesrq_image_create: %s", hipGetErrorString(e));
     }
@@ -339,7 +304,7 @@ extern "C" int sesrq_image_create(float scale_in, int zero_in, int exact_div, se
 
 extern "C" void sesrq_image_destroy(sesrq_image_ctx c) {
     if (!c) return;
-    if (c->tab) (void)hipFree(c->tab);
+    table_destroy(c->t);
     delete c;
 }
 
@@ -355,11 +320,6 @@ static int runs(const char *who, int N, int H, int W, int num_cu, int &segs, int
     return 0;
 }
 
-static int grid_of(int items, int num_cu) {
-    const long long want = ((long long)items + THREADS - 1) / THREADS, cap = (long long)num_cu * BLOCKS_PER_CU;
-    return (int)(want < cap ? want : cap);
-}
-
 extern "C" int sesrq_image_decode(sesrq_image_ctx c, const uint8_t *img, int form, int order, int8_t *q0, float *x, int N, int H, int W,
                                   void *stream) {
     g_err[0] = 0;
@@ -369,26 +329,24 @@ extern "C" int sesrq_image_decode(sesrq_image_ctx c, const uint8_t *img, int for
     if (form != SESRQ_IMAGE_Y && form != SESRQ_IMAGE_RGB) return fail("sesrq_image_decode: form %d (0 = Y, 1 = RGB)", form);
     if (order != SESRQ_IMAGE_ORDER_RGB && order != SESRQ_IMAGE_ORDER_BGR) return fail("sesrq_image_decode: order %d (0 = RGB, 1 = BGR)", order);
     int segs, items;
-    if (runs("sesrq_image_decode", N, H, W, c->num_cu, segs, items)) return 1;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != c->device)
-        return fail("sesrq_image_decode: the context lives on device %d, device %d is current", c->device, dev);
+    if (runs("sesrq_image_decode", N, H, W, c->t.num_cu, segs, items)) return 1;
+    if (table_on_current("sesrq_image_decode", c->t)) return 1;
 
     DecodeArgs a;
     a.img = img;
-    a.tab = c->tab;
+    a.tab = static_cast<const Tables *>(c->t.ptr);
     a.q0 = q0;
     a.x = x;
     a.HW = H * W;
     a.segs = segs;
     a.items = items;
     a.bgr = order == SESRQ_IMAGE_ORDER_BGR;
-    a.recip = c->recip;
+    a.recip = c->q.recip;
     a.planes16 = a.HW % SEG == 0;
-    a.s0 = c->s0;
-    a.r0 = c->r0;
-    a.z0 = c->z0;
-    const int grid = grid_of(items, c->num_cu);
+    a.s0 = c->q.s0;
+    a.r0 = c->q.r0;
+    a.z0 = c->q.z0;
+    const int grid = grid_cap(items, THREADS, c->t.num_cu, BLOCKS_PER_CU);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int out = (q0 ? OUT_Q : 0) | (x ? OUT_F : 0);
     int k;
@@ -407,7 +365,7 @@ extern "C" int sesrq_image_decode(sesrq_image_ctx c, const uint8_t *img, int for
 #undef SESRQ_IMAGE_DECODE
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail("sesrq_image_decode: kernel launch: %s", hipGetErrorString(e));
-    ++g_launches[k];
+    ++g_count.launches[k];
     return 0;
 }
 
@@ -441,7 +399,7 @@ extern "C" int sesrq_image_export(const void *pred, int pred_dtype, float scale,
     a.planes16 = a.HW % SEG == 0;
     a.scale = scale;
     a.zero = zero;
-    const int grid = grid_of(items, num_cu);
+    const int grid = grid_cap(items, THREADS, num_cu, BLOCKS_PER_CU);
     hipStream_t st = static_cast<hipStream_t>(stream);
     int k;
     if (pred_dtype == SESRQ_IMAGE_F32) {
@@ -455,14 +413,14 @@ extern "C" int sesrq_image_export(const void *pred, int pred_dtype, float scale,
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail("sesrq_image_export: kernel launch: %s", hipGetErrorString(e));
-    ++g_launches[k];
+    ++g_count.launches[k];
     return 0;
 }
 
-extern "C" int sesrq_image_instance_count(void) { return K_COUNT; }
+extern "C" int sesrq_image_instance_count(void) { return g_count.count(); }
 
-extern "C" const char *sesrq_image_instance_name(int i) { return i >= 0 && i < K_COUNT ? kNames[i] : nullptr; }
+extern "C" const char *sesrq_image_instance_name(int i) { return g_count.name(i); }
 
-extern "C" long long sesrq_image_instance_launches(int i) { return i >= 0 && i < K_COUNT ? g_launches[i].load() : -1; }
+extern "C" long long sesrq_image_instance_launches(int i) { return g_count.get(i); }
 
 extern "C" const char *sesrq_image_last_error(void) { return g_err; }

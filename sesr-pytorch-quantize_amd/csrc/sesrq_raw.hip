@@ -12,13 +12,11 @@
 // aligned (W % 8 != 0, or unaligned buffers) take the per-pixel path of the same kernel.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 
 #include "sesrq_raw.h"
+#include "sesrq_side.h"
 
 namespace sesrq_rawk {
 
@@ -125,38 +123,22 @@ __global__ __launch_bounds__(THREADS) void raw_unpack(UnpackArgs a) {
 using namespace sesrq_rawk;
 
 struct sesrq_raw_ctx_s {
-    int8_t *table;     // device
-    int device;
-    int num_cu;
+    DeviceTable t;     // SESRQ_RAW_CODES bytes of q0
 };
 
 enum { K_Q = 0, K_F, K_QF, K_COUNT };
 static const char *const kNames[K_COUNT] = {"raw_unpack<q0>", "raw_unpack<spread>", "raw_unpack<q0,spread>"};
-static std::atomic<long long> g_launches[K_COUNT];
-static thread_local char g_err[512];
-
-static int fail(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return 1;
-}
+static Counters<K_COUNT> g_count{kNames};
 
 extern "C" int sesrq_raw_table(float scale_in, int zero_in, int exact_div, int8_t table[SESRQ_RAW_CODES]) {
     g_err[0] = 0;
     if (!table) return fail("sesrq_raw_table: table is NULL");
-    if (!(scale_in > 0.f) || !std::isfinite(scale_in)) return fail("sesrq_raw_table: scale_in must be positive and finite");
-    if (zero_in < -(1 << 24) || zero_in > (1 << 24)) return fail("sesrq_raw_table: zero_in %d is not exact in fp32", zero_in);
-    if (exact_div < 0 || exact_div > 2) return fail("sesrq_raw_table: exact_div %d (0, 1 or 2)", exact_div);
-    const volatile float r = 1.0f / scale_in;            // exact_div 2: fl(1 / s0), formed once
-    const float z = (float)zero_in;
+    if (check_domain("sesrq_raw_table", scale_in, zero_in, exact_div)) return 1;
+    const InQuant d = in_quant(scale_in, zero_in, exact_div);
     for (int v = 0; v < SESRQ_RAW_CODES; ++v) {
         float x = (float)v / (float)CODE_MAX;                // true IEEE quotient, as torch's CPU tensor / scalar
         x = fminf(fmaxf(x, 0.f), 1.f);
-        const float t = exact_div == 2 ? x * r : x / scale_in;
-        const float q = rintf(t + z);                        // round half to even, as torch.round
-        table[v] = (int8_t)fminf(fmaxf(q, -128.f), 127.f);
+        table[v] = host_quant(x, d);
     }
     return 0;
 }
@@ -168,12 +150,8 @@ extern "C" int sesrq_raw_create(float scale_in, int zero_in, int exact_div, sesr
     int8_t host[SESRQ_RAW_CODES];
     if (sesrq_raw_table(scale_in, zero_in, exact_div, host)) return 1;
     auto *c = new sesrq_raw_ctx_s();
-    hipError_t e = hipGetDevice(&c->device);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&c->num_cu, hipDeviceAttributeMultiprocessorCount, c->device);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->table), SESRQ_RAW_CODES);
-    if (e == hipSuccess) e = hipMemcpy(c->table, host, SESRQ_RAW_CODES, hipMemcpyHostToDevice);
+    const hipError_t e = table_create(c->t, host, SESRQ_RAW_CODES);
     if (e != hipSuccess) {
-        if (c->table) (void)hipFree(c->table);
         delete c;
         return fail("sesrq_raw_create: %s", hipGetErrorString(e));
     }
@@ -183,7 +161,7 @@ extern "C" int sesrq_raw_create(float scale_in, int zero_in, int exact_div, sesr
 
 extern "C" void sesrq_raw_destroy(sesrq_raw_ctx c) {
     if (!c) return;
-    if (c->table) (void)hipFree(c->table);
+    table_destroy(c->t);
     delete c;
 }
 
@@ -194,15 +172,13 @@ extern "C" int sesrq_raw_unpack(sesrq_raw_ctx c, const uint16_t *raw, int8_t *q0
     if (!q0 && !spread) return fail("sesrq_raw_unpack: neither q0 nor spread requested");
     if (N < 1 || H < 1 || W < 1) return fail("sesrq_raw_unpack: empty frame (N = %d, H = %d, W = %d)", N, H, W);
     const long long segs = (W + SEG - 1) / SEG, items = (long long)N * H * segs;
-    if (items > 0x7fffffffLL - (long long)THREADS * c->num_cu * BLOCKS_PER_CU)
+    if (items > 0x7fffffffLL - (long long)THREADS * c->t.num_cu * BLOCKS_PER_CU)
         return fail("sesrq_raw_unpack: frame of %d x %d x %d is too large", N, H, W);
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != c->device)
-        return fail("sesrq_raw_unpack: the context lives on device %d, device %d is current", c->device, dev);
+    if (table_on_current("sesrq_raw_unpack", c->t)) return 1;
 
     UnpackArgs a;
     a.raw = raw;
-    a.table = c->table;
+    a.table = static_cast<const int8_t *>(c->t.ptr);
     a.q0 = q0;
     a.spread = spread;
     a.H = H;
@@ -211,8 +187,7 @@ extern "C" int sesrq_raw_unpack(sesrq_raw_ctx c, const uint16_t *raw, int8_t *q0
     a.items = (int)items;
     a.vec = W % SEG == 0 && reinterpret_cast<uintptr_t>(raw) % 16 == 0 && reinterpret_cast<uintptr_t>(q0) % 8 == 0 &&
             reinterpret_cast<uintptr_t>(spread) % 16 == 0;
-    const long long want = (items + THREADS - 1) / THREADS;
-    const int grid = (int)(want < (long long)c->num_cu * BLOCKS_PER_CU ? want : (long long)c->num_cu * BLOCKS_PER_CU);
+    const int grid = grid_cap(items, THREADS, c->t.num_cu, BLOCKS_PER_CU);
     hipStream_t st = static_cast<hipStream_t>(stream);
     int k;
     if (q0 && spread) {
@@ -227,14 +202,14 @@ extern "C" int sesrq_raw_unpack(sesrq_raw_ctx c, const uint16_t *raw, int8_t *q0
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail("sesrq_raw_unpack: kernel launch: %s", hipGetErrorString(e));
-    ++g_launches[k];
+    ++g_count.launches[k];
     return 0;
 }
 
-extern "C" int sesrq_raw_instance_count(void) { return K_COUNT; }
+extern "C" int sesrq_raw_instance_count(void) { return g_count.count(); }
 
-extern "C" const char *sesrq_raw_instance_name(int i) { return i >= 0 && i < K_COUNT ? kNames[i] : nullptr; }
+extern "C" const char *sesrq_raw_instance_name(int i) { return g_count.name(i); }
 
-extern "C" long long sesrq_raw_instance_launches(int i) { return i >= 0 && i < K_COUNT ? g_launches[i].load() : -1; }
+extern "C" long long sesrq_raw_instance_launches(int i) { return g_count.get(i); }
 
 extern "C" const char *sesrq_raw_last_error(void) { return g_err; }

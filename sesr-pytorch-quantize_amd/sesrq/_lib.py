@@ -1,4 +1,5 @@
-"""ctypes binding of libsesrq.so (C ABI declared in include/sesrq.h).
+"""ctypes binding of libsesrq.so (C ABI declared in include/sesrq.h), and the host plumbing every binding in the package shares:
+the loader (bind, Library), the stream entry of a launch and the input domain of the front ends.
 
 The library is the product: if it is missing or a symbol cannot be resolved this module
 raises immediately -- there is no CPU or PyTorch fallback anywhere in the package.
@@ -101,43 +102,101 @@ SYMBOLS = {
     "sesrq_version": (C.c_int, []),
 }
 
-_lib = None
+
+def bind(path: str, symbols: dict, who: str = "sesrq") -> C.CDLL:
+    """Load the library at `path` and bind every symbol of `symbols` (name -> (restype, argtypes)); raise loudly when it is absent."""
+    if not os.path.isfile(path):
+        raise RuntimeError(f"{who}: native library not found at {path}. Build it with "
+                           "`make -C sesr-pytorch-quantize_amd/csrc` (or __graft_entry__.build()); there is no fallback path.")
+    # PyTorch-ROCm wheels bundle their own libamdhip64 (SONAME libamdhip64.so.7, needed by torch as
+    # "libamdhip64.so").  Loading a library of ours first would pull /opt/rocm's copy in and torch would then
+    # load a SECOND runtime; importing torch first makes the loader satisfy our NEEDED entry by SONAME
+    # with the runtime torch already mapped -> one HIP runtime per process, shared streams/pointers.
+    try:
+        import torch  # noqa: F401
+    except ImportError:  # standalone C/C++ use of the library: system runtime only
+        pass
+    handle = C.CDLL(path)
+    for name, (res, args) in symbols.items():
+        fn = getattr(handle, name)          # AttributeError if the .so lacks a declared symbol
+        fn.restype, fn.argtypes = res, args
+    return handle
 
 
-def lib() -> C.CDLL:
-    """Load libsesrq.so once and bind every declared symbol; raise loudly when it is absent."""
-    global _lib
-    if _lib is None:
-        if not os.path.isfile(LIB_PATH):
-            raise RuntimeError(
-                f"sesrq: native library not found at {LIB_PATH}. Build it with "
-                "`make -C sesr-pytorch-quantize_amd/csrc` (or __graft_entry__.build()); there is no fallback path.")
-        # PyTorch-ROCm wheels bundle their own libamdhip64 (SONAME libamdhip64.so.7, needed by torch as
-        # "libamdhip64.so").  Loading libsesrq.so first would pull /opt/rocm's copy in and torch would then
-        # load a SECOND runtime; importing torch first makes the loader satisfy our NEEDED entry by SONAME
-        # with the runtime torch already mapped -> one HIP runtime per process, shared streams/pointers.
-        try:
-            import torch  # noqa: F401
-        except ImportError:  # standalone C/C++ use of the library: system runtime only
-            pass
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(handle, name)          # AttributeError if the .so lacks a declared symbol
-            fn.restype, fn.argtypes = res, args
-        _lib = handle
-    return _lib
+class Library:
+    """One native library, loaded and bound on first use.  `prefix` names its C entry points: <prefix>_last_error, the launch
+    counters <prefix>_<counters>_{count,name,launches} and, for the raw / image front ends, <prefix>_create of a device context."""
+
+    def __init__(self, path: str, symbols: dict, who: str, prefix: str, counters: str = "instance"):
+        self.path, self.symbols, self.who, self.prefix, self.counters = path, symbols, who, prefix, counters
+        self._handle = None
+        self._ctx = {}          # (device index, f32 scale bits, zero, exact_div) -> context handle; lives as long as the process
+
+    def lib(self) -> C.CDLL:
+        """The library, loaded once with every declared symbol bound; raises loudly when it is absent."""
+        if self._handle is None:
+            self._handle = bind(self.path, self.symbols, self.who)
+        return self._handle
+
+    def last_error(self) -> str:
+        return (getattr(self.lib(), self.prefix + "_last_error")() or b"").decode()
+
+    def instances(self):
+        """{name: launches so far} of every kernel instantiation the library can launch."""
+        l, p = self.lib(), f"{self.prefix}_{self.counters}"
+        name, launches = getattr(l, p + "_name"), getattr(l, p + "_launches")
+        return {name(i).decode(): int(launches(i)) for i in range(getattr(l, p + "_count")())}
+
+    def context(self, device, scale_in, zero_in, exact_div):
+        """The device context (<prefix>_create) of one input domain on `device`, created once."""
+        import numpy as np
+        import torch
+        key = (device.index, np.float32(scale_in).tobytes(), int(zero_in), int(exact_div))
+        h = self._ctx.get(key)
+        if h is None:
+            h, create = C.c_void_p(), getattr(self.lib(), self.prefix + "_create")
+            with torch.cuda.device(device):
+                if create(float(np.float32(scale_in)), int(zero_in), int(exact_div), C.byref(h)) != 0:
+                    raise ValueError(self.last_error())
+            self._ctx[key] = h
+        return h
 
 
-def instances():
-    """{name: launches so far} of every kernel instantiation the library can select (sesrq_instance_*)."""
-    l = lib()
-    return {l.sesrq_instance_name(i).decode(): int(l.sesrq_instance_launches(i)) for i in range(l.sesrq_instance_count())}
-
-
-def last_error() -> str:
-    return (lib().sesrq_last_error() or b"").decode()
+_core = Library(LIB_PATH, SYMBOLS, "sesrq", "sesrq")
+lib, last_error, instances = _core.lib, _core.last_error, _core.instances
 
 
 def check(rc: int, exc=RuntimeError) -> None:
     if rc != 0:
         raise exc("sesrq: " + last_error())
+
+
+def enter_stream(device, stream, *tensors):
+    """The stream to launch on: the current stream of `device` when `stream` is None or is that stream.  Any other stream is
+    ordered after the work already queued on the current stream (which may still be producing an input, or own the memory of
+    freshly allocated outputs), and every tensor the launch touches (None entries are skipped) is recorded on it so that the
+    caching allocator does not recycle it while the kernels run."""
+    import torch
+    cur = torch.cuda.current_stream(device)
+    if stream is None or stream == cur:
+        return cur
+    stream.wait_stream(cur)
+    for t in tensors:
+        if t is not None:
+            t.record_stream(stream)
+    return stream
+
+
+def input_domain(engine_or_bundle, want_q: bool, who: str):
+    """(bundle, scale_in, zero_in, exact_div, device) of a front end's q0 (raw.unpack, image.decode).  An Engine fixes all of them;
+    a Bundle all but the device (None) and exact_div (0); None only allows the fp32 frame: (None, 1.0, 0, 0, None)."""
+    from .bundle import Bundle
+    if engine_or_bundle is None:          # the fp32 frame alone: no input domain involved
+        if want_q:
+            raise ValueError(f"{who}: q0 needs the net's input domain (an Engine or a Bundle)")
+        return None, 1.0, 0, 0, None
+    if isinstance(engine_or_bundle, Bundle):
+        b, exact_div, dev = engine_or_bundle, 0, None
+    else:
+        b, exact_div, dev = engine_or_bundle.bundle, engine_or_bundle.exact_div, engine_or_bundle.device
+    return b, b.scale[0], b.zero[0], exact_div, dev

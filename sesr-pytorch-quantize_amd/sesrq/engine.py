@@ -202,8 +202,7 @@ class Engine:
                 _lib.check(_lib.lib().sesrq_create_q(C.byref(desc), C.byref(opts), self.quan_bits, C.byref(handle)), ValueError)
         self._h = handle
         self._ws: Dict[tuple, torch.Tensor] = {}
-        self._raw_q0: Dict[tuple, torch.Tensor] = {}
-        self._img_in: Dict[tuple, torch.Tensor] = {}
+        self._in: Dict[tuple, torch.Tensor] = {}      # kept input buffers of forward_raw / forward_image
 
     def close(self):
         if getattr(self, "_op_id", None):      # registered as a torch.ops.sesrq.forward handle: the C++ side drops its pointer first
@@ -253,19 +252,35 @@ class Engine:
             self._ws[key] = ws
         return ws
 
-    def _enter_stream(self, stream, *tensors):
-        """Resolve the stream to launch on.  A side stream is ordered after the work already queued on the
-        current stream (which may still be producing `x` or own the memory of freshly allocated outputs),
-        and every tensor the launch touches is recorded on it so the caching allocator does not recycle it
-        while the kernels run."""
-        cur = torch.cuda.current_stream(self.device)
-        if stream is None or stream == cur:
-            return cur
-        stream.wait_stream(cur)
-        for t in tensors:
-            if t is not None:
-                t.record_stream(stream)
-        return stream
+    def _run(self, src, dt, want_q, want_f, out_q, out_f, stream, slot, in_shape=None, decode=None):
+        """What every stream-ordered forward shares: the outputs asked for and not given are allocated, the slot's workspace taken
+        and the stream entered; then `decode(src, inp, stream)` fills a kept (N, C, H, W) input buffer of dtype `dt` from `src`
+        (a front end's launch; without it `src` is the input), and sesrq_forward runs on that input."""
+        with torch.cuda.device(self.device):
+            src = src.contiguous()
+            if decode is None:
+                inp, (N, _, H, W) = src, src.shape
+            else:
+                N, _, H, W = in_shape
+                key = (*in_shape, slot, dt)
+                inp = self._in.get(key)
+                if inp is None:
+                    inp = self._in[key] = torch.empty(in_shape, dtype=torch.float32 if dt == _lib.F32 else torch.int8,
+                                                      device=self.device)
+            shp = self.out_shape(N, H, W)
+            if want_q and out_q is None:
+                out_q = torch.empty(shp, dtype=torch.int8, device=self.device)
+            if want_f and out_f is None:
+                out_f = torch.empty(shp, dtype=torch.float32, device=self.device)
+            ws = self.workspace(N, H, W, slot)
+            st = _lib.enter_stream(self.device, stream, src, inp, out_q, out_f, ws)
+            if decode is not None:
+                decode(src, inp, st)
+            rc = _lib.lib().sesrq_forward(self._h, inp.data_ptr(), dt, out_q.data_ptr() if out_q is not None else None,
+                                          out_f.data_ptr() if out_f is not None else None, N, H, W, ws.data_ptr(), ws.numel(),
+                                          st.cuda_stream)
+        _lib.check(rc)
+        return out_q, out_f
 
     def _check_in(self, x: torch.Tensor):
         if x.dim() != 4:
@@ -300,21 +315,7 @@ class Engine:
                                                 out_f.data_ptr() if want_f else None, N, H, W, ws.data_ptr(), ws.numel(),
                                                 stream.cuda_stream))
             return (out_q if want_q else None), (out_f if want_f else None)
-        with torch.cuda.device(self.device):
-            x = x.contiguous()
-            N, _, H, W = x.shape
-            shp = self.out_shape(N, H, W)
-            if want_q and out_q is None:
-                out_q = torch.empty(shp, dtype=torch.int8, device=self.device)
-            if want_f and out_f is None:
-                out_f = torch.empty(shp, dtype=torch.float32, device=self.device)
-            ws = self.workspace(N, H, W, slot)
-            st = self._enter_stream(stream, x, out_q, out_f, ws).cuda_stream
-            rc = _lib.lib().sesrq_forward(self._h, x.data_ptr(), dt, out_q.data_ptr() if out_q is not None else None,
-                                          out_f.data_ptr() if out_f is not None else None, N, H, W, ws.data_ptr(),
-                                          ws.numel(), st)
-        _lib.check(rc)
-        return out_q, out_f
+        return self._run(x, dt, want_q, want_f, out_q, out_f, stream, slot)
 
     __call__ = forward
 
@@ -339,26 +340,13 @@ class Engine:
             raise ValueError("forward_raw: ask for the int8 output, the fp32 output or both")
         raw = rawmod._frames(raw, self.device)
         N, H, W = raw.shape
-        with torch.cuda.device(self.device):
-            raw = raw.contiguous()
-            key = (N, H, W, slot)
-            narrow = self.quan_bits != 8
-            q0 = self._raw_q0.get(key)
-            if q0 is None:      # q0, or the fp32 frame of a narrow net
-                q0 = self._raw_q0[key] = torch.empty((N, 3, H, W), dtype=torch.float32 if narrow else torch.int8, device=self.device)
-            shp = self.out_shape(N, H, W)
-            if want_q and out_q is None:
-                out_q = torch.empty(shp, dtype=torch.int8, device=self.device)
-            if want_f and out_f is None:
-                out_f = torch.empty(shp, dtype=torch.float32, device=self.device)
-            ws = self.workspace(N, H, W, slot)
-            st = self._enter_stream(stream, raw, q0, out_q, out_f, ws)
-            rawmod.launch(self.device, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, raw, None if narrow else q0,
-                          q0 if narrow else None, st)
-            rc = _lib.lib().sesrq_forward(self._h, q0.data_ptr(), _lib.F32 if narrow else _lib.I8, out_q.data_ptr() if want_q else None,
-                                          out_f.data_ptr() if want_f else None, N, H, W, ws.data_ptr(), ws.numel(), st.cuda_stream)
-        _lib.check(rc)
-        return (out_q if want_q else None), (out_f if want_f else None)
+        narrow = self.quan_bits != 8       # the buffer holds q0, or the fp32 frame of a narrow net
+
+        def unpack(src, buf, st):
+            rawmod.launch(self.device, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, src, None if narrow else buf,
+                          buf if narrow else None, st)
+        return self._run(raw, _lib.F32 if narrow else _lib.I8, want_q, want_f, out_q if want_q else None, out_f if want_f else None,
+                         stream, slot, (N, 3, H, W), unpack)
 
     def forward_image(self, img_u8: torch.Tensor, form=None, order: str = "rgb", want_q: bool = True, want_f: bool = True, out_q=None,
                       out_f=None, stream=None, slot: int = 0):
@@ -386,28 +374,14 @@ class Engine:
         imgmod._order(order)
         img = imgmod._images(img_u8, self.device)
         N, H, W, _ = img.shape
-        with torch.cuda.device(self.device):
-            img = img.contiguous()
-            key = (N, H, W, slot)
-            fp = self.anchor_add or self.quan_bits != 8
-            buf = self._img_in.get(key)
-            if buf is None:     # q0, or the fp32 frame an anchored forward adds back / a narrow net quantises itself
-                buf = self._img_in[key] = torch.empty((N, cin, H, W), dtype=torch.float32 if fp else torch.int8,
-                                                      device=self.device)
-            shp = self.out_shape(N, H, W)
-            if want_q and out_q is None:
-                out_q = torch.empty(shp, dtype=torch.int8, device=self.device)
-            if want_f and out_f is None:
-                out_f = torch.empty(shp, dtype=torch.float32, device=self.device)
-            ws = self.workspace(N, H, W, slot)
-            st = self._enter_stream(stream, img, buf, out_q, out_f, ws)
-            q0, x = (None, buf) if fp else (buf, None)
-            imgmod.launch(self.device, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, img, f, order, q0, x, st)
-            rc = _lib.lib().sesrq_forward(self._h, buf.data_ptr(), _lib.F32 if fp else _lib.I8,
-                                          out_q.data_ptr() if want_q else None, out_f.data_ptr() if want_f else None, N, H, W,
-                                          ws.data_ptr(), ws.numel(), st.cuda_stream)
-        _lib.check(rc)
-        return (out_q if want_q else None), (out_f if want_f else None)
+        # the buffer holds q0, or the fp32 frame an anchored forward adds back / a narrow net quantises itself
+        fp = self.anchor_add or self.quan_bits != 8
+
+        def decode(src, buf, st):
+            imgmod.launch(self.device, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, src, f, order, None if fp else buf,
+                          buf if fp else None, st)
+        return self._run(img, _lib.F32 if fp else _lib.I8, want_q, want_f, out_q if want_q else None, out_f if want_f else None,
+                         stream, slot, (N, cin, H, W), decode)
 
     def submission(self, frames, outs_q, streams, outs_f=None, group: int = 1):
         """A prepared batch of independent forwards for sesrq_forward_many: frame k = frames[k] -> outs_q[k] (/ outs_f[k]; either may be None) on

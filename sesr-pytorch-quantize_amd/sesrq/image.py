@@ -16,6 +16,8 @@ import os
 
 import numpy as np
 
+from . import _lib
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "lib", "libsesrq_image.so"))
 
@@ -42,38 +44,8 @@ SYMBOLS = {
     "sesrq_image_last_error": (C.c_char_p, []),
 }
 
-_lib = None
-_ctx = {}                   # (device index, f32 scale bits, zero, exact_div) -> context handle; lives as long as the process
-
-
-def lib() -> C.CDLL:
-    """Load libsesrq_image.so once and bind every declared symbol; raise loudly when it is absent."""
-    global _lib
-    if _lib is None:
-        if not os.path.isfile(LIB_PATH):
-            raise RuntimeError(f"sesrq.image: native library not found at {LIB_PATH}. Build it with "
-                               "`make -C sesr-pytorch-quantize_amd/csrc` (or __graft_entry__.build()); there is no fallback path.")
-        try:                      # one HIP runtime per process: torch's, mapped before the library (see _lib.lib())
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = handle
-    return _lib
-
-
-def last_error() -> str:
-    return (lib().sesrq_image_last_error() or b"").decode()
-
-
-def instances():
-    """{name: launches so far} of every kernel instantiation libsesrq_image.so can launch."""
-    l = lib()
-    return {l.sesrq_image_instance_name(i).decode(): int(l.sesrq_image_instance_launches(i))
-            for i in range(l.sesrq_image_instance_count())}
+_so = _lib.Library(LIB_PATH, SYMBOLS, "sesrq.image", "sesrq_image")
+lib, last_error, instances = _so.lib, _so.last_error, _so.instances
 
 
 def form_of(mflag: int) -> str:
@@ -144,19 +116,6 @@ def save_png(path: str, img_u8) -> None:
 
 
 # ------------------------------------------------------------------------------------------------------------------ device
-def _handle(device, scale_in, zero_in, exact_div):
-    import torch
-    key = (device.index, np.float32(scale_in).tobytes(), int(zero_in), int(exact_div))
-    h = _ctx.get(key)
-    if h is None:
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            if lib().sesrq_image_create(float(np.float32(scale_in)), int(zero_in), int(exact_div), C.byref(h)) != 0:
-                raise ValueError(last_error())
-        _ctx[key] = h
-    return h
-
-
 def _images(img, device):
     """(N, H, W, 3) view of a (N, H, W, 3) / (H, W, 3) uint8 tensor on `device` (None: any HIP device)."""
     import torch
@@ -176,7 +135,7 @@ def _images(img, device):
 def launch(device, scale_in, zero_in, exact_div, img, form, order, q0, x, stream):
     """Enqueue one decode of the (N, H, W, 3) contiguous uint8 `img` into caller-owned q0 / x (either may be None) on `stream`."""
     N, H, W, _ = img.shape
-    h = _handle(device, scale_in, zero_in, exact_div)
+    h = _so.context(device, scale_in, zero_in, exact_div)
     rc = lib().sesrq_image_decode(h, img.data_ptr(), _form(form), _order(order), q0.data_ptr() if q0 is not None else None,
                                   x.data_ptr() if x is not None else None, N, H, W, stream.cuda_stream)
     if rc != 0:
@@ -191,23 +150,13 @@ def decode(engine_or_bundle, img_u8, form, order: str = "rgb", want_q: bool = Tr
     formed, its exact_div); x is the reference's fp32 input frame (engine_or_bundle may be None when only x is asked for).  Enqueued
     on `stream` (default: current), not synchronised."""
     import torch
-    from .bundle import Bundle
     f = _form(form)
     _order(order)
     if not (want_q or want_f):
         raise ValueError("decode: ask for q0, x or both")
-    if engine_or_bundle is None:          # the fp32 frame alone: no input domain involved
-        if want_q:
-            raise ValueError("decode: q0 needs the net's input domain (an Engine or a Bundle)")
-        scale_in, zero_in, exact_div, dev = 1.0, 0, 0, None
-    else:
-        if isinstance(engine_or_bundle, Bundle):
-            b, exact_div, dev = engine_or_bundle, 0, None
-        else:
-            b, exact_div, dev = engine_or_bundle.bundle, engine_or_bundle.exact_div, engine_or_bundle.device
-        if b.in_channels != CHANNELS[f]:
-            raise ValueError(f"image form {form!r} gives {CHANNELS[f]} channel(s); this net takes {b.in_channels}")
-        scale_in, zero_in = b.scale[0], b.zero[0]
+    b, scale_in, zero_in, exact_div, dev = _lib.input_domain(engine_or_bundle, want_q, "decode")
+    if b is not None and b.in_channels != CHANNELS[f]:
+        raise ValueError(f"image form {form!r} gives {CHANNELS[f]} channel(s); this net takes {b.in_channels}")
     img = _images(img_u8, dev)
     dev = img.device
     N, H, W, _ = img.shape
@@ -216,14 +165,7 @@ def decode(engine_or_bundle, img_u8, form, order: str = "rgb", want_q: bool = Tr
         img = img.contiguous()
         q0 = torch.empty((N, Ch, H, W), dtype=torch.int8, device=dev) if want_q else None
         x = torch.empty((N, Ch, H, W), dtype=torch.float32, device=dev) if want_f else None
-        cur = torch.cuda.current_stream(dev)
-        st = cur if stream is None else stream
-        if st != cur:             # ordered behind the work that produced the image; the memory stays alive until it has run
-            st.wait_stream(cur)
-            for t in (img, q0, x):
-                if t is not None:
-                    t.record_stream(st)
-        launch(dev, scale_in, zero_in, exact_div, img, f, order, q0, x, st)
+        launch(dev, scale_in, zero_in, exact_div, img, f, order, q0, x, _lib.enter_stream(dev, stream, img, q0, x))
     return q0, x
 
 
@@ -267,12 +209,7 @@ def export(pred, order: str = "rgb", scale=None, zero=None, stream=None):
     with torch.cuda.device(dev):
         pred = pred.contiguous()
         out = torch.empty((N, H, W, Ch), dtype=torch.uint8, device=dev)
-        cur = torch.cuda.current_stream(dev)
-        st = cur if stream is None else stream
-        if st != cur:
-            st.wait_stream(cur)
-            for t in (pred, out):
-                t.record_stream(st)
+        st = _lib.enter_stream(dev, stream, pred, out)
         rc = lib().sesrq_image_export(pred.data_ptr(), dt, s, z, Ch, o, out.data_ptr(), N, H, W, st.cuda_stream)
     if rc != 0:
         raise ValueError(last_error())

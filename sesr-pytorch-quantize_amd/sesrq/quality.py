@@ -15,6 +15,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+from . import _lib
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "lib", "libsesrq_eval.so"))
 
@@ -40,36 +42,8 @@ SYMBOLS = {
     "sesrq_eval_last_error": (C.c_char_p, []),
 }
 
-_lib = None
-
-
-def lib() -> C.CDLL:
-    """Load libsesrq_eval.so once and bind every declared symbol; raise loudly when it is absent."""
-    global _lib
-    if _lib is None:
-        if not os.path.isfile(LIB_PATH):
-            raise RuntimeError(f"sesrq.quality: native library not found at {LIB_PATH}. Build it with "
-                               "`make -C sesr-pytorch-quantize_amd/csrc` (or __graft_entry__.build()); there is no fallback path.")
-        try:                      # one HIP runtime per process: torch's, mapped before the library (see _lib.lib())
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = handle
-    return _lib
-
-
-def last_error() -> str:
-    return (lib().sesrq_eval_last_error() or b"").decode()
-
-
-def kernels():
-    """{name: launches so far} of every kernel instantiation libsesrq_eval.so can launch."""
-    l = lib()
-    return {l.sesrq_eval_kernel_name(i).decode(): int(l.sesrq_eval_kernel_launches(i)) for i in range(l.sesrq_eval_kernel_count())}
+_so = _lib.Library(LIB_PATH, SYMBOLS, "sesrq.quality", "sesrq_eval", counters="kernel")
+lib, last_error, kernels = _so.lib, _so.last_error, _so.instances
 
 
 def form_of(mflag: int) -> int:
@@ -115,17 +89,33 @@ def score(pred, gt, mflag: int, scale=None, zero=None, stream=None):
         pred, gt = pred.contiguous(), gt.contiguous()
         out = torch.empty((N, 3), dtype=torch.float64, device=dev)
         ws = torch.empty(max(1, lib().sesrq_eval_workspace_bytes(N, Ch, H, W)), dtype=torch.uint8, device=dev)
-        cur = torch.cuda.current_stream(dev)
-        st = cur if stream is None else stream
-        if st != cur:             # ordered behind the work that produced the frames; the memory stays alive until it has run
-            st.wait_stream(cur)
-            for t in (pred, gt, out, ws):
-                t.record_stream(st)
+        st = _lib.enter_stream(dev, stream, pred, gt, out, ws)
         rc = lib().sesrq_eval(C.byref(d), pred.data_ptr(), gt.data_ptr(), N, Ch, H, W, out.data_ptr(), ws.data_ptr(), ws.numel(),
                               st.cuda_stream)
     if rc != 0:
         raise ValueError("sesrq_eval: " + last_error())
     return out
+
+
+def _evaluate(engine, mflag: int, pairs, step):
+    """The loop of evaluate, evaluate_raw and evaluate_image: per (input, gt) of `pairs`, step(input, gt, fp32) runs the forward and
+    returns (prediction, device fp32 gt).  MFLAG 6 scores the anchored fp32 output (fp32 True), every other MFLAG the int8 output
+    in the net's output domain.  One synchronisation at the end; a host float64 array (frames, 3) of (mse, psnr, ssim)."""
+    import torch
+    form = form_of(mflag)
+    if form == FORM_X2 and not getattr(engine, "anchor_add", False):
+        raise ValueError("MFLAG 6 is scored on the anchored output: create the engine with anchor_add=True")
+    b = engine.bundle
+    scale, zero = float(b.scale[b.L]), int(b.zero[b.L])
+    rows = []
+    for x, g in pairs:
+        pred, gt = step(x, g, form == FORM_X2)
+        rows.append(score(pred, gt, mflag) if form == FORM_X2 else score(pred, gt, mflag, scale=scale, zero=zero))
+    if not rows:
+        raise ValueError("no frames")
+    res = torch.cat(rows)
+    torch.cuda.synchronize(engine.device)
+    return res.cpu().numpy()
 
 
 def evaluate(engine, frames, gts, mflag: int):
@@ -136,29 +126,15 @@ def evaluate(engine, frames, gts, mflag: int):
     domain (bundle.scale[L], bundle.zero[L]).  MFLAG 6: the forward writes only the anchored float output; the engine must have
     been created with anchor_add=True.  Returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
     import torch
-    form = form_of(mflag)
-    if form == FORM_X2 and not getattr(engine, "anchor_add", False):
-        raise ValueError("MFLAG 6 is scored on the anchored output: create the engine with anchor_add=True")
-    b = engine.bundle
-    L = b.L
-    scale, zero = float(b.scale[L]), int(b.zero[L])
     dev = engine.device
-    rows = []
-    for x, g in zip(frames, gts):
+
+    def step(x, g, fp32):
         x = x if x.dim() == 4 else x.unsqueeze(0)
         g = g if g.dim() == 4 else g.unsqueeze(0)
         x, g = x.to(dev, non_blocking=True), g.to(dev, dtype=torch.float32, non_blocking=True)
-        if form == FORM_X2:
-            _, y = engine.forward(x, want_q=False, want_f=True)
-            rows.append(score(y, g, mflag))
-        else:
-            q, _ = engine.forward(x, want_q=True, want_f=False)
-            rows.append(score(q, g, mflag, scale=scale, zero=zero))
-    if not rows:
-        raise ValueError("no frames")
-    res = torch.cat(rows)
-    torch.cuda.synchronize(dev)
-    return res.cpu().numpy()
+        q, y = engine.forward(x, want_q=not fp32, want_f=fp32)
+        return (y if fp32 else q), g
+    return _evaluate(engine, mflag, zip(frames, gts), step)
 
 
 def evaluate_raw(engine, raws, gts_u16, mflag: int):
@@ -174,20 +150,13 @@ def evaluate_raw(engine, raws, gts_u16, mflag: int):
     from . import raw as rawmod
     if form_of(mflag) != FORM_RGB:
         raise ValueError(f"MFLAG {mflag}: raw RGGB frames feed the denoise / demosaic nets (MFLAG 3, 4)")
-    b = engine.bundle
-    scale, zero = float(b.scale[b.L]), int(b.zero[b.L])
     dev = engine.device
-    rows = []
-    for r, g in zip(raws, gts_u16):
+
+    def step(r, g, fp32):
         r = torch.from_numpy(np.ascontiguousarray(r)) if isinstance(r, np.ndarray) else r
-        r = r.to(dev, non_blocking=True)
-        q, _ = engine.forward_raw(r, want_q=True, want_f=False)
-        rows.append(score(q, rawmod.load_gt(g, dev), mflag, scale=scale, zero=zero))
-    if not rows:
-        raise ValueError("no frames")
-    res = torch.cat(rows)
-    torch.cuda.synchronize(dev)
-    return res.cpu().numpy()
+        q, _ = engine.forward_raw(r.to(dev, non_blocking=True), want_q=True, want_f=False)
+        return q, rawmod.load_gt(g, dev)
+    return _evaluate(engine, mflag, zip(raws, gts_u16), step)
 
 
 def evaluate_image(engine, lr_imgs, hr_imgs, mflag: int, order: str = "rgb"):
@@ -201,26 +170,14 @@ def evaluate_image(engine, lr_imgs, hr_imgs, mflag: int, order: str = "rgb"):
     import numpy as np
     import torch
     from . import image as imgmod
-    form = form_of(mflag)
+    form_of(mflag)
     imgmod.form_of(mflag)
-    if form == FORM_X2 and not getattr(engine, "anchor_add", False):
-        raise ValueError("MFLAG 6 is scored on the anchored output: create the engine with anchor_add=True")
-    b = engine.bundle
-    scale, zero = float(b.scale[b.L]), int(b.zero[b.L])
     dev = engine.device
-    rows = []
-    for lr, hr in zip(lr_imgs, hr_imgs):
+
+    def step(lr, hr, fp32):
         lr = torch.from_numpy(np.ascontiguousarray(lr)) if isinstance(lr, np.ndarray) else lr
         lr = lr.to(dev, non_blocking=True)
         g = imgmod.load_gt(hr, mflag, dev, order=order)
-        if form == FORM_X2:
-            _, y = engine.forward_image(lr, order=order, want_q=False, want_f=True)
-            rows.append(score(y, g, mflag))
-        else:
-            q, _ = engine.forward_image(lr, order=order, want_q=True, want_f=False)
-            rows.append(score(q, g, mflag, scale=scale, zero=zero))
-    if not rows:
-        raise ValueError("no frames")
-    res = torch.cat(rows)
-    torch.cuda.synchronize(dev)
-    return res.cpu().numpy()
+        q, y = engine.forward_image(lr, order=order, want_q=not fp32, want_f=fp32)
+        return (y if fp32 else q), g
+    return _evaluate(engine, mflag, zip(lr_imgs, hr_imgs), step)

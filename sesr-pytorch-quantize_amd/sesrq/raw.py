@@ -13,6 +13,8 @@ import os
 
 import numpy as np
 
+from . import _lib
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "lib", "libsesrq_raw.so"))
 
@@ -31,37 +33,8 @@ SYMBOLS = {
     "sesrq_raw_last_error": (C.c_char_p, []),
 }
 
-_lib = None
-_ctx = {}                   # (device index, f32 scale bits, zero, exact_div) -> context handle; lives as long as the process
-
-
-def lib() -> C.CDLL:
-    """Load libsesrq_raw.so once and bind every declared symbol; raise loudly when it is absent."""
-    global _lib
-    if _lib is None:
-        if not os.path.isfile(LIB_PATH):
-            raise RuntimeError(f"sesrq.raw: native library not found at {LIB_PATH}. Build it with "
-                               "`make -C sesr-pytorch-quantize_amd/csrc` (or __graft_entry__.build()); there is no fallback path.")
-        try:                      # one HIP runtime per process: torch's, mapped before the library (see _lib.lib())
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = handle
-    return _lib
-
-
-def last_error() -> str:
-    return (lib().sesrq_raw_last_error() or b"").decode()
-
-
-def instances():
-    """{name: launches so far} of every kernel instantiation libsesrq_raw.so can launch."""
-    l = lib()
-    return {l.sesrq_raw_instance_name(i).decode(): int(l.sesrq_raw_instance_launches(i)) for i in range(l.sesrq_raw_instance_count())}
+_so = _lib.Library(LIB_PATH, SYMBOLS, "sesrq.raw", "sesrq_raw")
+lib, last_error, instances = _so.lib, _so.last_error, _so.instances
 
 
 def table(scale_in: float, zero_in: int, exact_div: int = 0) -> np.ndarray:
@@ -125,19 +98,6 @@ def load_gt(array_u16, device=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------ device
-def _handle(device, scale_in, zero_in, exact_div):
-    import torch
-    key = (device.index, np.float32(scale_in).tobytes(), int(zero_in), int(exact_div))
-    h = _ctx.get(key)
-    if h is None:
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            if lib().sesrq_raw_create(float(np.float32(scale_in)), int(zero_in), int(exact_div), C.byref(h)) != 0:
-                raise ValueError(last_error())
-        _ctx[key] = h
-    return h
-
-
 def _frames(raw, device):
     """(N, H, W) view of a (N, 1, H, W) / (N, H, W) / (H, W) uint16 device tensor."""
     import torch
@@ -159,7 +119,7 @@ def _frames(raw, device):
 def launch(device, scale_in, zero_in, exact_div, raw, q0, spread, stream):
     """Enqueue one unpack of the (N, H, W) contiguous uint16 `raw` into caller-owned q0 / spread (either may be None) on `stream`."""
     N, H, W = raw.shape
-    h = _handle(device, scale_in, zero_in, exact_div)
+    h = _so.context(device, scale_in, zero_in, exact_div)
     rc = lib().sesrq_raw_unpack(h, raw.data_ptr(), q0.data_ptr() if q0 is not None else None,
                                 spread.data_ptr() if spread is not None else None, N, H, W, stream.cuda_stream)
     if rc != 0:
@@ -172,23 +132,13 @@ def unpack(engine_or_bundle, raw, want_q: bool = True, want_spread: bool = False
     q0 is in the input domain of the net (engine.bundle or the bundle itself: scale[0], zero[0]; an Engine also fixes how x / s0 is
     formed, its exact_div); spread is the reference's fp32 input frame (engine_or_bundle may be None when only spread is asked for).  Enqueued on `stream` (default: current), not synchronised."""
     import torch
-    from .bundle import Bundle
     if not (want_q or want_spread):
         raise ValueError("unpack: ask for q0, spread or both")
-    if engine_or_bundle is None:          # the fp32 frame alone: no input domain involved
-        if want_q:
-            raise ValueError("unpack: q0 needs the net's input domain (an Engine or a Bundle)")
-        scale_in, zero_in, exact_div = 1.0, 0, 0
+    b, scale_in, zero_in, exact_div, dev = _lib.input_domain(engine_or_bundle, want_q, "unpack")
+    if b is not None and b.in_channels != 3:
+        raise ValueError(f"a raw RGGB frame feeds 3-channel nets; this one takes {b.in_channels}")
+    if dev is None:
         dev = raw.device if isinstance(raw, torch.Tensor) else None
-    else:
-        if isinstance(engine_or_bundle, Bundle):
-            b, exact_div = engine_or_bundle, 0
-            dev = raw.device if isinstance(raw, torch.Tensor) else None
-        else:
-            b, exact_div, dev = engine_or_bundle.bundle, engine_or_bundle.exact_div, engine_or_bundle.device
-        if b.in_channels != 3:
-            raise ValueError(f"a raw RGGB frame feeds 3-channel nets; this one takes {b.in_channels}")
-        scale_in, zero_in = b.scale[0], b.zero[0]
     raw = _frames(raw, dev)
     if dev is None or dev.type != "cuda":
         raise ValueError("the raw frame must be on a HIP device")
@@ -197,12 +147,5 @@ def unpack(engine_or_bundle, raw, want_q: bool = True, want_spread: bool = False
         raw = raw.contiguous()
         q0 = torch.empty((N, 3, H, W), dtype=torch.int8, device=dev) if want_q else None
         sp = torch.empty((N, 3, H, W), dtype=torch.float32, device=dev) if want_spread else None
-        cur = torch.cuda.current_stream(dev)
-        st = cur if stream is None else stream
-        if st != cur:             # ordered behind the work that produced the frame; the memory stays alive until it has run
-            st.wait_stream(cur)
-            for t in (raw, q0, sp):
-                if t is not None:
-                    t.record_stream(st)
-        launch(dev, scale_in, zero_in, exact_div, raw, q0, sp, st)
+        launch(dev, scale_in, zero_in, exact_div, raw, q0, sp, _lib.enter_stream(dev, stream, raw, q0, sp))
     return q0, sp
