@@ -293,6 +293,54 @@ int sesrq_calib_fakequant(const float *in, float *out, size_t n, float scale, in
 /* (clamp_b(rint(x/scale + zero)) - zero) * scale at width quan_bits (2..8) */
 int sesrq_calib_fakequant_q(const float *in, float *out, size_t n, float scale, int zero, int quan_bits, void *stream);
 
+/* ---- device-resident calibration pass: no host round trip until the caller reads the slots back ---------------------
+ * The entry points above take each batch's (scale, zero) from the host, so a calibration forward waits on the host once per
+ * quantiser.  The ones below keep all of it on the device: per quantiser input K = 0..L one slot, which holds this batch's
+ * extrema, the running extrema, and the domain derived from this batch (what test.py's mode-0 quantisers compute on the host).
+ * Per quantiser and batch: sesrq_calib_observe_slot, then the conv / fake-quantiser that reads the slot.  They run on the same
+ * kernel instantiations as the host-driven entry points (the slot is a run-time operand).
+ * The results have the bits of the host-driven pass (sesrq/calibrate.py Calibrator.observe) at every width. */
+typedef struct sesrq_calib_slot {
+    uint32_t ord[2];           /* reduction scratch (order-preserving keys); back at {0xffffffff, 0} after every observe_slot */
+    float min, max;            /* this batch's extrema */
+    float run_min, run_max;    /* running extrema over every batch since the reset */
+    double scale;              /* this batch's scale, (max - min) / (2^b - 1) in fp64 */
+    int32_t zero;              /* this batch's zero, -2^(b-1) - rint(min / scale) */
+    int32_t degenerate;        /* sticky: some batch had max == min (the host pass asserts there) */
+    int32_t batches;           /* batches folded into run_min / run_max */
+    float scale32, zero32;     /* f32(scale), (float)zero: what the fake-quantiser divides by and adds */
+    float ss;                  /* f32(scale * sw) */
+    float acc_lo, acc_hi;      /* f32(((lo - zero) * scale) * sw) of the PE accumulator bounds */
+    float add_lo, add_hi;      /* the same for the PE adder bounds */
+    float qbias[16];           /* f32(clamp_bias(rint(f32(b) / ss)) * ss) per output channel */
+} sesrq_calib_slot;
+
+typedef struct sesrq_calib_domain_desc {
+    int32_t quan_bits;         /* 2..8 */
+    int32_t oc;                /* bias constants to derive, 0..16 (0: the quantiser in front of PixelShuffle / the output range) */
+    const float *bias;         /* device fp32 [oc], the conv's float bias; NULL when oc == 0 */
+    double sw;                 /* the conv's weight scale */
+    int32_t acc_bits, add_bits, bias_bits;   /* PE_ACC_BIT, PE_ADD_BIT, BIAS_BIT */
+} sesrq_calib_domain_desc;
+
+/* sizeof(sesrq_calib_slot), for bindings that mirror it */
+size_t sesrq_calib_slot_bytes(void);
+/* Host: n slots in their initial state (no batch seen, keys at {0xffffffff, 0}); the caller copies them to the device to reset a pass. */
+int sesrq_calib_slots_init(sesrq_calib_slot *host_slots, int n);
+/* One quantiser input of one batch: the min / max of a device fp32 tensor -> slot->min / max, folded into run_min / run_max (a
+ * strictly smaller min / larger max replaces the running one, as the host pass does), then this batch's domain: scale, zero and,
+ * with the conv's weight scale and bias (d->oc > 0), ss, the four PE bounds and the bias constants -- fp64 where the host pass
+ * computes in Python floats, fp32 where it uses numpy float32, in its order.  max == min raises slot->degenerate.  Two kernels on
+ * `stream` (the reduction, then one wave); nothing waits on the host. */
+int sesrq_calib_observe_slot(const float *x, size_t n, sesrq_calib_slot *slot, const sesrq_calib_domain_desc *d, void *stream);
+/* sesrq_calib_conv_q with in_scale, in_zero, ss, the bounds and qbias read from the slot (the desc's own are ignored) */
+int sesrq_calib_conv_slot(const sesrq_calib_conv_desc *d, const sesrq_calib_slot *slot, const float *in, const float *skip,
+                          float *out, int N, int H, int W, int quan_bits, void *stream);
+/* sesrq_calib_fakequant_q of an (N, C, H, W) tensor with the slot's f32(scale) and zero, written pixel-shuffled by r
+ * (out: (N, C / r^2, H r, W r); r = 1: unshuffled; C must be a multiple of r^2). */
+int sesrq_calib_fakequant_slot(const float *in, float *out, int N, int C, int H, int W, int r, const sesrq_calib_slot *slot,
+                               int quan_bits, void *stream);
+
 /* ---- host scalar code of the path (load time) -------------------------------------- */
 
 /* quan_layer_between_const (myQL/quan_func.py:495-515): r -> (M, n), truncating. */

@@ -1,4 +1,4 @@
-// libsesrq_eval.so: PSNR / SSIM of output frames on the device (include/sesrq_eval.h).  A library of its own: it links nothing of
+// libsesrq_eval.so: PSNR / SSIM of output frames on the device (include/sesrq_eval.h, include/sesrq_eval_anchor.h).  A library of its own: it links nothing of
 // libsesrq.so and registers nothing in its instance table.
 //
 // One pass over the bytes.  A frame is cut into tiles of BAND input columns x (RH + 6) input rows, one block per tile and one wave per
@@ -17,8 +17,10 @@
 
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include "sesrq_eval.h"
+#include "sesrq_eval_anchor.h"
 #include "sesrq_side.h"
 
 namespace sesrq_evalk {
@@ -48,6 +50,7 @@ struct TileArgs {
     const void *pred;
     const float *gt;
     double *part;        // [N][ntiles][C][2]
+    const float *anchor; // x2 form, fp32 pred only: the LR frame (N, C, H/2, W/2) whose nearest upsampling is added to pred, or NULL
     int H, W, nbx, nby, ntiles, vec;
     float scale;
     int zero;
@@ -87,6 +90,13 @@ __device__ inline void load_pred(const int8_t *row, int col, int W, bool vec, fl
     for (int k = 0; k < KC; ++k) v[k] = col + k < W ? clip01(__fmul_rn((float)(q[k] - zero), scale)) : 0.f;
 }
 
+// pred + up2(anchor) in fp32, then clipped: the bits of scoring a frame the anchor was added to beforehand (torch: pred + up2(x))
+__device__ inline void load_pred_anchored(const float *row, const float *arow, int col, int W, bool vec, float v[KC]) {
+    load4(row, col, W, vec, v);
+#pragma unroll
+    for (int k = 0; k < KC; ++k) v[k] = clip01(__fadd_rn(v[k], col + k < W ? arow[(col + k) >> 1] : 0.f));
+}
+
 // the 10 columns col-3 .. col+6 of one row: three from the lane on the left, four own, three from the lane on the right
 // (lanes 0 and 63 receive their own values; they reach only SSIM outputs outside the tile)
 __device__ inline void halo(const float own[KC], float out[KC + 2 * PAD]) {
@@ -123,6 +133,18 @@ __global__ __launch_bounds__(64 * 3) void eval_tile(TileArgs a) {
     // SESRQ_EVAL_X2: the squared luma error needs all three channels of a pixel; the channel-0 wave forms it (the other two waves
     // read the same rows in the same block, so those bytes come from cache)
     const bool luma = FORM == SESRQ_EVAL_X2 && c == 0;
+    // one row of channel cc of pred, clipped (anchored first when the launch carries an anchor)
+    auto pred_row = [&](int cc, int rr, float v[KC]) {
+        if constexpr (FORM == SESRQ_EVAL_X2 && std::is_same<T, float>::value) {
+            if (a.anchor) {
+                const int Wl = W >> 1;
+                const float *arow = a.anchor + ((size_t)n * C + cc) * (size_t)(H >> 1) * Wl + (size_t)(rr >> 1) * Wl;
+                load_pred_anchored(pred + cc * plane + (size_t)rr * W, arow, col, W, vec, v);
+                return;
+            }
+        }
+        load_pred(pred + cc * plane + (size_t)rr * W, col, W, vec, a.scale, a.zero, v);
+    };
 
     double S[KC][5];
 #pragma unroll
@@ -137,11 +159,11 @@ __global__ __launch_bounds__(64 * 3) void eval_tile(TileArgs a) {
         const bool emit = r >= o0 + PAD;                    // the window of output row r - 3 is complete
         const size_t off = c * plane + (size_t)r * W;
         float x[KC], y[KC], xo[KC] = {0.f, 0.f, 0.f, 0.f}, yo[KC] = {0.f, 0.f, 0.f, 0.f};
-        load_pred(pred + off, col, W, vec, a.scale, a.zero, x);
+        pred_row(c, r, x);
         load4(gt + off, col, W, vec, y);
         if (leave) {
             const size_t offo = off - (size_t)(2 * PAD + 1) * W;
-            load_pred(pred + offo, col, W, vec, a.scale, a.zero, xo);
+            pred_row(c, r - (2 * PAD + 1), xo);
             load4(gt + offo, col, W, vec, yo);
         }
         if (FORM != SESRQ_EVAL_X2 && own_row) {
@@ -159,7 +181,7 @@ __global__ __launch_bounds__(64 * 3) void eval_tile(TileArgs a) {
             for (int cc = 0; cc < 3; ++cc) {
                 const double wc = cc == 0 ? 65.481 : cc == 1 ? 128.553 : 24.966;
                 float xc[KC], yc[KC];
-                load_pred(pred + cc * plane + (size_t)r * W, col, W, vec, a.scale, a.zero, xc);
+                pred_row(cc, r, xc);
                 load4(gt + cc * plane + (size_t)r * W, col, W, vec, yc);
 #pragma unroll
                 for (int k = 0; k < KC; ++k) {
@@ -276,9 +298,8 @@ extern "C" size_t sesrq_eval_workspace_bytes(int N, int C, int H, int W) {
     return (size_t)N * geometry(H, W).ntiles * C * 2 * sizeof(double);
 }
 
-extern "C" int sesrq_eval(const sesrq_eval_desc *d, const void *pred, const float *gt, int N, int C, int H, int W, double *out,
-                          void *workspace, size_t workspace_bytes, void *stream) {
-    g_err[0] = 0;
+static int eval_launch(const sesrq_eval_desc *d, const void *pred, const float *anchor, const float *gt, int N, int C, int H, int W,
+                       double *out, void *workspace, size_t workspace_bytes, void *stream) {
     if (!d) return fail("sesrq_eval: desc is NULL");
     if (d->form < SESRQ_EVAL_RGB || d->form > SESRQ_EVAL_X2) return fail("sesrq_eval: unknown form %d", d->form);
     if (d->pred_dtype != SESRQ_EVAL_F32 && d->pred_dtype != SESRQ_EVAL_I8)
@@ -304,6 +325,7 @@ extern "C" int sesrq_eval(const sesrq_eval_desc *d, const void *pred, const floa
     a.pred = pred;
     a.gt = gt;
     a.part = static_cast<double *>(workspace);
+    a.anchor = anchor;
     a.H = H;
     a.W = W;
     a.nbx = g.nbx;
@@ -335,6 +357,24 @@ extern "C" int sesrq_eval(const sesrq_eval_desc *d, const void *pred, const floa
     if (e != hipSuccess) return fail("sesrq_eval: finish kernel launch: %s", hipGetErrorString(e));
     ++g_count.launches[K_FINISH];
     return 0;
+}
+
+extern "C" int sesrq_eval(const sesrq_eval_desc *d, const void *pred, const float *gt, int N, int C, int H, int W, double *out,
+                          void *workspace, size_t workspace_bytes, void *stream) {
+    g_err[0] = 0;
+    return eval_launch(d, pred, nullptr, gt, N, C, H, W, out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int sesrq_eval_anchored(const sesrq_eval_desc *d, const float *pred, const float *lr, const float *gt, int N, int C, int H,
+                                   int W, double *out, void *workspace, size_t workspace_bytes, void *stream) {
+    g_err[0] = 0;
+    if (!d) return fail("sesrq_eval_anchored: desc is NULL");
+    if (d->form != SESRQ_EVAL_X2 || d->pred_dtype != SESRQ_EVAL_F32)
+        return fail("sesrq_eval_anchored: the anchor is added to an fp32 prediction in the x2 form (form %d, pred_dtype %d)", d->form,
+                    d->pred_dtype);
+    if (!lr) return fail("sesrq_eval_anchored: NULL lr");
+    if (H % 2 || W % 2) return fail("sesrq_eval_anchored: frame %dx%d is not twice an LR frame", H, W);
+    return eval_launch(d, pred, lr, gt, N, C, H, W, out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sesrq_eval_kernel_count(void) { return g_count.count(); }

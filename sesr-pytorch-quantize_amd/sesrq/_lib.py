@@ -46,6 +46,19 @@ class CalibConvDesc(C.Structure):
                 ("acc_hi", C.c_float), ("add_lo", C.c_float), ("add_hi", C.c_float), ("relu", C.c_int32)]
 
 
+class CalibSlot(C.Structure):
+    """sesrq_calib_slot: one quantiser input's state in the device-resident calibration pass (include/sesrq.h)."""
+    _fields_ = [("ord", C.c_uint32 * 2), ("min", C.c_float), ("max", C.c_float), ("run_min", C.c_float), ("run_max", C.c_float),
+                ("scale", C.c_double), ("zero", C.c_int32), ("degenerate", C.c_int32), ("batches", C.c_int32),
+                ("scale32", C.c_float), ("zero32", C.c_float), ("ss", C.c_float), ("acc_lo", C.c_float), ("acc_hi", C.c_float),
+                ("add_lo", C.c_float), ("add_hi", C.c_float), ("qbias", C.c_float * MAX_CH)]
+
+
+class CalibDomainDesc(C.Structure):
+    _fields_ = [("quan_bits", C.c_int32), ("oc", C.c_int32), ("bias", C.c_void_p), ("sw", C.c_double), ("acc_bits", C.c_int32),
+                ("add_bits", C.c_int32), ("bias_bits", C.c_int32)]
+
+
 class FrameIO(C.Structure):
     _fields_ = [("inp", C.c_void_p), ("out_q", C.c_void_p), ("out_f", C.c_void_p)]
 
@@ -90,6 +103,13 @@ SYMBOLS = {
     "sesrq_calib_fakequant": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int, C.c_void_p]),
     "sesrq_calib_fakequant_q": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int, C.c_int, C.c_void_p]),
     "sesrq_calib_histogram": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    "sesrq_calib_slot_bytes": (C.c_size_t, []),
+    "sesrq_calib_slots_init": (C.c_int, [C.POINTER(CalibSlot), C.c_int]),
+    "sesrq_calib_observe_slot": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(CalibDomainDesc), C.c_void_p]),
+    "sesrq_calib_conv_slot": (C.c_int, [C.POINTER(CalibConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, C.c_void_p]),
+    "sesrq_calib_fakequant_slot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                             C.c_void_p]),
     "sesrq_requant_const": (C.c_int, [C.c_double, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "sesrq_quantize_weight": (C.c_int, [C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_int8),
                                         C.POINTER(C.c_double)]),

@@ -12,7 +12,15 @@ Entropy variant (`method="entropy"`; BASELINE's north star names KL-entropy acti
 has min/max -- no oracle, PARITY UNPINNED): after the min/max pass a second pass over the same frames accumulates a
 histogram of every quantiser input over its observed range (sesrq_calib_histogram), and `finalize()` replaces (min, max)
 by the clipping range that minimises the KL divergence between the observed distribution and its 256-level quantisation
-(`entropy_range`).  The output domain keeps the reference's rule (min := 0)."""
+(`entropy_range`).  The output domain keeps the reference's rule (min := 0).
+
+Device-resident pass (`enqueue`, `enqueue_raw`, `enqueue_image`): the same forward with no host round trip.  `observe` reads each
+quantiser's min/max back to the host to form the next conv's (scale, zero); here one device slot per quantiser input holds the batch's
+extrema, the running extrema and the domain derived from them (sesrq_calib_observe_slot), and the conv / fake-quantiser read it there
+(sesrq_calib_conv_slot / _fakequant_slot).  Nothing waits on the host until `finalize()` (or `sync()`) reads the slots back.  Bit for
+bit the results of `observe` on the same frames: per-batch (scale, zero), mode-0 output, running min/max, domains, bundle.  Frames
+come as fp32 (N, C, H, W), 12-bit RGGB raw frames (decoded on the device into the reference's fp32 input, sesrq.raw) or 8-bit images
+(sesrq.image).  min/max only: the entropy variant keeps the host pass."""
 from __future__ import annotations
 
 import ctypes as C
@@ -118,6 +126,23 @@ class Calibrator:
         self.hist: List[Optional[torch.Tensor]] = [None] * (self.L + 1)     # entropy variant: second-pass histograms
         self._hist_pass = False
         self.set_method(method, bins)
+        self.in_channels = int(self.wq[0].shape[1])
+        # device-resident pass: float biases, descriptors, one slot per quantiser input (uploaded here and by reset(): enqueueing never
+        # waits on the host), kept activation buffers per (N, H, W)
+        self._bias_dev = [torch.from_numpy(b).to(self.device) for b in self.biases_f]
+        self._conv_desc, self._dom_desc = [], []
+        for k in range(self.L):
+            oc, ic, ks, _ = self.wq[k].shape
+            self._conv_desc.append(_lib.CalibConvDesc(k=ks, ic=ic, oc=oc, w=self._wdev[k].data_ptr(), relu=int(k != self.L - 1)))
+            self._dom_desc.append(_lib.CalibDomainDesc(quan_bits=self.quan_bits, oc=oc, bias=self._bias_dev[k].data_ptr(), sw=self.sw[k],
+                                                       acc_bits=self.acc_bits, add_bits=self.add_bits, bias_bits=self.bias_bits))
+        self._dom_desc.append(_lib.CalibDomainDesc(quan_bits=self.quan_bits, oc=0, bias=None, sw=1.0, acc_bits=self.acc_bits,
+                                                   add_bits=self.add_bits, bias_bits=self.bias_bits))
+        self._slot_bytes = C.sizeof(_lib.CalibSlot)
+        self._slots = torch.empty((self.L + 1) * self._slot_bytes, dtype=torch.uint8, device=self.device)
+        self._buffers = {}
+        self.last_input: Optional[torch.Tensor] = None
+        self._reset_slots()
 
     def set_method(self, method: str, bins: int = 2048):
         """'minmax' = the reference's rule; 'entropy' = KL-minimising clipping ranges from a second (histogram) pass."""
@@ -136,6 +161,13 @@ class Calibrator:
         self.run_max = [None] * (self.L + 1)
         self.hist = [None] * (self.L + 1)
         self._hist_pass = False
+        self._reset_slots()
+
+    def _reset_slots(self):
+        init = (_lib.CalibSlot * (self.L + 1))()
+        _lib.check(_lib.lib().sesrq_calib_slots_init(init, self.L + 1))
+        self._slots.copy_(torch.frombuffer(bytearray(bytes(init)), dtype=torch.uint8))
+        self._dev_pass = False
 
     def begin_histogram_pass(self):
         """Entropy variant: call after the min/max pass; the following observe() calls (the same frames again) accumulate
@@ -171,6 +203,8 @@ class Calibrator:
         fake-quantised float output, pixel-shuffled)."""
         if x.dim() != 4 or x.dtype != torch.float32 or x.device != self.device:
             raise ValueError("Calibrator.observe: need a (N,C,H,W) float32 tensor on " + str(self.device))
+        if self._dev_pass:
+            raise RuntimeError("Calibrator.observe: this calibrator holds a device-resident pass (enqueue*); reset() first")
         lib = _lib.lib()
         st = torch.cuda.current_stream(self.device).cuda_stream
         N, _, H, W = x.shape
@@ -208,10 +242,123 @@ class Calibrator:
         self._observe(L, a)                                   # nets without PixelShuffle: range of the last conv's output (quan_func.py:460-479)
         return a
 
+
+    # ---- device-resident pass ----------------------------------------------------------------
+    def _check_device_pass(self, who: str):
+        if self.method != "minmax":
+            raise ValueError(f"Calibrator.{who}: the device-resident pass computes the reference's min/max ranges only; "
+                             "method='entropy' runs on the host pass (observe, begin_histogram_pass)")
+        if not self._dev_pass and any(v is not None for v in self.run_min):
+            raise RuntimeError(f"Calibrator.{who}: frames were observed on the host pass (observe); reset() first")
+
+    def _slot(self, k: int) -> int:
+        return self._slots.data_ptr() + k * self._slot_bytes
+
+    def _acts(self, N: int, H: int, W: int):
+        """The kept activation buffers of one (N, H, W): conv outputs 0 .. L-2, the last conv's output of a PixelShuffle net, and the
+        decoded input frame of raw / image input.  Only the most recent frame size is kept (a dataset of many sizes does not pile up
+        buffer sets); the caching allocator recycles the previous set only behind the work already queued on this stream."""
+        key = (N, H, W)
+        b = self._buffers.get(key)
+        if b is None:
+            shapes = [(N, self.wq[k].shape[0], H, W) for k in range(self.L - 1 if self.pixel_shuffle == 1 else self.L)]
+            b = {"acts": [torch.empty(sh, dtype=torch.float32, device=self.device) for sh in shapes],
+                 "input": torch.empty((N, self.in_channels, H, W), dtype=torch.float32, device=self.device)}
+            self._buffers = {key: b}
+        return b
+
+    def _forward_device(self, x: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
+        lib = _lib.lib()
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        N, _, H, W = x.shape
+        acts, L, r, qb = self._acts(N, H, W)["acts"], self.L, self.pixel_shuffle, self.quan_bits
+        oc = self.wq[L - 1].shape[0]
+        shape = (N, oc // (r * r), H * r, W * r)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"Calibrator: out must be a contiguous float32 {shape} tensor on {self.device}")
+        last = out if r == 1 else acts[L - 1]
+        a = x
+        self._dev_pass = True
+        for k in range(L):
+            _lib.check(lib.sesrq_calib_observe_slot(a.data_ptr(), a.numel(), self._slot(k), C.byref(self._dom_desc[k]), st))
+            dst = acts[k] if k < L - 1 else last
+            skip = acts[0] if k == L - 2 else None          # long skip: x_{L-1} = a_{L-2} + a_0 (float AddOp)
+            _lib.check(lib.sesrq_calib_conv_slot(C.byref(self._conv_desc[k]), self._slot(k), a.data_ptr(),
+                                                 skip.data_ptr() if skip is not None else None, dst.data_ptr(), N, H, W, qb, st))
+            a = dst
+        _lib.check(lib.sesrq_calib_observe_slot(a.data_ptr(), a.numel(), self._slot(L), C.byref(self._dom_desc[L]), st))
+        if r > 1:      # the quantiser in front of PixelShuffle, written shuffled (test.py:90-91)
+            _lib.check(lib.sesrq_calib_fakequant_slot(a.data_ptr(), out.data_ptr(), N, oc, H, W, r, self._slot(L), qb, st))
+        return out
+
+    def enqueue(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """observe() without a host round trip: x (N, Cin, H, W) float32 on the device -> the mode-0 output (a new tensor, or `out`),
+        enqueued on the current stream and not synchronised.  The ranges are read back by finalize() / sync().
+
+        One stream per calibrator: the slots and the kept activation buffers are shared by every frame and ordered only by the stream
+        the frames are enqueued on, so enqueue all of a pass's frames on one stream.  last_input is the fp32 frame the pass read
+        (for enqueue_raw / enqueue_image a kept buffer): valid until the next enqueue*."""
+        self._check_device_pass("enqueue")
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.dtype != torch.float32 or x.device != self.device:
+            raise ValueError("Calibrator.enqueue: need a (N,C,H,W) float32 tensor on " + str(self.device))
+        if x.shape[1] != self.in_channels or min(x.shape) < 1:
+            raise ValueError(f"Calibrator.enqueue: expected {self.in_channels} input channels and a non-empty frame, got {tuple(x.shape)}")
+        x = x.contiguous()
+        self.last_input = x
+        return self._forward_device(x, out)
+
+    def enqueue_raw(self, raw_u16: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """12-bit RGGB raw frames (N, 1, H, W) / (N, H, W) / (H, W) torch.uint16 on the device, unpacked on the device into the
+        reference's fp32 input (sesrq.raw, the spread frame: self_dataset.py TestDataset's inp) and calibrated as enqueue() does."""
+        from . import raw as rawmod
+        self._check_device_pass("enqueue_raw")
+        if self.in_channels != 3:
+            raise ValueError(f"Calibrator.enqueue_raw: a raw RGGB frame feeds 3-channel nets; this one takes {self.in_channels}")
+        raw = rawmod._frames(raw_u16, self.device).contiguous()
+        N, H, W = raw.shape
+        x = self._acts(N, H, W)["input"]
+        rawmod.launch(self.device, 1.0, 0, 0, raw, None, x, torch.cuda.current_stream(self.device))
+        self.last_input = x
+        return self._forward_device(x, out)
+
+    def enqueue_image(self, img_u8: torch.Tensor, order: str = "rgb", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """8-bit images (N, H, W, 3) / (H, W, 3) torch.uint8 on the device, in `order`, decoded on the device into the reference's fp32
+        input (sesrq.image: the float64 luma for a 1-channel net (MFLAG 5), RGB / 255 for a 3-channel one (MFLAG 6)) and calibrated
+        as enqueue() does."""
+        from . import image as imgmod
+        self._check_device_pass("enqueue_image")
+        form = imgmod.Y if self.in_channels == 1 else imgmod.RGB if self.in_channels == 3 else None
+        if form is None:
+            raise ValueError(f"Calibrator.enqueue_image: an 8-bit image feeds 1- or 3-channel nets; this one takes {self.in_channels}")
+        imgmod._order(order)
+        img = imgmod._images(img_u8, self.device).contiguous()
+        N, H, W, _ = img.shape
+        x = self._acts(N, H, W)["input"]
+        imgmod.launch(self.device, 1.0, 0, 0, img, form, order, None, x, torch.cuda.current_stream(self.device))
+        self.last_input = x
+        return self._forward_device(x, out)
+
+    def sync(self):
+        """Wait for the enqueued frames and read the slots back: run_min / run_max, last_scale / last_zero as observe() leaves them.
+        A batch whose quantiser input was constant (max == min, which observe() asserts against) raises here."""
+        if not self._dev_pass:
+            return
+        raw = bytes(self._slots.cpu().numpy().tobytes())
+        slots = (_lib.CalibSlot * (self.L + 1)).from_buffer_copy(raw)
+        for k, s in enumerate(slots):
+            if s.degenerate:
+                raise RuntimeError("Input tensor is all equal,{}".format(k))
+            if s.batches:
+                self.run_min[k], self.run_max[k] = float(s.run_min), float(s.run_max)
+                self.last_scale[k], self.last_zero[k] = float(s.scale), int(s.zero)
+
     # ---- results ------------------------------------------------------------------------------
     def finalize(self):
         """running (min, max) -> (scale[0..L], zero[0..L]) as test.py:185-217 (output domain: min := 0)."""
         from .bundle import calib_scale_zero
+        self.sync()
         if self.method == "entropy" and not self._hist_pass:
             raise RuntimeError("Calibrator.finalize: method='entropy' needs the histogram pass (begin_histogram_pass, observe again)")
         scale, zero = [], []

@@ -42,8 +42,29 @@ SYMBOLS = {
     "sesrq_eval_last_error": (C.c_char_p, []),
 }
 
+# what include/sesrq_eval_anchor.h declares (the same library)
+ANCHOR_SYMBOLS = {
+    "sesrq_eval_anchored": (C.c_int, [C.POINTER(EvalDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
 _so = _lib.Library(LIB_PATH, SYMBOLS, "sesrq.quality", "sesrq_eval", counters="kernel")
 lib, last_error, kernels = _so.lib, _so.last_error, _so.instances
+
+
+_anchor_bound = False
+
+
+def anchored_lib():
+    """The library with the entry points of include/sesrq_eval_anchor.h bound too (once)."""
+    global _anchor_bound
+    h = lib()
+    if not _anchor_bound:
+        for name, (res, args) in ANCHOR_SYMBOLS.items():
+            fn = getattr(h, name)
+            fn.restype, fn.argtypes = res, args
+        _anchor_bound = True
+    return h
 
 
 def form_of(mflag: int) -> int:
@@ -95,6 +116,109 @@ def score(pred, gt, mflag: int, scale=None, zero=None, stream=None):
     if rc != 0:
         raise ValueError("sesrq_eval: " + last_error())
     return out
+
+
+def score_anchored(pred, lr, gt, stream=None):
+    """MFLAG 6 scores of fl32(pred + up2(lr)) without forming that frame: pred (N, 3, 2H, 2W) float32 -- an output without the fused
+    anchor, such as the calibration pass's mode-0 output --, lr (N, 3, H, W) float32, the net's input, gt (N, 3, 2H, 2W) float32, all on
+    one device.  The bits of score(pred + up2(lr), gt, 6).  A device float64 (N, 3) tensor of (mse, psnr, ssim), not synchronised."""
+    import torch
+    for name, t in (("pred", pred), ("lr", lr), ("gt", gt)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.dtype != torch.float32:
+            raise ValueError(f"{name} must be a (N, C, H, W) float32 tensor")
+    if tuple(pred.shape) != tuple(gt.shape):
+        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have one shape")
+    N, Ch, H, W = pred.shape
+    if tuple(lr.shape) != (N, Ch, H // 2, W // 2) or H % 2 or W % 2:
+        raise ValueError(f"lr {tuple(lr.shape)} is not the half-size input of a {tuple(pred.shape)} prediction")
+    if Ch != CHANNELS[FORM_X2]:
+        raise ValueError(f"MFLAG 6 scores 3-channel frames, got {Ch}")
+    if H < 7 or W < 7:
+        raise ValueError(f"frame {H}x{W} is smaller than the 7x7 SSIM window")
+    if pred.device.type != "cuda" or gt.device != pred.device or lr.device != pred.device:
+        raise ValueError("pred, lr and gt must be on one HIP device")
+    d = EvalDesc(form=FORM_X2, pred_dtype=PRED_F32, pred_scale=0.0, pred_zero=0)
+    dev = pred.device
+    with torch.cuda.device(dev):
+        pred, lr, gt = pred.contiguous(), lr.contiguous(), gt.contiguous()
+        out = torch.empty((N, 3), dtype=torch.float64, device=dev)
+        ws = torch.empty(max(1, lib().sesrq_eval_workspace_bytes(N, Ch, H, W)), dtype=torch.uint8, device=dev)
+        st = _lib.enter_stream(dev, stream, pred, lr, gt, out, ws)
+        rc = anchored_lib().sesrq_eval_anchored(C.byref(d), pred.data_ptr(), lr.data_ptr(), gt.data_ptr(), N, Ch, H, W, out.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), st.cuda_stream)
+    if rc != 0:
+        raise ValueError("sesrq_eval_anchored: " + last_error())
+    return out
+
+
+KINDS = ("f32", "raw", "image")
+
+
+def check_calibration_input(calibrator, mflag: int, kind: str):
+    """The refusals of evaluate_calibration, before any device work: the input kind must fit the MFLAG (raw frames: 3 / 4, images:
+    5 / 6) and the net's input channels, and the calibrator must be on the min/max rule (the device pass has no entropy variant)."""
+    form_of(mflag)
+    if kind not in KINDS:
+        raise ValueError(f"kind {kind!r}: one of {KINDS}")
+    cin = calibrator.in_channels
+    if kind == "raw":
+        if FORMS[mflag] != FORM_RGB:
+            raise ValueError(f"MFLAG {mflag}: raw RGGB frames feed the denoise / demosaic nets (MFLAG 3, 4)")
+        if cin != 3:
+            raise ValueError(f"a raw RGGB frame feeds 3-channel nets; this one takes {cin}")
+    if kind == "image":
+        from . import image as imgmod
+        f = imgmod.form_of(mflag)
+        if imgmod.CHANNELS[imgmod._form(f)] != cin:
+            raise ValueError(f"MFLAG {mflag} images give {imgmod.CHANNELS[imgmod._form(f)]} channel(s); this net takes {cin}")
+    if calibrator.method != "minmax":
+        raise ValueError("evaluate_calibration: the device-resident calibration pass computes the reference's min/max ranges only; "
+                         "method='entropy' runs on the host pass (Calibrator.observe)")
+
+
+def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32", order: str = "rgb"):
+    """The reference's calibration loop (test.py:141-183) on the device: per frame the mode-0 forward (Calibrator.enqueue /
+    enqueue_raw / enqueue_image, which also accumulates the running ranges) and the metrics of its output in the form the MFLAG uses
+    -- MFLAG 6 the anchored output fl32(gfake + up2(inps)), formed inside the scoring kernel (score_anchored).  One synchronisation at
+    the end; calibrator.finalize() then gives the activation domains.
+
+    kind "f32": frames (1, Cin, H, W) float32 (or one (N, Cin, H, W) tensor, taken frame by frame); "raw": (1, 1, H, W) / (1, H, W) /
+    (H, W) uint16 RGGB frames; "image": (H, W, 3) / (1, H, W, 3) uint8 LR images in `order`.  gts, numpy or torch, by dtype: float32
+    frames of the output shape, uint16 RGB frames (3, H, W) / (1, 3, H, W) (sesrq.raw.load_gt), or uint8 HR images in `order`
+    (sesrq.image.load_gt).
+    Returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
+    import numpy as np
+    import torch
+    check_calibration_input(calibrator, mflag, kind)
+    dev = calibrator.device
+    form = FORMS[mflag]
+
+    def host(t):
+        return torch.from_numpy(np.ascontiguousarray(t)) if isinstance(t, np.ndarray) else t
+    rows = []
+    for x, g in zip(frames, gts):
+        x = host(x).to(dev, non_blocking=True)
+        if kind == "f32":
+            y = calibrator.enqueue(x.float() if x.dim() == 4 else x.float().unsqueeze(0))
+        elif kind == "raw":
+            y = calibrator.enqueue_raw(x)
+        else:
+            y = calibrator.enqueue_image(x, order=order)
+        g = host(g)
+        if g.dtype == torch.uint8:           # an 8-bit HR image: the reference's gt formed on the device
+            from . import image as imgmod
+            g = imgmod.load_gt(g, mflag, dev, order=order)
+        elif g.dtype == torch.uint16:        # a 16-bit RGB frame: / 4095, clamped (self_dataset.py:235-243)
+            from . import raw as rawmod
+            g = rawmod.load_gt(g, dev)
+        else:
+            g = (g if g.dim() == 4 else g.unsqueeze(0)).to(dev, dtype=torch.float32, non_blocking=True)
+        rows.append(score_anchored(y, calibrator.last_input, g) if form == FORM_X2 else score(y, g, mflag))
+    if not rows:
+        raise ValueError("no frames")
+    res = torch.cat(rows)
+    torch.cuda.synchronize(dev)
+    return res.cpu().numpy()
 
 
 def _evaluate(engine, mflag: int, pairs, step):

@@ -1,11 +1,18 @@
 """Calibration entry point -- the counterpart of the reference's ``test.py`` (:79-113 graph build with
 qmode = 0, :141-183 loop over calibration frames, :185-217 scale/zero derivation).  The reference's
-dataset is private; frames come from ``--frames`` (.npy / .pt, (N,C,H,W) float32, one batch per N).
+dataset is private; frames come from ``--frames`` (.npy / .pt, (N,C,H,W) float32, one batch per N), or from ``--input``: what
+sim.py reads -- 12-bit RGGB raw frames (``*.raw``, MFLAG 3 / 4), 8-bit images (``.png``, or uint8 ``.npy`` with ``--image``; MFLAG
+5 / 6) or fp32 ``.npy`` / ``.pt`` frames -- decoded on the device and calibrated frame by frame without a host round trip
+(Calibrator.enqueue*).  With ``--gt`` every frame's mode-0 output is scored as the reference's loop scores it (each frame's PSNR, then
+the mean line) before the domains are printed.
 
     python test.py --mflag 5 --params tests/golden/sesr_x4.params.npz --frames tests/golden/rand_SR_Input_80x960.npy \\
                    --save-bundle x4.bundle.npz
+    python test.py --mflag 3 --params tests/golden/nrdm_3.params.npz --input a_132_128.raw b_132_128.raw --gt gt16.npy
+    python test.py --mflag 6 --params ... --input lr0.png lr1.png --gt hr0.png hr1.png
 """
 import argparse
+import types
 
 import numpy as np
 import torch
@@ -44,7 +51,15 @@ def main(argv=None):
     ap.add_argument("--mflag", type=int, default=define.MFLAG)
     ap.add_argument("--ckpt")
     ap.add_argument("--params")
-    ap.add_argument("--frames", required=True)
+    ap.add_argument("--frames", help="(N,C,H,W) float32 frames, .npy / .pt: calibrated on the host-driven pass (without --gt)")
+    ap.add_argument("--input", nargs="+", help="dataset frames as sim.py reads them: *.raw 12-bit RGGB frames <name>_<rows>_<cols>.raw "
+                                              "(MFLAG 3 / 4), 8-bit images .png (or uint8 .npy with --image; MFLAG 5 / 6), or fp32 "
+                                              ".npy / .pt (N,C,H,W); calibrated on the device-resident pass")
+    ap.add_argument("--gt", nargs="+", help="ground truths, one per --input file (or one batch .npy / .pt): score every frame's mode-0 "
+                                           "output and print its PSNR and the mean line, as the reference's test.py does.  fp32 or "
+                                           "uint16 RGB (N,3,H,W) .npy / .pt, or 8-bit HR images (.png, uint8 .npy with --image)")
+    ap.add_argument("--image", action="store_true", help="--input / --gt .npy files are uint8 (H, W, 3) or (N, H, W, 3) images")
+    ap.add_argument("--order", choices=("rgb", "bgr"), default="rgb", help="byte order of uint8 .npy images (PNGs are read as RGB)")
     ap.add_argument("--method", default="minmax", choices=["minmax", "entropy"],
                     help="minmax: the reference's running min/max (default); entropy: KL-minimising clipping ranges from a second "
                          "pass over the frames (no reference counterpart, parity unpinned)")
@@ -59,7 +74,11 @@ def main(argv=None):
     define.check()
     print("QUAN_BIT:", define.QUAN_BIT)
     STORE.clear()
+    if (args.frames is None) == (args.input is None):
+        raise SystemExit("test.py: give the frames with --frames or with --input (one of them)")
     model = splice_calibration(sim.float_model(args.mflag, args.ckpt, args.params))
+    if args.input is not None or args.gt is not None:
+        return dataset_pass(args, model)
     frames = torch.load(args.frames, weights_only=True, map_location="cpu") if args.frames.endswith(".pt") else torch.from_numpy(np.load(args.frames))
     if not torch.cuda.is_available():
         raise SystemExit("test.py: calibration runs on a HIP device (no CPU fallback)")
@@ -78,6 +97,10 @@ def main(argv=None):
         STORE.set_activation_domains(scale, zero)
     else:
         scale, zero = finish_calibration(STORE, cal.L)
+    return report(args, model, scale, zero)
+
+
+def report(args, model, scale, zero):
     for s, z in zip(scale, zero):
         print("scale:", s)
         print("zero:", z)
@@ -88,6 +111,99 @@ def main(argv=None):
     if args.save_bundle:
         model._sesrq_cal.bundle(name=f"mflag{args.mflag}").save(args.save_bundle)
     return scale, zero
+
+
+def _frames_of(a, image):
+    """A file's frames: one frame, or a batch of them along a leading axis.  Images (H, W, 3) uint8; other frames (1, C, H, W)."""
+    a = a.numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    if a.ndim == 3:
+        a = a[None]
+    if a.ndim != 4:
+        raise SystemExit(f"test.py: expected a frame or a batch of frames, got shape {a.shape}")
+    return [a[i] if image else a[i:i + 1] for i in range(a.shape[0])]
+
+
+def load_inputs(paths, image_flag):
+    """(kind, [host frame]) of the --input files: "raw" (H, W) uint16, "image" (H, W, 3) uint8, "f32" (1, C, H, W) float32."""
+    kinds = {"raw" if p.endswith(".raw") else "image" if sim.is_image(p, image_flag) else "f32" for p in paths}
+    if len(kinds) != 1:
+        raise SystemExit("test.py: --input files must all be of one kind (raw frames, images or fp32 frames)")
+    kind = kinds.pop()
+    frames = []
+    for p in paths:
+        if kind == "raw":
+            from sesrq import raw
+            frames.append(raw.load_raw(p))
+        elif kind == "image":
+            from sesrq import image
+            frames += _frames_of(image.load_image(p), True)
+        else:
+            frames += [f.astype(np.float32) for f in _frames_of(sim.load_frames(p), False)]
+    return kind, frames
+
+
+def load_gts(paths, kind, image_flag):
+    gts = []
+    for p in paths:
+        if sim.is_image(p, image_flag):
+            from sesrq import image
+            gts += _frames_of(image.load_image(p), True)
+        else:
+            gts += _frames_of(sim.load_frames(p), False)
+    return gts
+
+
+def dataset_pass(args, model):
+    """--input / --gt: the reference's calibration loop (test.py:141-183) on the device-resident pass: every frame decoded and
+    calibrated on the device, scored with --gt; one synchronisation at the end."""
+    from sesrq import quality
+    from sesrq.lowering import lower_calibration
+    if args.method != "minmax":
+        raise SystemExit("test.py: --input / --gt run the device-resident pass, which computes the reference's min/max ranges only; "
+                         "use --frames for --method entropy")
+    if args.frames is not None:
+        kind, frames = "f32", [f.astype(np.float32) for f in _frames_of(sim.load_frames(args.frames), False)]
+    else:
+        kind, frames = load_inputs(args.input, args.image)
+    cin = next(m for m in model.modules() if isinstance(m, torch.nn.Conv2d)).in_channels
+    try:       # the refusals of forward_raw / forward_image, before any device work
+        quality.check_calibration_input(types.SimpleNamespace(in_channels=cin, method=args.method), args.mflag, kind)
+    except ValueError as e:
+        raise SystemExit(f"test.py: {e}") from None
+    gts = load_gts(args.gt, kind, args.image) if args.gt else None
+    if gts is not None and len(gts) != len(frames):
+        raise SystemExit(f"test.py: {len(frames)} input frames, {len(gts)} ground truths")
+    if not torch.cuda.is_available():
+        raise SystemExit("test.py: calibration runs on a HIP device (no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    cal = lower_calibration(model, dev)
+    model.__dict__["_sesrq_cal"] = cal
+    if gts is not None:
+        res = quality.evaluate_calibration(cal, frames, gts, args.mflag, kind=kind, order=args.order)
+        totalpsnr = totalssim = 0.0
+        for _, psnr, ssim in res:
+            print(float(psnr))
+            totalpsnr += float(psnr)
+            totalssim += float(ssim)
+        print(quality.TASKS[args.mflag] + ' mean psnr is: ', totalpsnr / len(res), ' ssim is: ', totalssim / len(res))
+    else:
+        for f in frames:
+            t = torch.from_numpy(np.ascontiguousarray(f)).to(dev)
+            if kind == "raw":
+                cal.enqueue_raw(t)
+            elif kind == "image":
+                cal.enqueue_image(t, order=args.order)
+            else:
+                cal.enqueue(t)
+    cal.sync()
+    for k in range(cal.L + 1):
+        STORE[f"input/input.{k}.min_val"] = cal.run_min[k]
+        STORE[f"input/input.{k}.max_val"] = cal.run_max[k]
+        STORE[f"input/input.{k}.scale"] = cal.last_scale[k]
+        STORE[f"input/input.{k}.zero"] = cal.last_zero[k]
+    print("calibrate start")
+    scale, zero = finish_calibration(STORE, cal.L)
+    return report(args, model, scale, zero)
 
 
 if __name__ == "__main__":
