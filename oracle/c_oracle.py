@@ -19,7 +19,7 @@ def _load():
     global _lib
     if _lib is None:
         _lib = C.CDLL(os.path.join(_HERE, "libsesrq_oracle.so"))
-        _lib.orc_forward.restype = C.c_int
+        _lib.orc_forward_q.restype = C.c_int
         _lib.orc_max_threads.restype = C.c_int
     return _lib
 
@@ -29,7 +29,7 @@ def max_threads():
 
 
 def forward(net, x, threads=0, keep=False, want_f=True):
-    """net: oracle.sesrq_oracle.Net ; x (N,Cin,H,W) fp32 -> dict(q_out, y[, input{k}, pe_out{k}, pe_add{k}])."""
+    """net: oracle.sesrq_oracle.Net (at its width net.quan_bits) ; x (N,Cin,H,W) fp32 -> dict(q_out, y[, input{k}, pe_out{k}, pe_add{k}])."""
     lib = _load()
     x = np.ascontiguousarray(x, np.float32)
     N, cin, H, W = x.shape
@@ -59,11 +59,12 @@ def forward(net, x, threads=0, keep=False, want_f=True):
             res[f"pe_out{k}"] = np.empty((4, oc, H, W), np.int32)
             res[f"pe_add{k}"] = np.empty((1, oc, H, W), np.int32)
             sq[k], sp[k], sa[k] = res[f"input{k}"].ctypes.data, res[f"pe_out{k}"].ctypes.data, res[f"pe_add{k}"].ctypes.data
-    rc = lib.orc_forward(C.c_int(L), layers, zero, C.c_float(np.float32(net.scale[0])), C.c_float(np.float32(net.scale[L])),
+    rc = lib.orc_forward_q(C.c_int(L), layers, zero, C.c_float(np.float32(net.scale[0])), C.c_float(np.float32(net.scale[L])),
                          C.c_uint32(net.M_res), C.c_uint32(net.n_res), C.c_int(r), C.c_int(net.acc_bits),
                          C.c_int(net.add_bits), C.c_void_p(x.ctypes.data), C.c_int(N), C.c_int(H), C.c_int(W),
                          C.c_void_p(out_q.ctypes.data), C.c_void_p(out_f.ctypes.data if want_f else None),
-                         C.c_int(threads), sq if keep else None, sp if keep else None, sa if keep else None)
+                         C.c_int(threads), sq if keep else None, sp if keep else None, sa if keep else None,
+                         C.c_int(int(getattr(net, "quan_bits", 8))))
     if rc != 0:
         raise RuntimeError(f"orc_forward failed: {rc}")
     res["q_out"] = out_q

@@ -1,6 +1,6 @@
 """CPU ORACLE (numpy) -- TEST INFRASTRUCTURE ONLY, never on the product path.
 
-An independent restatement of the reference's INT8 integer-inference arithmetic
+An independent restatement of the reference's integer-inference arithmetic at QUAN_BIT = 8 (INT8) and 2..7
 (gui-yupeng/sesr-pytorch-quantize, `sim.py` path).  Only tests/, __graft_entry__.smoke()
 and bench.py's cpu_baseline leg may import this file.  The shipped package
 (sesr-pytorch-quantize_amd/) must never import it and fails loudly when its HIP library
@@ -111,10 +111,19 @@ class Net:
     acc_bits: int = 18
     add_bits: int = 20
     name: str = ""
+    quan_bits: int = 8        # define.py QUAN_BIT: weights and activations live in [qlo, qhi] = [-2^(b-1), 2^(b-1) - 1]
 
     @property
     def L(self):
         return len(self.layers)
+
+    @property
+    def qlo(self):
+        return -(1 << (self.quan_bits - 1))
+
+    @property
+    def qhi(self):
+        return (1 << (self.quan_bits - 1)) - 1
 
 
 def quantize_weight_per_channel(w: np.ndarray, width: int = 8):
@@ -125,15 +134,17 @@ def quantize_weight_per_channel(w: np.ndarray, width: int = 8):
 
 
 def derive_net(Wf: List[np.ndarray], bf: List[np.ndarray], scale: List[float], zero: List[int],
-               pixel_shuffle: int, name: str = "", per_channel: bool = False) -> Net:
+               pixel_shuffle: int, name: str = "", per_channel: bool = False, quan_bit: int = 8) -> Net:
     """float collapsed convs + calibrated (scale, zero) -> integer parameter bundle.
 
     Role rules restate myQL/quan_func.py:523-609: layer 0 and layer L-2 requantise into
     domain 1 (the long-residual domain), layer L-1 into domain L, the others into k+1;
     residual multiplier = s_1 / s_{L-1} (quan_func.py:256-260).  For L == 5 this is exactly
     the reference; for other depths (nrdm_6) it is the positional generalisation (parity
-    unpinned, no reference implementation exists).
+    unpinned, no reference implementation exists).  quan_bit: the width b the weights are
+    quantised at (quan_func.py:58-71 with width = b); the per-channel variant is 8-bit only.
     """
+    assert not (per_channel and quan_bit != 8), "per-channel requant constants are 8-bit only"
     L = len(Wf)
     layers = []
     for k in range(L):
@@ -145,12 +156,12 @@ def derive_net(Wf: List[np.ndarray], bf: List[np.ndarray], scale: List[float], z
             layers.append(Layer(wq=wq, add_const=ac, M=Mn[0][0], n=Mn[0][1], relu=(k != L - 1),
                                 M_oc=np.array([m for m, _ in Mn], np.int64), n_oc=np.array([n_ for _, n_ in Mn], np.int64)))
             continue
-        wq, sw = quantize_weight(Wf[k])
+        wq, sw = quantize_weight(Wf[k], quan_bit)
         M, n = qconst(scale[k] / scale[nxt] * sw)
         layers.append(Layer(wq=wq, add_const=add_const(bf[k], wq, scale[k], zero[k], sw), M=M, n=n, relu=(k != L - 1)))
     M_res, n_res = qconst(scale[1] / scale[L - 1])
     return Net(layers=layers, scale=list(scale), zero=list(zero), M_res=M_res, n_res=n_res,
-               pixel_shuffle=pixel_shuffle, name=name)
+               pixel_shuffle=pixel_shuffle, name=name, quan_bits=quan_bit)
 
 
 def net_from_fixture(fx) -> Net:
@@ -161,7 +172,7 @@ def net_from_fixture(fx) -> Net:
                     M=meta["M"][k], n=meta["n"][k], relu=(k != L - 1)) for k in range(L)]
     ps = {5: 4, 6: 2, 3: 1}[meta["mflag"]]
     return Net(layers=layers, scale=meta["scale"], zero=meta["zero"], M_res=meta["M_res"], n_res=meta["n_res"],
-               pixel_shuffle=ps, name=meta["case"])
+               pixel_shuffle=ps, name=meta["case"], quan_bits=int(meta.get("quan_bits", 8)))
 
 
 # --------------------------------------------------------------------------- forward
@@ -169,20 +180,22 @@ def _sat(x, bits):
     return np.clip(x, -(2 ** (bits - 1)), 2 ** (bits - 1) - 1)
 
 
-def quantize_input(x: np.ndarray, s0: float, z0: int, reciprocal: bool = False) -> np.ndarray:
-    """q0 = clamp8(rint(x / f32(s0) + f32(z0)))   -- myQL/quan_func.py:222-225 (true fp32 division).
+def quantize_input(x: np.ndarray, s0: float, z0: int, reciprocal: bool = False, quan_bits: int = 8) -> np.ndarray:
+    """q0 = clamp_b(rint(x / f32(s0) + f32(z0)))   -- myQL/quan_func.py:218-225 (true fp32 division), clamp_b = [-2^(b-1), 2^(b-1) - 1].
     reciprocal=True: x * f32(1 / f32(s0)) instead of the quotient -- how torch evaluates tensor / scalar on a GPU, where
     the reference's scripts run; no fixture pins it (the goldens come from a CPU run)."""
     x = np.asarray(x, F32)
-    with np.errstate(over="ignore"):          # huge x / s0 -> inf -> clamps to +-127 like in the reference
+    with np.errstate(over="ignore"):          # huge x / s0 -> inf -> clamps to the range ends like in the reference
         t = x * (F32(1) / F32(s0)) if reciprocal else x / F32(s0)
-    return np.clip(np.rint(t + F32(z0)), -128, 127).astype(np.int8)
+    return _qb(t + F32(z0), quan_bits).astype(np.int8)
 
 
 def conv_pe(q: np.ndarray, lay: Layer, z_in: int, pe: int, acc_bits: int, add_bits: int, return_raw: bool = False):
     """One layer's integer accumulate.  q: (N,IC,H,W) int8 -> (pe_out (N,pe,OC,H,W), acc (N,OC,H,W)) int64.
 
     pe_out[p] = clamp_acc( sum_{ic = p mod pe, taps} W*q )   with the image padded by zc = max(z_in,-128)
+    (the literal -128 at every width: quan_func.py:290 tests the zero point against it, while :249-252 scale the residual
+    offsets with the width -- the pad value is not clamped to [-2^(b-1), 2^(b-1) - 1] at b < 8)
     acc       = clamp_add( sum_p pe_out[p] ) + add_const
     Restates myQL/quan_func.py:298-318 (channel split), the zero-padded nn.Conv2d on (q - zc),
     :338-356 (add back zc*sum(W_pe)), :370 (18-bit clamp after the complete PE sum), :380-386,
@@ -224,8 +237,9 @@ def requant(acc: np.ndarray, M, n) -> np.ndarray:
     return (acc.astype(F32) * F32(M)) * F32(2.0 ** (-n))
 
 
-def _q8(v):
-    return np.clip(np.rint(v), -128, 127)
+def _qb(v, quan_bits: int = 8):
+    """clamp_b(rint(v)): the activation quantiser's round and clamp at width b (quan_func.py:201-202,218-225,280)."""
+    return np.clip(np.rint(v), -(1 << (quan_bits - 1)), (1 << (quan_bits - 1)) - 1)
 
 
 def pixel_shuffle(a: np.ndarray, r: int) -> np.ndarray:
@@ -238,13 +252,18 @@ def pixel_shuffle(a: np.ndarray, r: int) -> np.ndarray:
 
 
 def forward(net: Net, x: np.ndarray, keep: bool = False) -> Dict[str, np.ndarray]:
-    """Full integer forward.  x: (N, Cin, H, W) fp32.  Returns q_out (int8, pixel-shuffled),
+    """Full integer forward.  x: (N, Cin, H, W) fp32, or int8 = q0 itself (input.0.pt, inside the width's range).  Returns q_out (int8, pixel-shuffled),
     y (fp32 dequantised, pixel-shuffled) and, with keep=True, every stage the reference dumps
     (input{k}, pe_out{k}, pe_add{k}, shortcut, input4_special) for N == 1 comparisons.
     """
     L = net.L
+    b = net.quan_bits
     st: Dict[str, np.ndarray] = {}
-    q = quantize_input(x, net.scale[0], net.zero[0])
+    if np.asarray(x).dtype == np.int8:
+        q = np.asarray(x)
+        assert q.min() >= net.qlo and q.max() <= net.qhi, "q0 outside the width's range"
+    else:
+        q = quantize_input(x, net.scale[0], net.zero[0], quan_bits=b)
     short = None
     for k, lay in enumerate(net.layers):
         if keep:
@@ -259,7 +278,7 @@ def forward(net: Net, x: np.ndarray, keep: bool = False) -> Dict[str, np.ndarray
             t = np.maximum(t, F32(0))
         if k == L - 1:
             # quan_func.py:584-594: requantise into the output domain, then dequantise for software tests
-            qo = _q8(t + F32(net.zero[L])).astype(np.int8)
+            qo = _qb(t + F32(net.zero[L]), b).astype(np.int8)
             y = (qo.astype(F32) - F32(net.zero[L])) * F32(net.scale[L])
             if keep:
                 st[f"input{L}"] = qo
@@ -272,29 +291,34 @@ def forward(net: Net, x: np.ndarray, keep: bool = False) -> Dict[str, np.ndarray
                 st["shortcut"] = short.astype(F32)
         if k == L - 2:
             # long residual merged in the integer domain at the input of the last conv
-            # quan_func.py:249-270: both operands re-quantised with offset -128, +256, requant
-            rc = _q8(short - F32(128))
-            ic = _q8(t - F32(128))
+            # quan_func.py:249-270: both operands re-quantised with offset -2^(b-1), + 2^b, requant
+            half, span = F32(1 << (b - 1)), F32(1 << b)
+            rc = _qb(short - half, b)
+            ic = _qb(t - half, b)
             if keep:
                 st["input4_special"] = ic.astype(np.int8)
-            u = rc + ic + F32(256)
+            u = rc + ic + span
             v = (u * F32(net.M_res)) * F32(2.0 ** (-net.n_res))
-            q = _q8(v + F32(net.zero[k + 1])).astype(np.int8)
+            q = _qb(v + F32(net.zero[k + 1]), b).astype(np.int8)
         else:
-            q = _q8(t + F32(net.zero[k + 1])).astype(np.int8)      # quan_func.py:275-280
+            q = _qb(t + F32(net.zero[k + 1]), b).astype(np.int8)      # quan_func.py:275-280
     return st
 
 
 # --------------------------------------------------------------------------- synthetic nets
-def synth_net(kind: str, seed: int = 0, n_blocks: int = 3, hard: bool = False) -> Net:
+def synth_net(kind: str, seed: int = 0, n_blocks: int = 3, hard: bool = False, quan_bits: int = 8) -> Net:
     """Deterministic random integer bundle of a reference topology (no checkpoint needed).
 
     kind: 'sesr_x4' (1->16, PS4), 'sesr_x2' (3->12, PS2), 'nrdm' (3->3).  `hard` draws wide
-    weights / odd zero points so that the saturation and z<-128 branches fire.
+    weights / odd zero points so that the saturation and z<-128 branches fire.  quan_bits = b < 8:
+    weights in the b-bit range and every requant multiplier sized on a probe frame so that the
+    activations reach both ends of [-2^(b-1), 2^(b-1) - 1] (_synth_narrow).
     """
     rng = np.random.default_rng(seed)
     cin, cout, ps = {"sesr_x4": (1, 16, 4), "sesr_x2": (3, 12, 2), "nrdm": (3, 3, 1)}[kind]
     shapes = [(16, cin, 5)] + [(16, 16, 3)] * n_blocks + [(cout, 16, 5)]
+    if quan_bits != 8:
+        return _synth_narrow(kind, seed, rng, cin, ps, shapes, hard, quan_bits)
     L = len(shapes)
     layers = []
     for k, (oc, ic, ks) in enumerate(shapes):
@@ -319,3 +343,62 @@ def synth_net(kind: str, seed: int = 0, n_blocks: int = 3, hard: bool = False) -
     M_res, n_res = qconst(float(rng.uniform(0.2, 0.9)))
     return Net(layers=layers, scale=scale, zero=zero, M_res=M_res, n_res=n_res, pixel_shuffle=ps,
                name=f"synth_{kind}_{seed}{'_hard' if hard else ''}")
+
+
+def _synth_narrow(kind, seed, rng, cin, ps, shapes, hard, b) -> Net:
+    """synth_net at width b < 8.  plain: normal weights, every zero point at -2^(b-1).  hard: weights at the two extremes of the range,
+    each output channel leaning to one of them; zero points anywhere in [-170, 2^(b-1) - 1], the last conv's input domain below -128
+    (its border pixels then read the pad value -128 under 5 x 5 taps of one sign: the 18-bit PE clamp fires from b = 6 on)."""
+    assert 2 <= b < 8
+    qlo, qhi = -(1 << (b - 1)), (1 << (b - 1)) - 1
+    L = len(shapes)
+    if hard:
+        zero = [int(z) for z in rng.integers(-170, qhi + 1, L + 1)]
+        zero[L - 1] = int(rng.integers(-170, -128))
+    else:
+        zero = [qlo] * (L + 1)
+    scale = [float(s) for s in rng.uniform(0.003, 0.04, L + 1)]
+    scale[0] = 1.0 / (255.0 if hard else (1 << b) - 1)
+    wts, acs = [], []
+    for oc, ic, ks in shapes:
+        fan = ic * ks * ks
+        if hard:
+            lean = rng.choice(np.array([0.05, 0.95]), size=oc)[:, None, None, None]
+            w = np.where(rng.random((oc, ic, ks, ks)) < lean, qlo, qhi)
+            w = np.where(rng.random(w.shape) < 0.15, rng.integers(qlo, qhi + 1, w.shape), w)
+        else:
+            w = np.clip(np.rint(rng.standard_normal((oc, ic, ks, ks)) * max(0.7, 14.0 * 2.0 ** (b - 8))), qlo, qhi)
+            w[rng.integers(oc), rng.integers(ic), ks // 2, ks // 2] = qhi
+        a = max(8, fan << (2 * b - 4))                         # of the order of the accumulator: the constant shifts, never dominates
+        wts.append(w.astype(np.int8))
+        acs.append(np.clip(rng.integers(-2 * a if hard else -a, 2 * a if hard else a, oc), -32768, 32767).astype(np.int32))
+    # requant multipliers from a probe frame, layer by layer: the 90th percentile of the positive accumulators lands 30 % above the
+    # value that reaches qhi in the next domain (ReLU zeros and the clamp reach qlo)
+    x = rng.random((1, cin, 12, 12), dtype=np.float32)
+    net = Net(layers=[], scale=scale, zero=zero, M_res=1, n_res=0, pixel_shuffle=ps, quan_bits=b,
+              name=f"synth_{kind}_{seed}{'_hard' if hard else ''}_q{b}")
+
+    def mult(v, span):
+        v = np.asarray(v, np.float64)
+        v = v[v > 0]
+        return qconst(1.3 * span / (float(np.percentile(v, 90)) if v.size else 1.0))
+
+    q = quantize_input(x, scale[0], zero[0], quan_bits=b)
+    short = None
+    for k in range(L):
+        lay = Layer(wq=wts[k], add_const=acs[k], M=1, n=0, relu=(k != L - 1))
+        _, acc = conv_pe(q, lay, zero[k], net.pe, net.acc_bits, net.add_bits)
+        nxt = L if k == L - 1 else (1 if k in (0, L - 2) else k + 1)
+        lay.M, lay.n = mult(acc, (1 << b) if k == L - 2 else qhi - zero[nxt] + 1)
+        net.layers.append(lay)
+        t = requant(acc, lay.M, lay.n)
+        if lay.relu:
+            t = np.maximum(t, F32(0))
+        if k == 0:
+            short = t
+        if k == L - 2:
+            u = _qb(short - F32(1 << (b - 1)), b) + _qb(t - F32(1 << (b - 1)), b) + F32(1 << b)
+            net.M_res, net.n_res = mult(u, qhi - zero[L - 1] + 1)
+            t = (u * F32(net.M_res)) * F32(2.0 ** (-net.n_res))
+        q = _qb(t + F32(zero[nxt]), b).astype(np.int8)
+    return net

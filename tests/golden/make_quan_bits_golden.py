@@ -14,6 +14,9 @@ Per (case, b), under tests/golden/quan_bits/:
                           80 x 960 frame's q_out (input.5.pt, after PixelShuffle) and y
   <case>.q<b>.zeros.npz   the same crop with zero[1] != -2^(b-1) (layer 0 then writes a separate residual operand) and zero[L] moved
 
+Widths: b = 3, 4, 6 and 7 for sesr_x4, nrdm_3 and sesr_x2_rand, b = 2 and 5 for nrdm_3; the reference's own calibration runs at every
+one of these (case, b) pairs.
+
 Usage:  python tests/golden/make_quan_bits_golden.py                  # every case (one process each)
         python tests/golden/make_quan_bits_golden.py --case sesr_x4 --bits 4
 """
@@ -32,7 +35,8 @@ sys.path.insert(0, HERE)
 from make_golden import CASES, CROP_H, CROP_W, REF, sha  # noqa: E402
 
 OUT = os.path.join(HERE, "quan_bits")
-RUNS = [("sesr_x4", 4), ("sesr_x4", 6), ("nrdm_3", 4), ("nrdm_3", 2), ("nrdm_3", 6), ("sesr_x2_rand", 4), ("sesr_x2_rand", 6)]
+RUNS = [("sesr_x4", 4), ("sesr_x4", 6), ("nrdm_3", 4), ("nrdm_3", 2), ("nrdm_3", 6), ("sesr_x2_rand", 4), ("sesr_x2_rand", 6),
+        ("sesr_x4", 3), ("sesr_x4", 7), ("nrdm_3", 3), ("nrdm_3", 5), ("nrdm_3", 7), ("sesr_x2_rand", 3), ("sesr_x2_rand", 7)]
 
 
 def run_case(name: str, b: int) -> None:

@@ -16,7 +16,7 @@ def bundle_from_oracle(net: O.Net) -> Bundle:
                                       n_oc=getattr(l, 'n_oc', None)) for l in net.layers],
                   scale=list(net.scale), zero=list(net.zero), M_res=net.M_res, n_res=net.n_res,
                   pixel_shuffle=net.pixel_shuffle, pe_num=net.pe, pe_acc_bits=net.acc_bits, pe_add_bits=net.add_bits,
-                  name=net.name)
+                  name=net.name, quan_bits=getattr(net, "quan_bits", 8))
 
 
 def fixture_case(path):
