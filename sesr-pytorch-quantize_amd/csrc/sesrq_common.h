@@ -242,6 +242,8 @@ struct LayerPlan {
     long long worst_pe = 0, worst_sum = 0;
     int risky_mask = 0;      // PEs (bit p) whose 18-bit clamp can fire for some output channel
     int risky_oc = 0;        // output channels (bit o) with such a PE sum
+    bool hybrid = false;     // exactly one PE can saturate, at the 18 / 20-bit clamps: the MFMA kernels may run its merged chain + that PE's
+    int risky_reg = 4;       // hybrid first layer: the accumulator register holding every channel that can saturate (0..3), or 4 = any
 };
 
 void set_error(const std::string &msg);

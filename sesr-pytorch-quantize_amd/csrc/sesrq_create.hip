@@ -380,9 +380,14 @@ int sesrq_create_q(const sesrq_net_desc *d, const sesrq_options *opts, int quan_
         for (int o = 0; o < l.oc; ++o) a.add_const[o] = l.add_const[o];
         lp.engine_dot4 = std::string(lp.general ? "dot4-general" : "dot4-merged") + (l.M_oc ? "-perchannel" : "") +
                          (narrow ? "-q" + std::to_string(quan_bits) : "");
+        // exactly one risky PE (its image is packed above) at the reference's 18 / 20-bit clamps, which the hybrid kernels hold as literals
+        lp.hybrid = lp.d_afrag_others && d->pe_acc_bits == 18 && d->pe_add_bits == 20;
+        // hidden-layer rows: channel o sits in register o >> 2 of lane group o & 3.  If every channel that can saturate lives in
+        // ONE register, the hybrid first layer clamps that register only (risky_reg), else all four (4)
+        for (int i = 0; i < 4; ++i)
+            if (lp.risky_oc && (lp.risky_oc & ~(0xf << (4 * i))) == 0) lp.risky_reg = i;
         static const char *kn[] = {"", "mfma-h3", "mfma-h5", "mfma-f5"};
-        const bool hyb = lp.general && __builtin_popcount(lp.risky_mask) == 1 && d->pe_acc_bits == 18 && d->pe_add_bits == 20;
-        lp.engine_mfma = lp.mfma_kind == MFMA_NONE ? lp.engine_dot4 : std::string(kn[lp.mfma_kind]) + (hyb ? "-hybrid" : (lp.general ? "-general" : "-merged"));
+        lp.engine_mfma = lp.mfma_kind == MFMA_NONE ? lp.engine_dot4 : std::string(kn[lp.mfma_kind]) + (lp.hybrid ? "-hybrid" : (lp.general ? "-general" : "-merged"));
         if (lp.d_afrag_pesplit) lp.engine_mfma = std::string("mfma-h5p-") + (lp.general ? "general" : "merged");
         lp.engine = (net->engine == SESRQ_ENGINE_DOT4) ? lp.engine_dot4 : lp.engine_mfma;
     }

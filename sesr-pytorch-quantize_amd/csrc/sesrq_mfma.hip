@@ -31,8 +31,7 @@
 //   * rint + float->int8 is one add of 1.5*2^23 (round-to-nearest-even into the low mantissa
 //     bits) followed by a byte pick; mul / fma / magic-add run as packed v_pk_*_f32.
 #include <algorithm>
-#include <map>
-#include <mutex>
+#include <type_traits>
 
 #include "sesrq_mfma_common.h"
 
@@ -919,7 +918,7 @@ constexpr int F5_SH = F5_TH + 4;
 constexpr int F5_SWP = MTW + 8;         // staged pixel columns (2 halo + 64 + 2 halo + over-read)
 constexpr int F5_PITCH = F5_SH + 2;     // LDS column pitch in dwords (>= rows, = 2 mod 4)
 static_assert(F5_PITCH % 4 == 2 && 3 * F5_PITCH + F5_SH < 256, "column pitch: bank rule / ds_read2_b32 offset range");
-// RR (HYBS): the accumulator register whose rows can saturate (sesrq_api.hip: risky_reg), 4 = clamp all four
+// RR (HYBS): the accumulator register whose rows can saturate (LayerPlan::risky_reg, sesrq_create), 4 = clamp all four
 template <int MODE, int SRC, bool RC, int NCH, int RR = 4>
 __device__ __forceinline__ void mfma_f5_body(const ConvArgs &a, int4 *buf0, int4 *buf1) {
     constexpr bool GENERAL = mode_general(MODE);
@@ -1060,25 +1059,15 @@ extern "C" int sesrq_debug_fetch_stamps(void *host, size_t bytes) {
 #endif
 // Persistent walk geometry: one round of workgroups that exactly fits the chip.  The number of
 // co-resident workgroups per CU comes from the occupancy API for THIS kernel (registers / LDS differ a
-// lot between the merged and general variants); a strip's row tiles are then cut into the largest
+// lot between the merged and general variants), asked once per instantiation; a strip's row tiles are then cut into the largest
 // number of equal vertical runs that still fits.
 template <auto KERN>
 static void launch(ConvArgs a, hipStream_t st, int tile_h = MTH) {
-    const auto kern = KERN;
-    static std::mutex mu;
-    static std::map<const void *, int> occ;          // per kernel (all instantiations share this function type)
+    static const int blocks_per_cu = [] {
+        int b = 0;
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, KERN, 256, 0) == hipSuccess && b >= 1 ? b : 2;
+    }();
     const int num_cu = device_cu_count();
-    int blocks_per_cu;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = occ.find((const void *)kern);
-        if (it == occ.end()) {
-            int b = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, kern, 256, 0) != hipSuccess || b < 1) b = 2;
-            it = occ.emplace((const void *)kern, b).first;
-        }
-        blocks_per_cu = it->second;
-    }
     const int strips = (a.W + MTW - 1) / MTW, row_tiles = (a.H + tile_h - 1) / tile_h;
     long long k = (a.wg_budget > 0 ? (long long)a.wg_budget : (long long)blocks_per_cu * num_cu) / ((long long)strips * a.N);
     k = std::max(1LL, std::min<long long>(k, row_tiles));
@@ -1090,39 +1079,121 @@ static void launch(ConvArgs a, hipStream_t st, int tile_h = MTH) {
     launch_kernel<KERN>(grid, dim3(256), 0, st, a);
 }
 
-// hybrid first layer.  3 input channels: always the sparse MFMA (sesrq_create packs the 2:4 images for every 3-channel layer with exactly
-// one risky PE -- PE 3 holds no channel), by the register that needs the clamp; other channel counts: the dense hybrid kernel.
-template <int SRC, bool RC, int NCH>
-static int launch_f5_hybrid(const ConvArgs &a, hipStream_t st) {
-    if constexpr (NCH == 3) {
-        if (!a.afrag_sp) { set_error("mfma: hybrid 3-channel first layer without its sparse weight image"); return 1; }
-        switch (a.risky_reg) {
-            case 0: launch<mfma_f5_kernel_w4<HYBS, SRC, RC, 3, 0>>(a, st, F5_TH); break;
-            case 1: launch<mfma_f5_kernel_w4<HYBS, SRC, RC, 3, 1>>(a, st, F5_TH); break;
-            case 2: launch<mfma_f5_kernel_w4<HYBS, SRC, RC, 3, 2>>(a, st, F5_TH); break;
-            case 3: launch<mfma_f5_kernel_w4<HYBS, SRC, RC, 3, 3>>(a, st, F5_TH); break;
-            default: launch<mfma_f5_kernel_w4<HYBS, SRC, RC, 3, 4>>(a, st, F5_TH); break;
-        }
-    } else {
-        launch<mfma_f5_kernel_w4<HYB, SRC, RC, NCH>>(a, st, F5_TH);
+// ---- Kernel selection: select_mfma names the instance a launch runs as plain template-argument values; dispatch_mfma maps them onto the
+// instances the library builds, which the *_built predicates state -- the only combinations it instantiates (and so registers).
+enum Family { FAM_H3, FAM_H5, FAM_H5P, FAM_F5, FAM_F5_W4 };      // mfma_h3 / _h5 / _h5p / _f5 / _f5_w4 kernels
+struct Pick {
+    int fam = FAM_H3, mode = MERGED, epi = EPI_MID;
+    int src = SRC_F32, rc = 0, nch = 4, rr = 4;      // first layer: input form, writes the separate residual tensor, channels, HYBS register
+    int fast = 0, nv = 4, outf = 0;                  // last layer's store form (LastStore); other layers keep these defaults
+};
+
+constexpr bool h3_built(int m, int e) { return m != HYBS && e != EPI_LAST; }                 // no 3x3 output layer; HYBS: first layer only
+constexpr bool h5p_built(int m) { return m == MERGED || m == GEN_STD || m == GEN_ANY; }      // no taps; the hybrid needs no chain of its own
+constexpr bool h5_built(int m, int e, int fast, int nv, int outf) {
+    const int run = fast % 10, fma = fast / 10;
+    if (m == HYBS) return false;                                      // a first-layer form
+    if (e != EPI_LAST) return fast == 0 && nv == 4 && outf == 0;      // the store forms are the output layer's
+    if (m == GEN_TAP) return fast == 0 && outf == 0;                  // the tap kernels: the general store
+    if (fma && m == GEN_ANY) return false;                            // the one-fma requant needs biased sums
+    if (nv == 3 && run == 4) return false;                            // 3 rows: byte runs for the x2 pair map only
+    if (outf == 1) return run != 0;                                   // the fp32-only store rides on the byte-run forms
+    if (outf == 2) return run != 0 && nv == 3;                        // ... with the anchor add: the pair map only
+    return true;
+}
+// the tap kernels: one channel count (4) for all; merged and hybrid: the 4-waves form; the sparse hybrid: 3 channels, by risky register
+constexpr bool f5_built(int m, int nch) { return m == GEN_STD || m == GEN_ANY || (m == GEN_TAP && nch == 4); }
+constexpr bool f5_w4_built(int m, int nch, int rr) { return m == HYBS ? nch == 3 : rr == 4 && (m == MERGED || (m == HYB && nch != 3)); }
+
+// Which kernel a launch runs.  general / one_pe / tap: forward_impl's per-call decisions (per-PE sums; the one-risky-PE hybrid applies;
+// PE taps).  Returns 1 (set_error) where no MFMA kernel fits.
+static int select_mfma(const LayerPlan &lp, const ConvArgs &a, int src, int epi, bool general, bool one_pe, bool tap, Pick &p) {
+    p = Pick{};
+    p.epi = epi;
+    // the clamp bounds as literals (GEN_STD, HYB) for the reference's 18 / 20-bit widths, as arguments (GEN_ANY) for any other
+    const bool std_bits = a.acc_lo == -131072 && a.acc_hi == 131071 && a.add_lo == -524288 && a.add_hi == 524287;
+    p.mode = tap ? GEN_TAP : !general ? MERGED : !std_bits ? GEN_ANY : one_pe ? HYB : GEN_STD;
+    const bool pesplit = lp.d_afrag_pesplit && a.afrag == lp.d_afrag_pesplit;
+    if (tap && pesplit) { set_error("mfma: the pe-split last-layer kernel has no PE taps"); return 1; }
+    switch (lp.mfma_kind) {
+        case MFMA_H3:
+            if (epi == EPI_LAST) { set_error("mfma: 3x3 last layer not supported"); return 1; }
+            p.fam = FAM_H3;
+            return 0;
+        case MFMA_F5:
+            // merged and hybrid: 4 waves per SIMD (mfma_f5_kernel_w4); the per-PE forms take the registers they ask for
+            p.fam = (p.mode == MERGED || p.mode == HYB) ? FAM_F5_W4 : FAM_F5;
+            p.src = (src == SRC_F32 || src == SRC_I8D) ? src : SRC_I8;
+            p.rc = a.rc_out != nullptr;
+            p.nch = (a.ic == 1 || a.ic == 3) && !tap ? a.ic : 4;      // 2 or 4 channels, and every tap kernel: the 4-channel form
+            if (p.mode == HYB && p.nch == 3) {      // 3 channels: always the sparse MFMA (sesrq_create packs its image), by the register to clamp
+                if (!a.afrag_sp) { set_error("mfma: hybrid 3-channel first layer without its sparse weight image"); return 1; }
+                p.mode = HYBS;
+                p.rr = lp.risky_reg;
+            }
+            return 0;
+        case MFMA_H5:
+            p.fam = FAM_H5;
+            if (epi != EPI_LAST) return 0;
+            if (pesplit) {      // OC <= 4: its one chain already yields the four clamped PE sums, so the hybrid runs the GEN_STD kernel
+                p.fam = FAM_H5P;
+                if (p.mode == HYB) p.mode = GEN_STD;
+                return 0;
+            }
+            p.nv = last_nv(a.oc);      // real rows per lane group (must match pack_mfma_frags)
+            if (tap) return 0;
+            {   // FAST = the width of the PixelShuffle byte runs (the x2 pair map; 16 rows at x2 / x4) + 10 x the one-fma requant form;
+                // OUTF = the fp32 frame alone (1), with the x2 anchor add (2: the pair map of a 16-channel layer only)
+                const bool pair = last_pairmap(a.oc, a.ps);
+                const int run = pair ? 2 : (p.nv == 4 && (a.ps == 2 || a.ps == 4)) ? a.ps : 0;
+                if (a.out_q && !a.out_f) p.fast = run;
+                else if (!a.out_q && a.out_f && !a.anchor) { p.fast = run; p.outf = run ? 1 : 0; }
+                else if (!a.out_q && a.out_f && pair && a.ic == 16) { p.fast = run; p.outf = 2; }
+                // the output requant as one fma (ConvArgs::direct: proven for this layer's (M, n)) into zero point -128, from biased sums
+                // (GEN_ANY sums carry no bias); an anchored net's int8-only store keeps the two-step requant, its fp32 store does not
+                if (p.fast && p.mode != GEN_ANY && a.z_out == -128.f && (!a.anchor || p.outf == 2)) p.fast += 10 * a.direct;
+            }
+            return 0;
+        default: set_error("mfma: layer shape not supported by the MFMA engine"); return 1;
     }
-    return 0;
 }
 
-#define SESRQ_BY_MODE(KERN, ...)                                                         \
-    do {                                                                                 \
-        if (mode == MERGED) launch<KERN<MERGED, __VA_ARGS__>>(a, st);                    \
-        else if (mode == GEN_STD) launch<KERN<GEN_STD, __VA_ARGS__>>(a, st);             \
-        else if (mode == HYB) launch<KERN<HYB, __VA_ARGS__>>(a, st);                     \
-        else launch<KERN<GEN_ANY, __VA_ARGS__>>(a, st);                                  \
-    } while (0)
-// the one-fma last-layer flavours exist for the biased modes only (GEN_ANY sums carry no bias: it keeps the general store)
-#define SESRQ_BY_MODE_B(KERN, ...)                                                       \
-    do {                                                                                 \
-        if (mode == MERGED) launch<KERN<MERGED, __VA_ARGS__>>(a, st);                    \
-        else if (mode == GEN_STD) launch<KERN<GEN_STD, __VA_ARGS__>>(a, st);             \
-        else launch<KERN<HYB, __VA_ARGS__>>(a, st);                                      \
-    } while (0)
+// pick(f, Of<V...>{}, v, ...) calls f(std::integral_constant<int, V>...) with, per list, the member equal to its run-time value; false if
+// a value is in no list or f returns false (no such instance)
+template <int... V> struct Of {};
+template <int V, class F> static auto bind(F &f) { return [&f](auto... c) { return f(std::integral_constant<int, V>{}, c...); }; }
+template <class F> static bool pick(F &&f) { return f(); }
+template <class F, int... V, class... R> static bool pick(F &&f, Of<V...>, int v, R... r) { return ((v == V && pick(bind<V>(f), r...)) || ...); }
+
+static bool dispatch_mfma(const Pick &p, const ConvArgs &a, hipStream_t st) {
+    using Modes = Of<MERGED, GEN_STD, GEN_ANY, HYB, GEN_TAP, HYBS>;
+    using Epis = Of<EPI_MID, EPI_PRERES, EPI_LAST>;
+    using Srcs = Of<SRC_F32, SRC_I8, SRC_I8D>;
+    using Nchs = Of<1, 3, 4>;
+    switch (p.fam) {
+        case FAM_H3:
+            return pick([&](auto M, auto E) {
+                if constexpr (h3_built(M, E)) return launch<mfma_h3_kernel<M, E>>(a, st), true; else return false;
+            }, Modes{}, p.mode, Epis{}, p.epi);
+        case FAM_H5:
+            return pick([&](auto M, auto E, auto F, auto V, auto O) {
+                if constexpr (h5_built(M, E, F, V, O)) return launch<mfma_h5_kernel<M, E, F, V, O>>(a, st), true; else return false;
+            }, Modes{}, p.mode, Epis{}, p.epi, Of<0, 2, 4, 12, 14, 22, 24>{}, p.fast, Of<3, 4>{}, p.nv, Of<0, 1, 2>{}, p.outf);
+        case FAM_H5P:
+            return pick([&](auto M) {
+                if constexpr (h5p_built(M)) return launch<mfma_h5p_kernel<M>>(a, st), true; else return false;
+            }, Modes{}, p.mode);
+        case FAM_F5:
+            return pick([&](auto M, auto S, auto R, auto C) {
+                if constexpr (f5_built(M, C)) return launch<mfma_f5_kernel<M, S, R == 1, C>>(a, st, F5_TH), true; else return false;
+            }, Modes{}, p.mode, Srcs{}, p.src, Of<0, 1>{}, p.rc, Nchs{}, p.nch);
+        case FAM_F5_W4:
+            return pick([&](auto M, auto S, auto R, auto C, auto RR) {
+                if constexpr (f5_w4_built(M, C, RR)) return launch<mfma_f5_kernel_w4<M, S, R == 1, C, RR>>(a, st, F5_TH), true; else return false;
+            }, Modes{}, p.mode, Srcs{}, p.src, Of<0, 1>{}, p.rc, Nchs{}, p.nch, Of<0, 1, 2, 3, 4>{}, p.rr);
+    }
+    return false;
+}
 
 int launch_mfma(const LayerPlan &lp, const ConvArgs &a_in, int src, int epi, bool general, hipStream_t st, bool one_risky_pe, bool tap) {
     ConvArgs a = a_in;
@@ -1131,91 +1202,9 @@ int launch_mfma(const LayerPlan &lp, const ConvArgs &a_in, int src, int epi, boo
     if (epi == (getenv("SESRQ_STAMP_EPI") ? atoi(getenv("SESRQ_STAMP_EPI")) : 0) && lp.mfma_kind == (getenv("SESRQ_STAMP_KIND") ? atoi(getenv("SESRQ_STAMP_KIND")) : MFMA_H3)) a.dbg_pe = g_stampbuf;
 #endif
     if ((size_t)a.H * a.W * 16 >= ((size_t)1 << 28)) { set_error("mfma: frame too large for 32-bit buffer offsets (H*W must stay below 2^24 pixels)"); return 1; }
-    const bool std_bits = a.acc_lo == -131072 && a.acc_hi == 131071 && a.add_lo == -524288 && a.add_hi == 524287;
-    const int mode = tap ? GEN_TAP : (!general ? MERGED : (std_bits ? (one_risky_pe ? HYB : GEN_STD) : GEN_ANY));
-    if (mode == GEN_TAP) {      // debug forward with PE taps: the per-PE kernels in their run-time-bounds form, every output kind
-        if (lp.d_afrag_pesplit && a.afrag == lp.d_afrag_pesplit) { set_error("mfma: the pe-split last-layer kernel has no PE taps"); return 1; }
-        switch (lp.mfma_kind) {
-            case MFMA_H3:
-                if (epi == EPI_MID) launch<mfma_h3_kernel<GEN_TAP, EPI_MID>>(a, st);
-                else if (epi == EPI_PRERES) launch<mfma_h3_kernel<GEN_TAP, EPI_PRERES>>(a, st);
-                else { set_error("mfma: 3x3 last layer not supported"); return 1; }
-                break;
-            case MFMA_H5:
-                if (epi == EPI_MID) launch<mfma_h5_kernel<GEN_TAP, EPI_MID>>(a, st);
-                else if (epi == EPI_PRERES) launch<mfma_h5_kernel<GEN_TAP, EPI_PRERES>>(a, st);
-                else if (last_nv(a.oc) == 3) launch<mfma_h5_kernel<GEN_TAP, EPI_LAST, 0, 3>>(a, st);
-                else launch<mfma_h5_kernel<GEN_TAP, EPI_LAST>>(a, st);
-                break;
-            case MFMA_F5:
-                if (src == SRC_F32) { if (a.rc_out) launch<mfma_f5_kernel<GEN_TAP, SRC_F32, true, 4>>(a, st, F5_TH); else launch<mfma_f5_kernel<GEN_TAP, SRC_F32, false, 4>>(a, st, F5_TH); }
-                else if (src == SRC_I8D) { if (a.rc_out) launch<mfma_f5_kernel<GEN_TAP, SRC_I8D, true, 4>>(a, st, F5_TH); else launch<mfma_f5_kernel<GEN_TAP, SRC_I8D, false, 4>>(a, st, F5_TH); }
-                else { if (a.rc_out) launch<mfma_f5_kernel<GEN_TAP, SRC_I8, true, 4>>(a, st, F5_TH); else launch<mfma_f5_kernel<GEN_TAP, SRC_I8, false, 4>>(a, st, F5_TH); }
-                break;
-            default: set_error("mfma: layer shape not supported by the MFMA engine"); return 1;
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_error(std::string("mfma launch failed: ") + hipGetErrorString(e)); return 1; }
-        return 0;
-    }
-    const bool dl = a.direct && mode != GEN_ANY && epi == EPI_LAST && a.z_out == -128.f && !a.anchor;
-    const bool d1 = dl && a.direct == 1, d2 = dl && a.direct == 2;
-    switch (lp.mfma_kind) {
-        case MFMA_H3:
-            if (epi == EPI_MID) SESRQ_BY_MODE(mfma_h3_kernel, EPI_MID);
-            else if (epi == EPI_PRERES) SESRQ_BY_MODE(mfma_h3_kernel, EPI_PRERES);
-            else { set_error("mfma: 3x3 last layer not supported"); return 1; }
-            break;
-        case MFMA_H5:
-            if (epi == EPI_LAST && lp.d_afrag_pesplit && a.afrag == lp.d_afrag_pesplit) {
-                if (mode == MERGED) launch<mfma_h5p_kernel<MERGED>>(a, st);
-                else if (mode == GEN_ANY) launch<mfma_h5p_kernel<GEN_ANY>>(a, st);
-                else launch<mfma_h5p_kernel<GEN_STD>>(a, st);
-                break;
-            }
-            if (epi == EPI_MID) SESRQ_BY_MODE(mfma_h5_kernel, EPI_MID);
-            else if (epi == EPI_PRERES) SESRQ_BY_MODE(mfma_h5_kernel, EPI_PRERES);
-            // (below) d1: the output requant as one fma -- proven for this layer's (M, n), zero point -128, biased sums, int8 output only
-
-            // fp32 frame + the x2 anchor add on the pair map (3 -> 12 channels, PixelShuffle 2): OUTF = 2; the one-fma forms do not care about the anchor
-            else if (!a.out_q && a.out_f && a.anchor && last_nv(a.oc) == 3 && last_pairmap(a.oc, a.ps) && a.ic == 16) {
-                const bool da = a.direct && mode != GEN_ANY && a.z_out == -128.f;
-                if (da && a.direct == 1) SESRQ_BY_MODE_B(mfma_h5_kernel, EPI_LAST, 12, 3, 2); else if (da && a.direct == 2) SESRQ_BY_MODE_B(mfma_h5_kernel, EPI_LAST, 22, 3, 2); else SESRQ_BY_MODE(mfma_h5_kernel, EPI_LAST, 2, 3, 2);
-            }
-            // fp32 frame only (the reference's return type), no anchor: the OUTF flavours of the same FAST instances
-            else if (!a.out_q && a.out_f && !a.anchor && last_nv(a.oc) == 3 && last_pairmap(a.oc, a.ps)) { if (d1) SESRQ_BY_MODE_B(mfma_h5_kernel, EPI_LAST, 12, 3, 1); else if (d2) SESRQ_BY_MODE_B(mfma_h5_kernel, EPI_LAST, 22, 3, 1); else SESRQ_BY_MODE(mfma_h5_kernel, EPI_LAST, 2, 3, 1); }
-            else if (!a.out_q && a.out_f && !a.anchor && last_nv(a.oc) == 4 && a.ps == 2) { if (d1) SESRQ_BY_MODE_B(mfma_h5_kernel, EPI_LAST, 12, 4, 1); else if (d2) SESRQ_BY_MODE_B(mfma_h5_kernel, EPI_LAST, 22, 4, 1); else SESRQ_BY_MODE(mfma_h5_kernel, EPI_LAST, 2, 4, 1); }
-            else if (!a.out_q && a.out_f && !a.anchor && last_nv(a.oc) == 4 && a.ps == 4) { if (d1) SESRQ_BY_MODE_B(mfma_h5_kernel, EPI_LAST, 14, 4, 1); else if (d2) SESRQ_BY_MODE_B(mfma_h5_kernel, EPI_LAST, 24, 4, 1); else SESRQ_BY_MODE(mfma_h5_kernel, EPI_LAST, 4, 4, 1); }
-            else if (last_nv(a.oc) == 3) {       // up to 12 output channels: three real rows per lane group (must match pack_mfma_frags)
-                if (a.out_q && !a.out_f && last_pairmap(a.oc, a.ps)) { if (d1) SESRQ_BY_MODE_B(mfma_h5_kernel, EPI_LAST, 12, 3); else if (d2) SESRQ_BY_MODE_B(mfma_h5_kernel, EPI_LAST, 22, 3); else SESRQ_BY_MODE(mfma_h5_kernel, EPI_LAST, 2, 3); }
-                else SESRQ_BY_MODE(mfma_h5_kernel, EPI_LAST, 0, 3);
-            }
-            else if (a.out_q && !a.out_f && a.ps == 2) { if (d1) SESRQ_BY_MODE_B(mfma_h5_kernel, EPI_LAST, 12); else if (d2) SESRQ_BY_MODE_B(mfma_h5_kernel, EPI_LAST, 22); else SESRQ_BY_MODE(mfma_h5_kernel, EPI_LAST, 2); }
-            else if (a.out_q && !a.out_f && a.ps == 4) { if (d1) SESRQ_BY_MODE_B(mfma_h5_kernel, EPI_LAST, 14); else if (d2) SESRQ_BY_MODE_B(mfma_h5_kernel, EPI_LAST, 24); else SESRQ_BY_MODE(mfma_h5_kernel, EPI_LAST, 4); }
-            else SESRQ_BY_MODE(mfma_h5_kernel, EPI_LAST);
-            break;
-        case MFMA_F5:
-#define SESRQ_F5(...)                                                                    \
-    do {                                                                                 \
-        if (mode == MERGED) launch<mfma_f5_kernel_w4<MERGED, __VA_ARGS__>>(a, st, F5_TH);       \
-        else if (mode == HYB) { if (launch_f5_hybrid<__VA_ARGS__>(a, st)) return 1; }    \
-        else if (mode == GEN_STD) launch<mfma_f5_kernel<GEN_STD, __VA_ARGS__>>(a, st, F5_TH);   \
-        else launch<mfma_f5_kernel<GEN_ANY, __VA_ARGS__>>(a, st, F5_TH);                        \
-    } while (0)
-#define SESRQ_F5_NCH(...)                                                      \
-    do {                                                                       \
-        if (a.ic == 3) SESRQ_F5(__VA_ARGS__, 3);                               \
-        else if (a.ic == 1) SESRQ_F5(__VA_ARGS__, 1);                          \
-        else SESRQ_F5(__VA_ARGS__, 4);                                         \
-    } while (0)
-            if (src == SRC_F32) { if (a.rc_out) SESRQ_F5_NCH(SRC_F32, true); else SESRQ_F5_NCH(SRC_F32, false); }
-            else if (src == SRC_I8D) { if (a.rc_out) SESRQ_F5_NCH(SRC_I8D, true); else SESRQ_F5_NCH(SRC_I8D, false); }
-            else { if (a.rc_out) SESRQ_F5_NCH(SRC_I8, true); else SESRQ_F5_NCH(SRC_I8, false); }
-#undef SESRQ_F5_NCH
-#undef SESRQ_F5
-            break;
-        default: set_error("mfma: layer shape not supported by the MFMA engine"); return 1;
-    }
+    Pick p;
+    if (select_mfma(lp, a, src, epi, general, one_risky_pe, tap, p)) return 1;
+    if (!dispatch_mfma(p, a, st)) { set_error("mfma: no kernel instance for the selected template arguments"); return 1; }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error(std::string("mfma launch failed: ") + hipGetErrorString(e)); return 1; }
     return 0;

@@ -201,15 +201,11 @@ int forward_impl(const sesrq_net *net, const void *in, int in_dtype, void *out_q
         const bool use_mfma = mfma_ok && (!dbg || tap_mfma) && !q0tap && !ictap;
         if (use_mfma) {
             a.afrag = general ? lp.d_afrag_general : lp.d_afrag_merged;
-            // exactly one PE can saturate (and nothing forces the full per-PE path): merged chain + that PE's chain
-            const bool one_pe = lp.general && !net->force_general && !dbg && lp.d_afrag_others && net->acc_bits == 18 && net->add_bits == 20;
+            // the hybrid (merged chain + the risky PE's chain) unless something forces the full per-PE path
+            const bool one_pe = lp.hybrid && !net->force_general && !dbg;
             if (one_pe) {
                 a.afrag = lp.d_afrag_others; a.afrag2 = lp.d_afrag_general; a.risky_pe = __builtin_ctz(lp.risky_mask); a.afrag_sp = lp.d_afrag_sparse;
-                // hidden-layer rows: channel o sits in register o >> 2 of lane group o & 3.  If every channel that can saturate lives in
-                // ONE register, the hybrid first layer clamps that register only (risky_reg), else all four (4)
-                a.risky_reg = 4;
-                for (int i = 0; i < 4; ++i)
-                    if (lp.risky_oc && (lp.risky_oc & ~(0xf << (4 * i))) == 0) a.risky_reg = i;
+                a.risky_reg = lp.risky_reg;
             }
             if (lp.d_afrag_pesplit) a.afrag = lp.d_afrag_pesplit;
             if (launch_mfma(lp, a, src, epi, general, st, one_pe, tap_mfma)) return 1;

@@ -121,7 +121,7 @@ def test_eval_argument_checks_without_a_device():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_eval_isa_passes_store_hazard_scan(tmp_path):
+def test_eval_isa_clears_the_hazard_scan(tmp_path):
     asm = str(tmp_path / "sesrq_eval.s")
     flags = subprocess.run(["make", "-s", "-C", CSRC, "print-cxxflags"], check=True, capture_output=True, text=True).stdout.split()
     assert "-ffp-contract=off" in flags
