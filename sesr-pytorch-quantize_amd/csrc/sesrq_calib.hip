@@ -7,12 +7,15 @@
 // with Wq*sw -> PEs_and_bias_adder mode 0 -> activation), with this batch's (scale, zero) of the input:
 //   q      = clamp_b(rint(x/scale + zero)) - zero            integer; outside the frame 0     (quan_func.py:207,215)
 //            (clamp_b = clamp(., -2^(b-1), 2^(b-1) - 1), the width b of sesrq_calib_conv_q; b = 8 for sesrq_calib_conv)
-//   pe_p   = sum_{ic = p mod 4, taps} Wq * q                  exact in int32                   (quan_func.py:298-318)
+//   pe_p   = sum_{ic = p mod 4, taps} Wq * q                  exact in int64                   (quan_func.py:298-318)
 //   v_p    = clamp(f32(pe_p) * f32(scale*sw), fmin18, fmax18)                                  (quan_func.py:330-333)
 //   v      = clamp(v_0 + v_1 + v_2 + v_3, fmin20, fmax20) + bias_q * f32(scale*sw)             (quan_func.py:431-434,459)
+// q and pe_p are exact for every zero derive_domain can produce (|zero| <= 2^30): q is staged as int32 and the PE sums are formed in
+// int64 -- a domain far from zero (min / span above ~127 at b = 8) has |q| far beyond 16 bits and |pe_p| beyond 32.
 // The reference forms the same sums in fp32 (fl(Wq*sw) * fl(q*scale) accumulated by oneDNN in an
 // unspecified order); here the integer sum is exact and scaled once, so results agree to fp32 rounding
-// -- calibration is pinned to the reference within a tolerance, not bit for bit.
+// -- calibration is pinned to the reference within a tolerance, not bit for bit, and to
+// oracle/calib_oracle.py (the definition above) bit for bit.
 #include <algorithm>
 #include <cmath>
 
@@ -27,7 +30,8 @@ struct CalibArgs {
     const int *w;           // [oc][ic][k][k] int32 (quantised weights)
     const float *qbias;     // [oc]  bias_q * f32(scale*sw)
     int N, H, W, ic, oc;
-    float scale, zero;      // this batch's input domain
+    float scale, zero;      // this batch's input domain (zero: f32 of izero)
+    int izero;
     float qlo, qhi;         // activation range of the width: -2^(b-1), 2^(b-1) - 1
     float ss;               // f32(scale * sw)
     float acc_lo, acc_hi, add_lo, add_hi;
@@ -38,12 +42,13 @@ struct CalibArgs {
 template <int K>
 __global__ __launch_bounds__(256) void calib_conv_kernel(const CalibArgs a) {
     constexpr int R = K / 2, TW = 32, TH = 8, SW = TW + K - 1, SH = TH + K - 1;
-    __shared__ short tile[SESRQ_MAX_CH][SH * SW];
+    __shared__ int tile[SESRQ_MAX_CH][SH * SW];     // q = r - zero: |q| <= 2^30 + 2^7 (K = 5: 27 KiB)
     const int tid = threadIdx.x, lx = tid & 31, ly = tid >> 5;
     const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH, n = blockIdx.z;
     const size_t HW = (size_t)a.H * a.W;
     const sesrq_calib_slot *d = a.slot;
     const float scale = d ? d->scale32 : a.scale, zero = d ? d->zero32 : a.zero, ss = d ? d->ss : a.ss;
+    const int izero = d ? d->zero : a.izero;
     const float acc_lo = d ? d->acc_lo : a.acc_lo, acc_hi = d ? d->acc_hi : a.acc_hi;
     const float add_lo = d ? d->add_lo : a.add_lo, add_hi = d ? d->add_hi : a.add_hi;
     const float *qbias = d ? d->qbias : a.qbias;
@@ -54,9 +59,9 @@ __global__ __launch_bounds__(256) void calib_conv_kernel(const CalibArgs a) {
             if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) {
                 const float xv = a.in[((size_t)n * a.ic + c) * HW + (size_t)gy * a.W + gx];
                 const float r = fminf(fmaxf(rintf(__fadd_rn(__fdiv_rn(xv, scale), zero)), a.qlo), a.qhi);
-                q = (int)(r - zero);
+                q = (int)r - izero;
             }
-            tile[c][i] = (short)q;
+            tile[c][i] = q;
         }
     __syncthreads();
     const int gx = x0 + lx, gy = y0 + ly;
@@ -64,13 +69,13 @@ __global__ __launch_bounds__(256) void calib_conv_kernel(const CalibArgs a) {
     for (int o = 0; o < a.oc; ++o) {
         float sum = 0.f;
         for (int p = 0; p < 4; ++p) {
-            int acc = 0;
+            long long acc = 0;
             for (int c = p; c < a.ic; c += 4) {
                 const int *wp = a.w + ((size_t)o * a.ic + c) * K * K;
 #pragma unroll
                 for (int ky = 0; ky < K; ++ky)
 #pragma unroll
-                    for (int kx = 0; kx < K; ++kx) acc += wp[ky * K + kx] * (int)tile[c][(ly + ky) * SW + lx + kx];
+                    for (int kx = 0; kx < K; ++kx) acc += (long long)wp[ky * K + kx] * tile[c][(ly + ky) * SW + lx + kx];
             }
             const float v = fminf(fmaxf(__fmul_rn((float)acc, ss), acc_lo), acc_hi);
             sum = (p == 0) ? v : __fadd_rn(sum, v);
@@ -225,10 +230,11 @@ int sesrq_calib_conv_q(const sesrq_calib_conv_desc *d, const float *in, const fl
     if (!d || !in || !out || !d->w || !d->qbias) { set_error("sesrq_calib_conv: null argument"); return 1; }
     if ((d->k != 3 && d->k != 5) || d->ic < 1 || d->ic > SESRQ_MAX_CH || d->oc < 1 || d->oc > SESRQ_MAX_CH) { set_error("sesrq_calib_conv: unsupported layer shape"); return 1; }
     if (N < 1 || H < 1 || W < 1 || !(d->in_scale > 0.f)) { set_error("sesrq_calib_conv: bad size or scale"); return 1; }
+    if (d->in_zero < -(1 << 30) || d->in_zero > (1 << 30)) { set_error("sesrq_calib_conv: |in_zero| must be <= 2^30"); return 1; }
     CalibArgs a;
     a.in = in; a.skip = skip; a.out = out; a.w = d->w; a.qbias = d->qbias;
     a.N = N; a.H = H; a.W = W; a.ic = d->ic; a.oc = d->oc;
-    a.scale = d->in_scale; a.zero = (float)d->in_zero; a.ss = d->ss;
+    a.scale = d->in_scale; a.zero = (float)d->in_zero; a.izero = d->in_zero; a.ss = d->ss;
     a.qlo = -(float)(1 << (quan_bits - 1)); a.qhi = (float)((1 << (quan_bits - 1)) - 1);
     a.acc_lo = d->acc_lo; a.acc_hi = d->acc_hi; a.add_lo = d->add_lo; a.add_hi = d->add_hi; a.relu = d->relu;
     a.slot = nullptr;

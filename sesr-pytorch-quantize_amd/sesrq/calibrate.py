@@ -32,6 +32,8 @@ import torch
 from . import _lib
 from .bundle import Bundle, derive_bundle, quantize_weight
 
+ZERO_LIMIT = 1 << 30        # |zero| of a batch's domain (csrc/sesrq_calib.hip derive_domain), for a domain far from 0
+
 
 def _smooth(d: np.ndarray, eps: float = 1e-4) -> np.ndarray:
     """Move a little mass onto the empty bins of a normalised histogram so that KL(p || q) stays finite where the folded
@@ -194,6 +196,7 @@ class Calibrator:
         assert mx != mn, "Input tensor is all equal,{}".format(k)
         scale = (mx - mn) / ((1 << self.quan_bits) - 1)
         zero = -(1 << (self.quan_bits - 1)) - round(mn / scale)
+        zero = min(max(zero, -ZERO_LIMIT), ZERO_LIMIT)      # as the device pass clamps it (derive_domain): the int the conv reads
         self.last_scale[k], self.last_zero[k] = scale, int(zero)
         return scale, int(zero)
 

@@ -17,8 +17,13 @@ Per (case, b), under tests/golden/quan_bits/:
 Widths: b = 3, 4, 6 and 7 for sesr_x4, nrdm_3 and sesr_x2_rand, b = 2 and 5 for nrdm_3; the reference's own calibration runs at every
 one of these (case, b) pairs.
 
+  <case>.q<b>.trace.npz   (--trace; TRACES) where the reference's own mode-0 run on the full frame and oracle/calib_oracle.py first
+                          round a quantiser input to different codes: the layer, the positions, both codes, the reference's fp32
+                          input values there and the oracle's, and the reference's per-layer extrema
+
 Usage:  python tests/golden/make_quan_bits_golden.py                  # every case (one process each)
         python tests/golden/make_quan_bits_golden.py --case sesr_x4 --bits 4
+        python tests/golden/make_quan_bits_golden.py --trace                # TRACES
 """
 import argparse
 import json
@@ -35,6 +40,7 @@ sys.path.insert(0, HERE)
 from make_golden import CASES, CROP_H, CROP_W, REF, sha  # noqa: E402
 
 OUT = os.path.join(HERE, "quan_bits")
+TRACES = [("sesr_x4", 3)]      # the (case, b) whose calibration the oracle does not reproduce within the bar (test_calib_oracle.py)
 RUNS = [("sesr_x4", 4), ("sesr_x4", 6), ("nrdm_3", 4), ("nrdm_3", 2), ("nrdm_3", 6), ("sesr_x2_rand", 4), ("sesr_x2_rand", 6),
         ("sesr_x4", 3), ("sesr_x4", 7), ("nrdm_3", 3), ("nrdm_3", 5), ("nrdm_3", 7), ("sesr_x2_rand", 3), ("sesr_x2_rand", 7)]
 
@@ -195,14 +201,113 @@ def run_case(name: str, b: int) -> None:
     shutil.rmtree(scratch, ignore_errors=True)
 
 
+def trace_case(name: str, b: int) -> None:
+    """The reference's mode-0 run with every quantiser's input and output recorded, layer by layer against calib_oracle: at the
+    first quantiser input k whose codes differ, the positions and values (the upstream codes all agree, so the oracle's input there is
+    its conv of the reference's own codes)."""
+    cfg = CASES[name]
+    sys.dont_write_bytecode = True
+    sys.path.insert(0, REF)
+    sys.path.insert(0, os.path.join(HERE, "..", ".."))
+    import torch
+    from torch import nn
+    import define
+    define.MFLAG = cfg["mflag"]
+    define.QUAN_BIT = b
+    from myQL import quan_func as qf
+    from myQL.quan_classes import NodeInsertMapping, FunctionPackage, NodeInsertMappingElement
+    from myQL.graph_modify import insert_before, insert_bias_bypass
+    from models import sesr, nrdm_3, sesr_arch
+    from oracle import calib_oracle as CO
+
+    torch.manual_seed(0)
+    scratch = tempfile.mkdtemp(prefix="golden_t_", dir=os.path.join(HERE, "..", "..", ".scratch"))
+    os.chdir(scratch)
+    float_cls = {5: sesr.sesr, 3: nrdm_3.nr, 6: sesr_arch.sesr}[cfg["mflag"]]
+    if cfg["ckpt"] is None:
+        torch.manual_seed(cfg["seed"])
+        proto_sd = {k: v.clone() for k, v in float_cls().state_dict().items()}
+    m = float_cls()
+    if cfg["ckpt"] is None:
+        m.load_state_dict(proto_sd, strict=False)
+    m.train()
+    if cfg["ckpt"] is not None:
+        m.load_state_dict(torch.load(os.path.join(REF, cfg["ckpt"]), weights_only=True, map_location="cpu"), strict=False)
+    m = m.float()
+    m.collapse()
+    convs = [m.conv_first.conv_expand] + [blk.conv_expand for blk in m.residual_block] + [m.conv_last.conv_expand]
+    Wf = [c.weight.detach().numpy().copy() for c in convs]
+    bf = [c.bias.detach().numpy().copy() for c in convs]
+
+    seen = {}
+
+    def recorder(*a, **kw):
+        t = kw["tensor_input"] if "tensor_input" in kw else a[0]
+        out = qf.quantize_asymmetrical_by_tensor(*a, **kw)
+        fid = kw["func_id"]
+        seen[fid] = (t.detach().numpy().copy(), out.detach().numpy().copy(),
+                     torch.load(f"output_pt/input/input.{fid}.scale.pt"), torch.load(f"output_pt/input/input.{fid}.zero.pt"))
+        return out
+
+    def pack(fn, kw):
+        mp = NodeInsertMapping()
+        mp.add_config(NodeInsertMappingElement(nn.Conv2d, FunctionPackage(fn, kw)))
+        return mp
+
+    model = qf.quantize_model_weight(m, b, 0)
+    mp = NodeInsertMapping()
+    fp = FunctionPackage(recorder, {"width": b, "exe_mode": 0})
+    mp.add_config(NodeInsertMappingElement(nn.Conv2d, fp))
+    mp.add_config(NodeInsertMappingElement(nn.PixelShuffle, fp))
+    model = insert_before(model_input=model, insert_mapping=mp, has_func_id=True)
+    model = insert_before(model_input=model, insert_mapping=pack(qf.reshape_input_for_hardware_pe, {"pe_num": define.PE}))
+    model = insert_bias_bypass(model_input=model, insert_mapping=pack(
+        qf.PEs_and_bias_adder, {"pe_add_width": define.PE_ADD_BIT, "pe_acc_width": define.PE_ACC_BIT,
+                                "bias_width": define.BIAS_BIT, "pe_num": define.PE, "exe_mode": 0}))
+    x_full = torch.load(os.path.join(REF, cfg["inp"]), weights_only=True, map_location="cpu").float()
+    with torch.no_grad():
+        model(x_full)
+    L = 5
+    ps = {5: 4, 6: 2, 3: 1}[cfg["mflag"]]
+    mins = [float(seen[k][0].min()) for k in range(L + 1)]
+    maxs = [float(seen[k][0].max()) for k in range(L + 1)]
+    # the reference's codes r = rint(out / scale) + zero (out = (r - zero) * scale in fp32: |out / scale - (r - zero)| << 0.5)
+    rcode = {k: np.rint(seen[k][1].astype(np.float64) / seen[k][2]).astype(np.int64) + seen[k][3] for k in range(L)}
+    orc = CO.forward(Wf, bf, ps, [x_full.numpy()], b, keep_inputs=True)
+    for k in range(L):
+        ocode = CO.codes(orc.inputs[0][k], orc.domains[0][k], b)
+        diff = np.argwhere(ocode != rcode[k])
+        if len(diff):
+            break
+    else:
+        raise SystemExit(f"{name} b={b}: the reference's codes and the oracle's agree at every layer")
+    idx = tuple(diff.T)
+    tag = f"{name}.q{b}"
+    np.savez_compressed(os.path.join(OUT, f"{tag}.trace.npz"),
+                        meta=np.array(json.dumps(dict(case=name, mflag=cfg["mflag"], quan_bits=b, layer=int(k), ref_min=mins,
+                                                      ref_max=maxs, ref_scale=float(seen[k][2]), ref_zero=int(seen[k][3])))),
+                        pos=diff.astype(np.int32), ref_code=rcode[k][idx].astype(np.int32), oracle_code=ocode[idx].astype(np.int32),
+                        ref_x=seen[k][0][idx].astype(np.float32), oracle_x=orc.inputs[0][k][idx].astype(np.float32))
+    print(f"[{tag}.trace] layer {k}: {len(diff)} codes differ, first at {diff[0].tolist()}: ref {rcode[k][idx][0]} oracle "
+          f"{ocode[idx][0]}; ref x {seen[k][0][idx][0]!r} oracle x {orc.inputs[0][k][idx][0]!r}", flush=True)
+    os.chdir(HERE)
+    shutil.rmtree(scratch, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default=None)
     ap.add_argument("--bits", type=int, default=None)
+    ap.add_argument("--trace", action="store_true")
     args = ap.parse_args()
     os.makedirs(os.path.join(HERE, "..", "..", ".scratch"), exist_ok=True)
     os.makedirs(OUT, exist_ok=True)
-    if args.case:
+    if args.trace and args.case:
+        trace_case(args.case, args.bits)
+    elif args.trace:
+        for c, b in TRACES:
+            subprocess.run([sys.executable, os.path.abspath(__file__), "--trace", "--case", c, "--bits", str(b)], check=True)
+    elif args.case:
         run_case(args.case, args.bits)
     else:
         for c, b in RUNS:
