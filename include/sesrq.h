@@ -154,6 +154,27 @@ int sesrq_layer_one_fma(const sesrq_net *net, int k);
  * bit-identical to clamp8(rint(fl(fl(s * M) * 2^-n - 128))) for every accumulator value s, 2 = (output_layer != 0 only) it is
  * not, but the single-rounding form is, 0 = neither.  No reference counterpart. */
 int sesrq_requant_form(uint32_t M, uint32_t n, int output_layer);
+/* The load-time saturation analysis of ONE layer as a host function (no device, no net): what sesrq_create decides from it.
+ *   w [oc][ic][k][k], add_const [oc] or NULL (= all zero), zero = the zero point of the layer's input domain (the pad value is
+ *   max(zero, -128)), acc_bits / add_bits = pe_acc_bits / pe_add_bits.
+ * For q in [-128, 127] PE p (input channels c = p mod 4) of output channel o reaches at most hi = 127 S+ + 128 S- and at least
+ * -lo = -(128 S+ + 127 S-), S+ / S- = the sums of its positive / negative weight magnitudes.  The PE clamp can fire iff
+ * hi > 2^(acc_bits-1) - 1 or lo > 2^(acc_bits-1); the adder clamp likewise for the sums over the four PEs.
+ *   *risky_mask : bit p = PE p's clamp can fire for some output channel
+ *   *worst_pe   : the largest hi / lo of any PE;  *worst_sum : of any four-PE sum
+ *   *reach      : min(*worst_sum, 2^(add_bits-1)) + max |add_const| = the largest |adder output + add constant|
+ * Returns a mask of SESRQ_VERDICT_* bits, or -1 (sesrq_last_error) for a NULL w or a shape / width sesrq_create refuses:
+ *   SATURATION_FREE : neither clamp can fire -- the merged kernels (one accumulator, no clamp; the fused trio) may run the layer; without
+ *                     it, exactly one risky PE at 18 / 20 bits selects the hybrid kernels, anything else the per-PE ones
+ *   BIASED_OK       : *reach < 2^22.  The MFMA kernels' merged, hybrid, literal-clamp per-PE and fused-trio forms carry the sum as the bit
+ *                     pattern of the float 1.5 * 2^23 + s, exact only for |s| < 2^22 (one binade).  The reference configuration -- 18 / 20
+ *                     bits, a 16-bit constant: 2^19 + 2^15 -- always has the bit.  Without it the MFMA engine runs the layer on the
+ *                     per-PE kernel with run-time bounds, which converts the integer sum (sesrq_layer_engine: "...-unbiased"), outside
+ *                     the fused trio and without the one-fma requant forms; the dot4 kernels never bias.  Same bits either way.
+ * No reference counterpart. */
+enum { SESRQ_VERDICT_SATURATION_FREE = 1, SESRQ_VERDICT_BIASED_OK = 2 };
+int sesrq_saturation_verdict(const int8_t *w, int k, int ic, int oc, const int32_t *add_const, int zero, int acc_bits, int add_bits,
+                             int *risky_mask, int64_t *worst_pe, int64_t *worst_sum, int64_t *reach);
 
 /* Channel geometry of a created net: input channels, output channels of the last conv (before PixelShuffle), PixelShuffle factor -- what a
  * caller needs to size the output of sesrq_forward, (N, cout / r^2, H * r, W * r) (csrc/torch_op/sesrq_torch_op.cpp does). */

@@ -244,6 +244,11 @@ struct LayerPlan {
     int risky_oc = 0;        // output channels (bit o) with such a PE sum
     bool hybrid = false;     // exactly one PE can saturate, at the 18 / 20-bit clamps: the MFMA kernels may run its merged chain + that PE's
     int risky_reg = 4;       // hybrid first layer: the accumulator register holding every channel that can saturate (0..3), or 4 = any
+    // |adder output + add constant| can reach BIASED_LIMIT: the MFMA kernels that seed the accumulator with MAGIC_I (merged, hybrid,
+    // literal-clamp per-PE, fused trio) would read a wrong float, so the MFMA engine runs this layer on the run-time-bounds per-PE
+    // kernel (GEN_ANY: v_cvt_f32_i32, no bias) and keeps it out of the trio and of the one-fma requant forms
+    long long reach = 0;
+    bool wide = false;
 };
 
 void set_error(const std::string &msg);
@@ -251,6 +256,10 @@ void set_error(const std::string &msg);
 // load-time proof (sesrq_verify.hip): can the 18-bit PE clamp / 20-bit adder clamp of this layer ever fire?
 bool saturation_free(const sesrq_layer_desc &d, int zc, int acc_bits, int add_bits, long long &worst_pe, long long &worst_sum, int &risky_mask,
                      int *risky_oc = nullptr);
+// The biased accumulator (bits = MAGIC_I + s read as the float 1.5 * 2^23 + s, sesrq_mfma_common.h) is exact only inside one binade:
+// |s| < 2^22.  reachable_sum = the largest |adder output + add constant| a layer can produce: min(worst_sum, adder range) + max |add_const|.
+constexpr long long BIASED_LIMIT = 1LL << 22;
+long long reachable_sum(long long worst_sum, int add_bits, const int32_t *add_const, int oc);
 
 // launch planner (sesrq_plan.hip)
 struct WsLayout {

@@ -272,6 +272,9 @@ int sesrq_create_q(const sesrq_net_desc *d, const sesrq_options *opts, int quan_
         lp.ocp = (k == L - 1) ? ((l.oc + 3) & ~3) : 16;
         const int zc = std::max(d->zero[k], -128);
         lp.general = !saturation_free(l, zc, d->pe_acc_bits, d->pe_add_bits, lp.worst_pe, lp.worst_sum, lp.risky_mask, &lp.risky_oc);
+        // the biased accumulator of the MFMA kernels is exact for |s| < 2^22 only (never reached at 18 / 20 bits with a 16-bit constant)
+        lp.reach = reachable_sum(lp.worst_sum, d->pe_add_bits, l.add_const, l.oc);
+        lp.wide = lp.reach >= BIASED_LIMIT;
         std::vector<int> gen, mer;
         pack_weights(l, lp.ocp, k == 0, gen, mer);
         const size_t bytes = gen.size() * sizeof(int);
@@ -370,6 +373,7 @@ int sesrq_create_q(const sesrq_net_desc *d, const sesrq_options *opts, int quan_
             a.Cs = a.Cd - 128.f;
         }
         if (l.M_oc || narrow) a.direct = 0;      // the reduced forms are proven for the 8-bit clamp only
+        if (lp.wide) a.direct = 0;               // ... and for |s| < 2^22 (biased sums), which this layer can leave
         a.qlo = (float)qlo; a.qhi = (float)qhi; a.qhalf = (float)(1 << (quan_bits - 1)); a.qspan = (float)(1 << quan_bits);
         a.mn_oc = lp.d_mn_oc;
         a.Mres = (float)d->M_res; a.shres = ldexpf(1.0f, -(int)d->n_res);
@@ -381,7 +385,7 @@ int sesrq_create_q(const sesrq_net_desc *d, const sesrq_options *opts, int quan_
         lp.engine_dot4 = std::string(lp.general ? "dot4-general" : "dot4-merged") + (l.M_oc ? "-perchannel" : "") +
                          (narrow ? "-q" + std::to_string(quan_bits) : "");
         // exactly one risky PE (its image is packed above) at the reference's 18 / 20-bit clamps, which the hybrid kernels hold as literals
-        lp.hybrid = lp.d_afrag_others && d->pe_acc_bits == 18 && d->pe_add_bits == 20;
+        lp.hybrid = lp.d_afrag_others && d->pe_acc_bits == 18 && d->pe_add_bits == 20 && !lp.wide;
         // hidden-layer rows: channel o sits in register o >> 2 of lane group o & 3.  If every channel that can saturate lives in
         // ONE register, the hybrid first layer clamps that register only (risky_reg), else all four (4)
         for (int i = 0; i < 4; ++i)
@@ -389,6 +393,8 @@ int sesrq_create_q(const sesrq_net_desc *d, const sesrq_options *opts, int quan_
         static const char *kn[] = {"", "mfma-h3", "mfma-h5", "mfma-f5"};
         lp.engine_mfma = lp.mfma_kind == MFMA_NONE ? lp.engine_dot4 : std::string(kn[lp.mfma_kind]) + (lp.hybrid ? "-hybrid" : (lp.general ? "-general" : "-merged"));
         if (lp.d_afrag_pesplit) lp.engine_mfma = std::string("mfma-h5p-") + (lp.general ? "general" : "merged");
+        // a sum that can leave the biased range: the per-PE kernel with run-time bounds (GEN_ANY), whatever the saturation verdict says
+        if (lp.wide && lp.mfma_kind != MFMA_NONE) lp.engine_mfma = std::string(lp.d_afrag_pesplit ? "mfma-h5p" : kn[lp.mfma_kind]) + "-unbiased";
         lp.engine = (net->engine == SESRQ_ENGINE_DOT4) ? lp.engine_dot4 : lp.engine_mfma;
     }
     // fused hidden trios, greedy from the residual-merging layer L-2 backwards: three consecutive 3x3 16->16 layers whose
@@ -396,7 +402,7 @@ int sesrq_create_q(const sesrq_net_desc *d, const sesrq_options *opts, int quan_
     net->trio_len.assign(L, 0);
     auto trio_ok = [&](int k) {
         const LayerPlan &lp = net->layers[k];
-        return k >= 1 && k <= L - 2 && lp.mfma_kind == MFMA_H3 && !lp.general && lp.ic == 16 && lp.oc == 16;
+        return k >= 1 && k <= L - 2 && lp.mfma_kind == MFMA_H3 && !lp.general && !lp.wide && lp.ic == 16 && lp.oc == 16;
     };
     for (int k = L - 4; k >= 1 && trio_ok(k) && trio_ok(k + 1) && trio_ok(k + 2); k -= 3) net->trio_len[k] = 3;
     {   // Residual merge (myQL/quan_func.py:256-270): q4 = clamp8(rint(fl(fl(u * M_res) * 2^-n_res + zero[L-1]))) is a function of the

@@ -1112,7 +1112,8 @@ static int select_mfma(const LayerPlan &lp, const ConvArgs &a, int src, int epi,
     p.epi = epi;
     // the clamp bounds as literals (GEN_STD, HYB) for the reference's 18 / 20-bit widths, as arguments (GEN_ANY) for any other
     const bool std_bits = a.acc_lo == -131072 && a.acc_hi == 131071 && a.add_lo == -524288 && a.add_hi == 524287;
-    p.mode = tap ? GEN_TAP : !general ? MERGED : !std_bits ? GEN_ANY : one_pe ? HYB : GEN_STD;
+    // ... and for a layer whose sums can leave the biased accumulator's range (LayerPlan::wide; forward_impl asks for per-PE sums then)
+    p.mode = tap ? GEN_TAP : !general ? MERGED : (!std_bits || lp.wide) ? GEN_ANY : one_pe ? HYB : GEN_STD;
     const bool pesplit = lp.d_afrag_pesplit && a.afrag == lp.d_afrag_pesplit;
     if (tap && pesplit) { set_error("mfma: the pe-split last-layer kernel has no PE taps"); return 1; }
     switch (lp.mfma_kind) {

@@ -170,7 +170,9 @@ int forward_impl(const sesrq_net *net, const void *in, int in_dtype, void *out_q
         // input tap and the pe-split last layer (OC <= 4) stay with the dot4 kernels
         const bool mfma_ok = net->engine != SESRQ_ENGINE_DOT4 && lp.mfma_kind != MFMA_NONE && (k > 0 || net->fd.ok);
         const bool tap_mfma = dbg && !taps->overflow && !q0tap && !ictap && mfma_ok && !lp.d_afrag_pesplit;
-        const bool general = lp.general || net->force_general || dbg;      // per-PE sums + clamps
+        const bool use_mfma = mfma_ok && (!dbg || tap_mfma) && !q0tap && !ictap;
+        // per-PE sums + clamps; a layer whose sums can leave the biased range (LayerPlan::wide) has no merged MFMA kernel
+        const bool general = lp.general || net->force_general || dbg || (lp.wide && use_mfma);
         a.wpk = general ? lp.d_wpk_general : lp.d_wpk_merged;
         a.N = N; a.H = H; a.W = W;
         a.wg_budget = net->wg_budget;
@@ -198,7 +200,6 @@ int forward_impl(const sesrq_net *net, const void *in, int in_dtype, void *out_q
         }
         if (launch >= NL) { set_error("sesrq_forward: more launches than sesrq_launch_plan reports"); return 1; }
         if (ev) tl_kernel_events = KernelEvents{ev[2 * launch], ev[2 * launch + 1]};     // begin / end events of the next kernel
-        const bool use_mfma = mfma_ok && (!dbg || tap_mfma) && !q0tap && !ictap;
         if (use_mfma) {
             a.afrag = general ? lp.d_afrag_general : lp.d_afrag_merged;
             // the hybrid (merged chain + the risky PE's chain) unless something forces the full per-PE path

@@ -39,6 +39,25 @@ int sesrq_requant_form(uint32_t M, uint32_t n, int output_layer) {
     return 0;
 }
 
+int sesrq_saturation_verdict(const int8_t *w, int k, int ic, int oc, const int32_t *add_const, int zero, int acc_bits, int add_bits,
+                             int *risky_mask, int64_t *worst_pe, int64_t *worst_sum, int64_t *reach) {
+    if (!w || (k != 3 && k != 5) || ic < 1 || ic > SESRQ_MAX_CH || oc < 1 || oc > SESRQ_MAX_CH) {
+        set_error("sesrq_saturation_verdict: null weights or bad layer shape (k 3 or 5, channels 1..16)"); return -1;
+    }
+    if (acc_bits < 9 || acc_bits > 31 || add_bits < acc_bits || add_bits > 31) { set_error("sesrq_saturation_verdict: pe_acc_bits/pe_add_bits out of range"); return -1; }
+    sesrq_layer_desc d = {};
+    d.k = k; d.ic = ic; d.oc = oc; d.w = w; d.add_const = add_const;
+    long long wp = 0, ws = 0;
+    int mask = 0;
+    const bool free_ = saturation_free(d, std::max(zero, -128), acc_bits, add_bits, wp, ws, mask);      // sesrq_create's own call
+    const long long r = reachable_sum(ws, add_bits, add_const, oc);
+    if (risky_mask) *risky_mask = mask;
+    if (worst_pe) *worst_pe = wp;
+    if (worst_sum) *worst_sum = ws;
+    if (reach) *reach = r;
+    return (free_ ? SESRQ_VERDICT_SATURATION_FREE : 0) | (r < BIASED_LIMIT ? SESRQ_VERDICT_BIASED_OK : 0);
+}
+
 int sesrq_quantize_weight(const float *w, size_t count, int width, int8_t *wq, double *scale) {
     if (!w || !wq || !scale || count == 0) { set_error("sesrq_quantize_weight: null/empty argument"); return 1; }
     if (width < 2 || width > 8) { set_error("sesrq_quantize_weight: width must be 2..8"); return 1; }

@@ -117,7 +117,9 @@ bool prove_direct_requant(unsigned M, unsigned n) {
     const float Mf = (float)M, sh = ldexpf(1.0f, -(int)n), Md = Mf * sh, Cd = -(12582912.f * Mf) * sh;
     const double scale = (double)M * ldexp(1.0, -(int)n);
     long long s_lo = (long long)floor(-2.0 / scale), s_hi = (long long)ceil(258.0 / scale);
-    const long long lim = (1ll << 22) - 1;
+    // |s| <= 2^22 - 1 is every sum a kernel that uses this form can see: the reduced forms run on biased sums only, and sesrq_create
+    // keeps a layer whose reachable |s| is 2^22 or more (LayerPlan::wide) off every biased kernel and clears its form
+    const long long lim = BIASED_LIMIT - 1;
     if (s_lo < -lim) s_lo = -lim;
     if (s_hi > lim) s_hi = lim;
     auto cvt_u8 = [](float w) { const float r = rintf(w); return r < 0.f ? 0.f : (r > 255.f ? 255.f : r); };
@@ -142,7 +144,7 @@ bool prove_single_requant(unsigned M, unsigned n) {
     if ((double)Cs != (double)Cd - 128.0) return false;                        // the fma's addend must be exact
     const double scale = (double)M * ldexp(1.0, -(int)n);
     long long s_lo = (long long)floor(-2.0 / scale), s_hi = (long long)ceil(258.0 / scale);
-    const long long lim = (1ll << 22) - 1;
+    const long long lim = BIASED_LIMIT - 1;      // as in prove_direct_requant: no biased kernel sees a sum beyond it
     if (s_lo < -lim) s_lo = -lim;
     if (s_hi > lim) s_hi = lim;
     auto cvt_u8 = [](float w) { const float r = rintf(w); return r < 0.f ? 0.f : (r > 255.f ? 255.f : r); };
@@ -190,5 +192,10 @@ bool saturation_free(const sesrq_layer_desc &d, int zc, int acc_bits, int add_bi
     return ok;
 }
 
+long long reachable_sum(long long worst_sum, int add_bits, const int32_t *add_const, int oc) {
+    long long amax = 0;
+    for (int o = 0; add_const && o < oc; ++o) amax = std::max(amax, std::llabs((long long)add_const[o]));
+    return std::min(worst_sum, 1LL << (add_bits - 1)) + amax;      // the adder clamp bounds what the constant is added to
+}
 
 }  // namespace sesrq

@@ -17,6 +17,7 @@ MAX_LAYERS = 16
 MAX_CH = 16
 F32, I8 = 0, 1
 ENGINE_AUTO, ENGINE_DOT4, ENGINE_MFMA = 0, 1, 2
+VERDICT_SATURATION_FREE, VERDICT_BIASED_OK = 1, 2
 ABI_VERSION = 4
 
 
@@ -79,6 +80,8 @@ SYMBOLS = {
     "sesrq_fast_division_proven": (C.c_int, [C.c_void_p]),
     "sesrq_layer_one_fma": (C.c_int, [C.c_void_p, C.c_int]),
     "sesrq_requant_form": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int]),
+    "sesrq_saturation_verdict": (C.c_int, [C.POINTER(C.c_int8), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int,
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sesrq_net_shape": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sesrq_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "sesrq_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,

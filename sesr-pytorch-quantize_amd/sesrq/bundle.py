@@ -97,6 +97,26 @@ def requant_form(M: int, n: int, output_layer: bool = False) -> int:
     return int(_lib.lib().sesrq_requant_form(int(M), int(n), 1 if output_layer else 0))
 
 
+def saturation_verdict(wq: np.ndarray, add_const=None, zero: int = -128, acc_bits: int = 18, add_bits: int = 20) -> dict:
+    """The load-time saturation analysis of one layer (sesrq_saturation_verdict, a host function: what sesrq_create decides from it).
+    wq (OC, IC, k, k) int8, add_const (OC,) or None, zero = the zero point of the layer's input domain.  Returns saturation_free,
+    biased_ok, risky_mask (bit p = PE p's clamp can fire), worst_pe, worst_sum and reach = the largest |adder output + add constant|."""
+    w = np.ascontiguousarray(wq, dtype=np.int8)
+    if w.ndim != 4 or w.shape[2] != w.shape[3]:
+        raise ValueError("saturation_verdict: weights must be (OC, IC, k, k)")
+    ac = None if add_const is None else np.ascontiguousarray(add_const, dtype=np.int32)
+    if ac is not None and ac.shape != (w.shape[0],):
+        raise ValueError("saturation_verdict: one add constant per output channel")
+    mask, wp, ws, reach = C.c_int(), C.c_int64(), C.c_int64(), C.c_int64()
+    rc = _lib.lib().sesrq_saturation_verdict(w.ctypes.data_as(C.POINTER(C.c_int8)), w.shape[2], w.shape[1], w.shape[0],
+                                             None if ac is None else ac.ctypes.data_as(C.POINTER(C.c_int32)), int(zero), int(acc_bits),
+                                             int(add_bits), C.byref(mask), C.byref(wp), C.byref(ws), C.byref(reach))
+    if rc < 0:
+        raise ValueError("sesrq: " + _lib.last_error())
+    return dict(saturation_free=bool(rc & _lib.VERDICT_SATURATION_FREE), biased_ok=bool(rc & _lib.VERDICT_BIASED_OK),
+                risky_mask=int(mask.value), worst_pe=int(wp.value), worst_sum=int(ws.value), reach=int(reach.value))
+
+
 def requant_const(r: float, data_bit: int = 16, shift_max: int = 32):
     M, n = C.c_uint32(), C.c_uint32()
     _lib.check(_lib.lib().sesrq_requant_const(float(r), data_bit, shift_max, C.byref(M), C.byref(n)), ValueError)

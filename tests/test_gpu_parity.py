@@ -164,8 +164,10 @@ def test_first_layer_with_two_and_four_input_channels(cin):
 @pytest.mark.parametrize("acc_bits,add_bits", [(16, 18), (17, 17), (20, 22), (24, 26)])
 def test_other_pe_bit_widths(acc_bits, add_bits):
     """define.py's PE_ACC_BIT / PE_ADD_BIT are configuration, not constants: narrower accumulators saturate often (and with
-    add_bits <= acc_bits + 1 the adder clamp is no longer a provable no-op), wider ones never -- the kernels take the widths
-    from the bundle (literal clamps only for the reference's 18 / 20).  Every engine vs the oracle, C oracle vs numpy."""
+    add_bits <= acc_bits + 1 the adder clamp is no longer a provable no-op), wider ones never ON THESE FRAMES -- the kernels take the
+    widths from the bundle (literal clamps only for the reference's 18 / 20).  Every engine vs the oracle, C oracle vs numpy.
+    Saturation merely happens here; tests/test_accumulator_limits.py drives the sums to the clamp bounds themselves and, at (24, 26), past
+    the 2^22 limit of the biased accumulator."""
     from oracle import c_oracle as CO
     for kind in ("sesr_x2", "nrdm"):
         net = O.synth_net(kind, 11, hard=True)
