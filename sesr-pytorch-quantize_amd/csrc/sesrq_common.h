@@ -69,6 +69,16 @@ __host__ __device__ inline void f5_tr(int g, int &row, int &col) {
     col = g == 0 ? 0 : (g == 2 ? 2 : 4);
 }
 __host__ __device__ inline void f5_pt(int i, int &row, int &col) { row = i == 0 ? 0 : 1; col = i < 2 ? 0 : i - 1; }
+// tap of dword i of lane group g in K-chunk c (0, 1), or false where that slot carries no weight (host images: pack_mfma_frags, pack_f5_sparse)
+__host__ __device__ inline bool f5_tap(int c, int g, int i, int &ky, int &kx) {
+    if (c == 0) { ky = g; kx = i; return true; }
+    int tr_r, tr_c, pt_r, pt_c;
+    f5_tr(g, tr_r, tr_c);
+    f5_pt(i, pt_r, pt_c);
+    ky = tr_r + pt_r; kx = tr_c + pt_c;
+    const bool in_l = (ky == 4 && kx <= 4) || (kx == 4 && ky <= 4);   // taps not in K-chunk 0
+    return in_l && !(g == 2 && i == 1);                               // (4,2) belongs to lane group 0
+}
 
 // 5x5 per-PE chains (MFMA_H5 general image; kernels: mfma_h5_kernel).  A lane's 16 operand bytes per PE and K-chunk are TWO VERTICAL
 // PAIRS of pixels.  Round 4: every pair starts on an EVEN row of the tile, so that in the column-major planar LDS image
@@ -223,19 +233,32 @@ struct TrioArgs {
     TrioLayer l[3];
 };
 
+// A device allocation and its owner: move-only, freed with the object (a net's images die with the net, on every path).
+template <typename T>
+class DevBuf {
+    T *p_ = nullptr;
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    ~DevBuf() { if (p_) (void)hipFree(p_); }
+    T *get() const { return p_; }                 // NULL until upload() succeeded
+    bool upload(const void *src, size_t bytes) {  // allocate + copy, once per buffer; false = the device refused
+        return !p_ && hipMalloc((void **)&p_, bytes) == hipSuccess && hipMemcpy(p_, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    bool upload(const std::vector<int> &v) { return upload(v.data(), v.size() * sizeof(int)); }
+};
+
 struct LayerPlan {
     int k, ic, oc, ocp;
     bool general;            // per-PE accumulators + 18/20-bit clamps needed
     std::string engine;
-    int *d_wpk_general = nullptr;   // device
-    int *d_wpk_merged = nullptr;    // device
+    DevBuf<int> d_wpk_general, d_wpk_merged;
     int mfma_kind = MFMA_NONE;
-    int4 *d_afrag_general = nullptr; // device
-    int4 *d_afrag_merged = nullptr;  // device
-    int4 *d_afrag_pesplit = nullptr; // device: last layer with OC <= 4 (MFMA_H5P image), else NULL
-    int4 *d_afrag_sparse = nullptr;  // device: first layer, exactly one risky PE, 3 input channels: sparse hybrid images, else NULL
-    int4 *d_afrag_others = nullptr;  // device: exactly one risky PE: merged image with that PE's channels zeroed, else NULL
-    float2 *d_mn_oc = nullptr;       // device: per-output-channel ((float)M, 2^-n), per-channel layers only (they run on the dot4 kernels)
+    DevBuf<int4> d_afrag_general, d_afrag_merged;
+    DevBuf<int4> d_afrag_pesplit;    // last layer with OC <= 4 (MFMA_H5P image), else NULL
+    DevBuf<int4> d_afrag_sparse;     // first layer, exactly one risky PE, 3 input channels: sparse hybrid images, else NULL
+    DevBuf<int4> d_afrag_others;     // exactly one risky PE: merged image with that PE's channels zeroed, else NULL
+    DevBuf<float2> d_mn_oc;          // per-output-channel ((float)M, 2^-n), per-channel layers only (they run on the dot4 kernels)
     std::string engine_dot4, engine_mfma;
     ConvArgs base;           // constant fields prefilled
     // static saturation analysis (per layer)
@@ -299,7 +322,7 @@ struct sesrq_net {
     int reduced_forms = -1;             // sesrq_options.reduced_forms, resolved (never -1 after sesrq_create)
     float i8_in_scale = 0.f;            // > 0: int8 input frames are in this (scale, zero) domain of an upstream net
     int i8_in_zero = 0;
-    int *d_merge_lut = nullptr;         // device: 512-byte table of the residual merge (see TrioArgs::merge_lut)
+    sesrq::DevBuf<int> d_merge_lut;     // 512-byte table of the residual merge (see TrioArgs::merge_lut)
     std::vector<int> trio_len;          // trio_len[k] == 3: layers k..k+2 are eligible for the fused hidden trio
     int device = 0;
     int quan_bits = 8;          // activation / weight width b (sesrq_create_q), 2..8

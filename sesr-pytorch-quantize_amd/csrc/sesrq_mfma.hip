@@ -9,7 +9,7 @@
 //   lane l:  n (or m) = l & 15, g = l >> 4;  D: lane holds rows m = 4g..4g+3 of column n.
 //
 // The K order inside the instruction is irrelevant: A and B are packed with the same
-// (g, byte) -> (tap, channel) table (host: pack_mfma_frags in sesrq_api.hip).
+// (g, byte) -> (tap, channel) table (host: pack_mfma_frags in sesrq_create.hip).
 //
 //   merged  (load-time proof: no 18/20-bit saturation possible): a lane group = one tap,
 //           16 bytes = the 16 channels; rows are re-used across ky (register rotation).
@@ -1114,7 +1114,7 @@ static int select_mfma(const LayerPlan &lp, const ConvArgs &a, int src, int epi,
     const bool std_bits = a.acc_lo == -131072 && a.acc_hi == 131071 && a.add_lo == -524288 && a.add_hi == 524287;
     // ... and for a layer whose sums can leave the biased accumulator's range (LayerPlan::wide; forward_impl asks for per-PE sums then)
     p.mode = tap ? GEN_TAP : !general ? MERGED : (!std_bits || lp.wide) ? GEN_ANY : one_pe ? HYB : GEN_STD;
-    const bool pesplit = lp.d_afrag_pesplit && a.afrag == lp.d_afrag_pesplit;
+    const bool pesplit = lp.d_afrag_pesplit.get() && a.afrag == lp.d_afrag_pesplit.get();
     if (tap && pesplit) { set_error("mfma: the pe-split last-layer kernel has no PE taps"); return 1; }
     switch (lp.mfma_kind) {
         case MFMA_H3:

@@ -140,7 +140,7 @@ int forward_impl(const sesrq_net *net, const void *in, int in_dtype, void *out_q
             memset(&t, 0, sizeof(t));
             void *dst = (cur == bufA) ? bufB : bufA;
             t.in = cur; t.out = dst; t.rc_in = bufRC;
-            t.merge_lut = net->d_merge_lut;
+            t.merge_lut = net->d_merge_lut.get();
             t.N = N; t.H = H; t.W = W;
             t.wg_budget = net->wg_budget;
             t.allow = net->reduced_forms;
@@ -148,7 +148,7 @@ int forward_impl(const sesrq_net *net, const void *in, int in_dtype, void *out_q
             t.Mres = lp.base.Mres; t.shres = lp.base.shres; t.z_merge = lp.base.z_merge;
             for (int j = 0; j < 3; ++j) {
                 const LayerPlan &lj = net->layers[k + j];
-                t.l[j].afrag = lj.d_afrag_merged;
+                t.l[j].afrag = lj.d_afrag_merged.get();
                 t.l[j].Mf = lj.base.Mf; t.l[j].sh = lj.base.sh; t.l[j].z_next = lj.base.z_next; t.l[j].Md = lj.base.Md; t.l[j].Cd = lj.base.Cd; t.l[j].direct = lj.base.direct;
                 t.l[j].zlo = lj.base.relu ? fmaxf(lj.base.z_next, -128.f) : -128.f;
                 t.l[j].pad_next = net->layers[k + j + 1].base.pad_word;
@@ -169,11 +169,11 @@ int forward_impl(const sesrq_net *net, const void *in, int in_dtype, void *out_q
         // PE taps on the MFMA engine: the per-PE kernels write them themselves (GEN_TAP); the overflow counters, the quantised
         // input tap and the pe-split last layer (OC <= 4) stay with the dot4 kernels
         const bool mfma_ok = net->engine != SESRQ_ENGINE_DOT4 && lp.mfma_kind != MFMA_NONE && (k > 0 || net->fd.ok);
-        const bool tap_mfma = dbg && !taps->overflow && !q0tap && !ictap && mfma_ok && !lp.d_afrag_pesplit;
+        const bool tap_mfma = dbg && !taps->overflow && !q0tap && !ictap && mfma_ok && !lp.d_afrag_pesplit.get();
         const bool use_mfma = mfma_ok && (!dbg || tap_mfma) && !q0tap && !ictap;
         // per-PE sums + clamps; a layer whose sums can leave the biased range (LayerPlan::wide) has no merged MFMA kernel
         const bool general = lp.general || net->force_general || dbg || (lp.wide && use_mfma);
-        a.wpk = general ? lp.d_wpk_general : lp.d_wpk_merged;
+        a.wpk = (general ? lp.d_wpk_general : lp.d_wpk_merged).get();
         a.N = N; a.H = H; a.W = W;
         a.wg_budget = net->wg_budget;
         a.in = cur;
@@ -201,14 +201,14 @@ int forward_impl(const sesrq_net *net, const void *in, int in_dtype, void *out_q
         if (launch >= NL) { set_error("sesrq_forward: more launches than sesrq_launch_plan reports"); return 1; }
         if (ev) tl_kernel_events = KernelEvents{ev[2 * launch], ev[2 * launch + 1]};     // begin / end events of the next kernel
         if (use_mfma) {
-            a.afrag = general ? lp.d_afrag_general : lp.d_afrag_merged;
+            a.afrag = (general ? lp.d_afrag_general : lp.d_afrag_merged).get();
             // the hybrid (merged chain + the risky PE's chain) unless something forces the full per-PE path
             const bool one_pe = lp.hybrid && !net->force_general && !dbg;
             if (one_pe) {
-                a.afrag = lp.d_afrag_others; a.afrag2 = lp.d_afrag_general; a.risky_pe = __builtin_ctz(lp.risky_mask); a.afrag_sp = lp.d_afrag_sparse;
+                a.afrag = lp.d_afrag_others.get(); a.afrag2 = lp.d_afrag_general.get(); a.risky_pe = __builtin_ctz(lp.risky_mask); a.afrag_sp = lp.d_afrag_sparse.get();
                 a.risky_reg = lp.risky_reg;
             }
-            if (lp.d_afrag_pesplit) a.afrag = lp.d_afrag_pesplit;
+            if (lp.d_afrag_pesplit.get()) a.afrag = lp.d_afrag_pesplit.get();
             if (launch_mfma(lp, a, src, epi, general, st, one_pe, tap_mfma)) return 1;
         } else if (launch_dot4(lp, general, a, src, epi, st)) return 1;
         tl_kernel_events = KernelEvents{};

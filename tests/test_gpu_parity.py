@@ -265,6 +265,9 @@ def test_4k_input_frame_large_offsets():
     torch.cuda.empty_cache()
 
 
+LEAK_CYCLES = 200      # refused creates in test_error_conventions: the parent of the fix lost the whole net's images on each
+
+
 def test_error_conventions():
     net = O.synth_net("nrdm", 0)
     b = bundle_from_oracle(net)
@@ -292,6 +295,24 @@ def test_error_conventions():
     tiny.scale[0] = 1e-39
     with pytest.raises(ValueError, match="exact_div = 2"):
         sesrq.Engine(bundle_from_oracle(tiny), _dev(), reciprocal_division=True)
+    # ... and a refused create keeps nothing on the device: a run of refusals costs no more free device memory than as many
+    # create + destroy cycles of the same bundle (the refusal once came after every weight image was uploaded, and freed none)
+    tb = bundle_from_oracle(tiny)
+
+    def free_drop(n, **kw):
+        torch.cuda.synchronize()
+        before = torch.cuda.mem_get_info(_dev())[0]
+        for _ in range(n):
+            try:
+                sesrq.Engine(tb, _dev(), **kw).close()
+            except ValueError:
+                assert kw
+        torch.cuda.synchronize()
+        return before - torch.cuda.mem_get_info(_dev())[0]
+    free_drop(8)                                         # first use: the proof's cache entry, the runtime's own pools
+    kept, leaked = free_drop(LEAK_CYCLES), free_drop(LEAK_CYCLES, reciprocal_division=True)
+    print(f"free device memory lost over {LEAK_CYCLES} cycles: create + destroy {kept} B, refused create {leaked} B")
+    assert leaked <= kept
     et = sesrq.Engine(bundle_from_oracle(tiny), _dev())
     assert not et.fast_division_proven() and et.layer_engines()[0].startswith("dot4")
     x = rand_frame((1, 3, 9, 21), 2) * np.float32(2e-37)
