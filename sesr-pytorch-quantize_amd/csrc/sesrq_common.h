@@ -4,7 +4,9 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "sesrq.h"
@@ -57,6 +59,32 @@ inline int env_knob(const char *name, int dflt, int lo, int hi) {
     const int v = atoi(e);
     return (v < lo || v > hi) ? dflt : v;
 }
+
+// Kernel selection, one idiom for every family: a select_* function names the instance a launch runs as plain template-argument values,
+// a constexpr *_built predicate states which combinations the library builds (and so registers), and pick maps the one onto the other.
+// pick(f, Of<V...>{}, v, ...) calls f(std::integral_constant<int, V>...) with, per list, the member equal to its run-time value; false if
+// a value is in no list or f returns false (no such instance).  The lists' order decides the order of the kernels in the code object.
+template <int... V> struct Of {};
+template <int V, class F> static auto bind(F &f) { return [&f](auto... c) { return f(std::integral_constant<int, V>{}, c...); }; }
+template <class F> static bool pick(F &&f) { return f(); }
+template <class F, int... V, class... R> static bool pick(F &&f, Of<V...>, int v, R... r) { return ((v == V && pick(bind<V>(f), r...)) || ...); }
+
+// Persistent-run geometry of the MFMA kernels and the fused trio: every 64-column strip of the N images is cut into k vertical runs, k =
+// the workgroup slots the launch may fill (wg_budget, or 0 = slots_per_chip: one round of the chip) / (strips * N), at least 1 and at
+// most one run per unit (row tile / 8-row step).  chunk = units per run, rounded up; run y covers units [y * run_q + min(y, run_rem),
+// ... + run_q + (y < run_rem)): the host's division, so that the kernels' prologues do none.
+struct RunCut {
+    int k, chunk, run_q, run_rem;
+    unsigned inv_nx;      // ceil(2^32 / strips) for the kernels' block -> (strip, run) split, or 0 (grid too large: they divide)
+};
+inline RunCut cut_runs(int strips, int units, int N, int wg_budget, int slots_per_chip) {
+    const long long want = (wg_budget > 0 ? (long long)wg_budget : (long long)slots_per_chip) / ((long long)strips * N);
+    const long long k = std::max(1LL, std::min<long long>(want, units));
+    return {(int)k, (int)((units + k - 1) / k), (int)(units / k), (int)(units % k),
+            ((long long)strips * k < 65536 && strips < 65536) ? (unsigned)((0x100000000ULL + (unsigned)strips - 1) / (unsigned)strips) : 0u};
+}
+// the kernels address a frame's NHWC16 image (16 bytes per pixel) with 32-bit buffer offsets: H * W stays below 2^24 pixels
+inline bool frame_fits_32bit_offsets(int H, int W) { return (size_t)H * W * 16 < ((size_t)1 << 28); }
 
 enum Epi { EPI_MID = 0, EPI_PRERES = 1, EPI_LAST = 2 };
 
@@ -261,6 +289,7 @@ struct LayerPlan {
     DevBuf<float2> d_mn_oc;          // per-output-channel ((float)M, 2^-n), per-channel layers only (they run on the dot4 kernels)
     std::string engine_dot4, engine_mfma;
     ConvArgs base;           // constant fields prefilled
+    TrioArgs trio;           // first layer of a fused hidden trio (sesrq_net::trio_len): its launch's constant fields, prefilled (plan_trios)
     // static saturation analysis (per layer)
     long long worst_pe = 0, worst_sum = 0;
     int risky_mask = 0;      // PEs (bit p) whose 18-bit clamp can fire for some output channel
@@ -275,6 +304,12 @@ struct LayerPlan {
 };
 
 void set_error(const std::string &msg);
+// behind every launch_<who>: 1 (set_error) if the runtime refused the launch
+inline int check_launch(const char *who) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) set_error(std::string(who) + " launch failed: " + hipGetErrorString(e));
+    return e != hipSuccess;
+}
 
 // load-time proof (sesrq_verify.hip): can the 18-bit PE clamp / 20-bit adder clamp of this layer ever fire?
 bool saturation_free(const sesrq_layer_desc &d, int zc, int acc_bits, int add_bits, long long &worst_pe, long long &worst_sum, int &risky_mask,
@@ -291,14 +326,32 @@ struct WsLayout {
 };
 WsLayout ws_layout(const sesrq_net *net, int N, int H, int W);
 bool groupable(const sesrq_net *net);      // can frames of separate caller buffers be the images of one launch (ConvArgs::ft)?
-// ft != NULL: the launch's N = ft->n images are the frames ft->in[k] -> ft->out_q[k] / ft->out_f[k]
-int forward_impl(const sesrq_net *net, const void *in, int in_dtype, void *out_q, void *out_f, int N, int H, int W, void *workspace,
-                 size_t workspace_bytes, void *stream, const sesrq_taps *taps, hipEvent_t *ev, const FrameTable *ft = nullptr);
+// One call of the forward.  ft != NULL: the launch's N = ft->n images are the frames ft->in[k] -> ft->out_q[k] / ft->out_f[k] (in / out_q /
+// out_f = frame 0's, for the null checks and as the "this output exists" flags)
+struct Call {
+    const void *in;
+    int in_dtype;
+    void *out_q, *out_f;
+    int N, H, W;
+    const sesrq_taps *taps;
+    const FrameTable *ft;
+};
+int forward_impl(const sesrq_net *net, const Call &c, void *workspace, size_t workspace_bytes, void *stream, hipEvent_t *ev);
 
-// dot4 engine
-int launch_dot4(const LayerPlan &lp, bool general, const ConvArgs &a, int src, int epi, hipStream_t st);      // general: per-PE sums + clamps
-// mfma engine
-int launch_mfma(const LayerPlan &lp, const ConvArgs &a, int src, int epi, bool general, hipStream_t st, bool one_risky_pe = false, bool tap = false);
+// What one layer of one forward runs on (choose_layer, sesrq_plan.hip): the kernel family, the accumulation mode and the weight images.
+struct LayerChoice {
+    bool mfma;               // the MFMA kernels (else dot4): the net's engine, the layer's shape, and no tap that only the dot4 kernels write
+    bool general;            // per-PE sums + clamps: the saturation verdict, force_general, any debug tap, or a wide layer on the MFMA engine
+    bool one_pe;             // MFMA hybrid (merged chain + the one risky PE's chain): LayerPlan::hybrid unless force_general / a debug tap
+    bool tap;                // the per-PE MFMA kernels write the PE taps themselves (GEN_TAP)
+    int src, epi;            // Src: layer 0 by the frame's dtype (and the upstream domain), else NHWC16; Epi: by the layer's position
+    const int *wpk;          // dot4 image: general or merged
+    const int4 *afrag;       // MFMA image: general / merged; the hybrid: merged without the risky PE; OC <= 4 last layer: the pe-split image
+    const int4 *afrag2, *afrag_sp;      // hybrid only: the per-PE image / the first layer's sparse images (ConvArgs::afrag2, afrag_sp)
+    int risky_pe, risky_reg;            // hybrid only (ConvArgs::risky_pe, risky_reg)
+};
+int launch_dot4(const LayerPlan &lp, const LayerChoice &c, const ConvArgs &a, hipStream_t st);
+int launch_mfma(const LayerPlan &lp, const LayerChoice &c, const ConvArgs &a, hipStream_t st);
 int launch_trio(const TrioArgs &a, int epi_c, hipStream_t st);
 int launch_unpack_nhwc16(const void *nhwc, signed char *nchw, int N, int C, int H, int W, hipStream_t st);
 

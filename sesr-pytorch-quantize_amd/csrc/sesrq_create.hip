@@ -307,20 +307,7 @@ static void engine_name(LayerPlan &lp, bool per_channel, int quan_bits, bool on_
     lp.engine = on_dot4 ? lp.engine_dot4 : lp.engine_mfma;
 }
 
-// Step 5: fused hidden trios, greedy from the residual-merging layer L-2 backwards: three consecutive 3x3 16->16 layers whose
-// load-time proof allows the merged accumulation mode
-static std::vector<int> plan_trios(const std::vector<LayerPlan> &layers) {
-    const int L = (int)layers.size();
-    std::vector<int> trio_len(L, 0);
-    auto trio_ok = [&](int k) {
-        const LayerPlan &lp = layers[k];
-        return k >= 1 && k <= L - 2 && lp.mfma_kind == MFMA_H3 && !lp.general && !lp.wide && lp.ic == 16 && lp.oc == 16;
-    };
-    for (int k = L - 4; k >= 1 && trio_ok(k) && trio_ok(k + 1) && trio_ok(k + 2); k -= 3) trio_len[k] = 3;
-    return trio_len;
-}
-
-// Step 6: residual merge (myQL/quan_func.py:256-270): q4 = clamp8(rint(fl(fl(u * M_res) * 2^-n_res + zero[L-1]))) is a function of the
+// Step 5: residual merge (myQL/quan_func.py:256-270): q4 = clamp8(rint(fl(fl(u * M_res) * 2^-n_res + zero[L-1]))) is a function of the
 // 9-bit integer u = rc + ic + 256 alone: a 511-entry byte table (512 bytes = 128 dwords) replaces the second requant of the fused trio's
 // last phase (2 fma + add + cvt per value) by one LDS byte read.  Same fp32 operations, same order, as requant4<true> + round_pack.
 static std::vector<int> merge_table(uint32_t M_res, uint32_t n_res, int zero_merge) {
@@ -335,6 +322,39 @@ static std::vector<int> merge_table(uint32_t M_res, uint32_t n_res, int zero_mer
         bytes[u] = (unsigned char)(signed char)(int)nearbyintf(v);
     }
     return lut;
+}
+
+// Step 6: fused hidden trios, greedy from the residual-merging layer L-2 backwards: three consecutive 3x3 16->16 layers whose
+// load-time proof allows the merged accumulation mode.  trio_len[k] == 3 marks a trio's first layer; that layer's LayerPlan::trio gets
+// the constant fields of the trio's launch arguments (the forward adds in / out / rc_in / N / H / W, launch_trio_k the run geometry)
+static std::vector<int> plan_trios(sesrq_net &net) {
+    std::vector<LayerPlan> &layers = net.layers;
+    const int L = (int)layers.size();
+    std::vector<int> trio_len(L, 0);
+    auto trio_ok = [&](int k) {
+        const LayerPlan &lp = layers[k];
+        return k >= 1 && k <= L - 2 && lp.mfma_kind == MFMA_H3 && !lp.general && !lp.wide && lp.ic == 16 && lp.oc == 16;
+    };
+    for (int k = L - 4; k >= 1 && trio_ok(k) && trio_ok(k + 1) && trio_ok(k + 2); k -= 3) {
+        trio_len[k] = 3;
+        const ConvArgs &b0 = layers[k].base;
+        TrioArgs &t = layers[k].trio;
+        memset(&t, 0, sizeof(t));
+        t.merge_lut = net.d_merge_lut.get();
+        t.wg_budget = net.wg_budget;
+        t.allow = net.reduced_forms;
+        t.pad_in = b0.pad_word;
+        t.Mres = b0.Mres; t.shres = b0.shres; t.z_merge = b0.z_merge;
+        for (int j = 0; j < 3; ++j) {
+            const ConvArgs &b = layers[k + j].base;
+            TrioLayer &tl = t.l[j];
+            tl.afrag = layers[k + j].d_afrag_merged.get();
+            tl.Mf = b.Mf; tl.sh = b.sh; tl.z_next = b.z_next; tl.Md = b.Md; tl.Cd = b.Cd; tl.direct = b.direct;
+            tl.zlo = b.relu ? fmaxf(b.z_next, -128.f) : -128.f;
+            tl.pad_next = layers[k + j + 1].base.pad_word;
+        }
+    }
+    return trio_len;
 }
 
 }  // namespace sesrq
@@ -354,8 +374,9 @@ static bool build_layers(sesrq_net &net, const sesrq_net_desc *d) {
         engine_name(lp, l.M_oc != nullptr, net.quan_bits, net.engine == SESRQ_ENGINE_DOT4 || (k == 0 && !net.fd.ok));
     }
     net.layers[0].base.fd = net.fd;
-    net.trio_len = plan_trios(net.layers);
-    return net.d_merge_lut.upload(merge_table(d->M_res, d->n_res, d->zero[L - 1]));
+    if (!net.d_merge_lut.upload(merge_table(d->M_res, d->n_res, d->zero[L - 1]))) return false;
+    net.trio_len = plan_trios(net);
+    return true;
 }
 
 extern "C" {

@@ -235,42 +235,29 @@ int launch_unpack_nhwc16(const void *nhwc, signed char *nchw, int N, int C, int 
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
-template <int K, int IN_DW, bool GENERAL, int EPI, int OCP, int SRC>
-static void launch_one(const ConvArgs &a, hipStream_t st) {
-    dim3 grid((a.W + TW - 1) / TW, (a.H + TH - 1) / TH, a.N);
-    launch_kernel<conv_dot4_kernel<K, IN_DW, GENERAL, EPI, OCP, SRC>>(grid, dim3(256), 0, st, a);
+// The instances the library builds, per kernel size 3 / 5 and accumulation mode: the first layer (one dword per pixel: its frame in any of the
+// three forms) as a hidden layer, the 16-channel hidden layers, and the last layer at every padded width
+constexpr bool dot4_built(int k, int general, int in_dw, int epi, int ocp, int src) {
+    if ((k != 3 && k != 5) || in_dw != (src == SRC_NHWC16 ? 4 : 1)) return false;
+    if (src != SRC_NHWC16 || epi != EPI_LAST) return epi != EPI_LAST && (src == SRC_NHWC16 || epi == EPI_MID) && ocp == 16;
+    return ocp == 4 || ocp == 8 || ocp == 12 || ocp == 16;
 }
 
-template <int K, bool GENERAL>
-static int dispatch(const LayerPlan &lp, const ConvArgs &a, int src, int epi, hipStream_t st) {
-    if (src != SRC_NHWC16) {
-        if (epi != EPI_MID) { set_error("dot4: first layer must be a hidden layer"); return 1; }
-        if (src == SRC_F32) launch_one<K, 1, GENERAL, EPI_MID, 16, SRC_F32>(a, st);
-        else if (src == SRC_I8D) launch_one<K, 1, GENERAL, EPI_MID, 16, SRC_I8D>(a, st);
-        else launch_one<K, 1, GENERAL, EPI_MID, 16, SRC_I8>(a, st);
-        return 0;
-    }
-    if (epi == EPI_MID) { launch_one<K, 4, GENERAL, EPI_MID, 16, SRC_NHWC16>(a, st); return 0; }
-    if (epi == EPI_PRERES) { launch_one<K, 4, GENERAL, EPI_PRERES, 16, SRC_NHWC16>(a, st); return 0; }
-    switch (lp.ocp) {
-        case 4: launch_one<K, 4, GENERAL, EPI_LAST, 4, SRC_NHWC16>(a, st); return 0;
-        case 8: launch_one<K, 4, GENERAL, EPI_LAST, 8, SRC_NHWC16>(a, st); return 0;
-        case 12: launch_one<K, 4, GENERAL, EPI_LAST, 12, SRC_NHWC16>(a, st); return 0;
-        case 16: launch_one<K, 4, GENERAL, EPI_LAST, 16, SRC_NHWC16>(a, st); return 0;
-    }
-    set_error("dot4: unsupported padded channel count");
-    return 1;
-}
-
-int launch_dot4(const LayerPlan &lp, bool general, const ConvArgs &a, int src, int epi, hipStream_t st) {
-    int rc;
-    if (lp.k == 3) rc = general ? dispatch<3, true>(lp, a, src, epi, st) : dispatch<3, false>(lp, a, src, epi, st);
-    else if (lp.k == 5) rc = general ? dispatch<5, true>(lp, a, src, epi, st) : dispatch<5, false>(lp, a, src, epi, st);
-    else { set_error("dot4: kernel size must be 3 or 5"); return 1; }
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("dot4 launch failed: ") + hipGetErrorString(e)); return 1; }
-    return 0;
+int launch_dot4(const LayerPlan &lp, const LayerChoice &c, const ConvArgs &a, hipStream_t st) {
+    if (lp.k != 3 && lp.k != 5) { set_error("dot4: kernel size must be 3 or 5"); return 1; }
+    if (c.src != SRC_NHWC16 && c.epi != EPI_MID) { set_error("dot4: first layer must be a hidden layer"); return 1; }
+    const bool built = pick([&](auto K, auto G, auto E, auto P, auto S) {
+        constexpr int IN_DW = S == SRC_NHWC16 ? 4 : 1;
+        if constexpr (dot4_built(K, G, IN_DW, E, P, S)) {
+            dim3 grid((a.W + TW - 1) / TW, (a.H + TH - 1) / TH, a.N);
+            launch_kernel<conv_dot4_kernel<K, IN_DW, G == 1, E, P, S>>(grid, dim3(256), 0, st, a);
+            return true;
+        } else return false;
+    }, Of<5, 3>{}, lp.k, Of<0, 1>{}, (int)c.general, Of<EPI_LAST, EPI_PRERES, EPI_MID>{}, c.epi, Of<16, 12, 8, 4>{}, c.epi == EPI_LAST ? lp.ocp : 16,
+       Of<SRC_NHWC16, SRC_I8, SRC_I8D, SRC_F32>{}, c.src);
+    // kernel size, mode, position and frame form are covered above or complete: the one way to get here is a last layer's lp.ocp
+    if (!built) { set_error("dot4: unsupported padded channel count"); return 1; }
+    return check_launch("dot4");
 }
 
 }  // namespace sesrq

@@ -1067,15 +1067,10 @@ static void launch(ConvArgs a, hipStream_t st, int tile_h = MTH) {
         int b = 0;
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, KERN, 256, 0) == hipSuccess && b >= 1 ? b : 2;
     }();
-    const int num_cu = device_cu_count();
     const int strips = (a.W + MTW - 1) / MTW, row_tiles = (a.H + tile_h - 1) / tile_h;
-    long long k = (a.wg_budget > 0 ? (long long)a.wg_budget : (long long)blocks_per_cu * num_cu) / ((long long)strips * a.N);
-    k = std::max(1LL, std::min<long long>(k, row_tiles));
-    a.chunk_tiles = (int)((row_tiles + k - 1) / k);
-    a.run_q = (int)(row_tiles / k);
-    a.run_rem = (int)(row_tiles % k);
-    a.inv_nx = ((long long)strips * k < 65536 && strips < 65536) ? (unsigned)((0x100000000ULL + (unsigned)strips - 1) / (unsigned)strips) : 0u;
-    dim3 grid(strips, (int)k, a.N);
+    const RunCut c = cut_runs(strips, row_tiles, a.N, a.wg_budget, blocks_per_cu * device_cu_count());
+    a.chunk_tiles = c.chunk; a.run_q = c.run_q; a.run_rem = c.run_rem; a.inv_nx = c.inv_nx;
+    dim3 grid(strips, c.k, a.N);
     launch_kernel<KERN>(grid, dim3(256), 0, st, a);
 }
 
@@ -1105,28 +1100,28 @@ constexpr bool h5_built(int m, int e, int fast, int nv, int outf) {
 constexpr bool f5_built(int m, int nch) { return m == GEN_STD || m == GEN_ANY || (m == GEN_TAP && nch == 4); }
 constexpr bool f5_w4_built(int m, int nch, int rr) { return m == HYBS ? nch == 3 : rr == 4 && (m == MERGED || (m == HYB && nch != 3)); }
 
-// Which kernel a launch runs.  general / one_pe / tap: forward_impl's per-call decisions (per-PE sums; the one-risky-PE hybrid applies;
-// PE taps).  Returns 1 (set_error) where no MFMA kernel fits.
-static int select_mfma(const LayerPlan &lp, const ConvArgs &a, int src, int epi, bool general, bool one_pe, bool tap, Pick &p) {
+// Which kernel a launch runs.  c: choose_layer's per-call decisions (per-PE sums; the one-risky-PE hybrid applies; PE taps).  Returns 1
+// (set_error) where no MFMA kernel fits.
+static int select_mfma(const LayerPlan &lp, const LayerChoice &c, const ConvArgs &a, Pick &p) {
     p = Pick{};
-    p.epi = epi;
+    p.epi = c.epi;
     // the clamp bounds as literals (GEN_STD, HYB) for the reference's 18 / 20-bit widths, as arguments (GEN_ANY) for any other
     const bool std_bits = a.acc_lo == -131072 && a.acc_hi == 131071 && a.add_lo == -524288 && a.add_hi == 524287;
-    // ... and for a layer whose sums can leave the biased accumulator's range (LayerPlan::wide; forward_impl asks for per-PE sums then)
-    p.mode = tap ? GEN_TAP : !general ? MERGED : (!std_bits || lp.wide) ? GEN_ANY : one_pe ? HYB : GEN_STD;
+    // ... and for a layer whose sums can leave the biased accumulator's range (LayerPlan::wide; choose_layer asks for per-PE sums then)
+    p.mode = c.tap ? GEN_TAP : !c.general ? MERGED : (!std_bits || lp.wide) ? GEN_ANY : c.one_pe ? HYB : GEN_STD;
     const bool pesplit = lp.d_afrag_pesplit.get() && a.afrag == lp.d_afrag_pesplit.get();
-    if (tap && pesplit) { set_error("mfma: the pe-split last-layer kernel has no PE taps"); return 1; }
+    if (c.tap && pesplit) { set_error("mfma: the pe-split last-layer kernel has no PE taps"); return 1; }
     switch (lp.mfma_kind) {
         case MFMA_H3:
-            if (epi == EPI_LAST) { set_error("mfma: 3x3 last layer not supported"); return 1; }
+            if (c.epi == EPI_LAST) { set_error("mfma: 3x3 last layer not supported"); return 1; }
             p.fam = FAM_H3;
             return 0;
         case MFMA_F5:
             // merged and hybrid: 4 waves per SIMD (mfma_f5_kernel_w4); the per-PE forms take the registers they ask for
             p.fam = (p.mode == MERGED || p.mode == HYB) ? FAM_F5_W4 : FAM_F5;
-            p.src = (src == SRC_F32 || src == SRC_I8D) ? src : SRC_I8;
+            p.src = (c.src == SRC_F32 || c.src == SRC_I8D) ? c.src : SRC_I8;
             p.rc = a.rc_out != nullptr;
-            p.nch = (a.ic == 1 || a.ic == 3) && !tap ? a.ic : 4;      // 2 or 4 channels, and every tap kernel: the 4-channel form
+            p.nch = (a.ic == 1 || a.ic == 3) && !c.tap ? a.ic : 4;      // 2 or 4 channels, and every tap kernel: the 4-channel form
             if (p.mode == HYB && p.nch == 3) {      // 3 channels: always the sparse MFMA (sesrq_create packs its image), by the register to clamp
                 if (!a.afrag_sp) { set_error("mfma: hybrid 3-channel first layer without its sparse weight image"); return 1; }
                 p.mode = HYBS;
@@ -1135,14 +1130,14 @@ static int select_mfma(const LayerPlan &lp, const ConvArgs &a, int src, int epi,
             return 0;
         case MFMA_H5:
             p.fam = FAM_H5;
-            if (epi != EPI_LAST) return 0;
+            if (c.epi != EPI_LAST) return 0;
             if (pesplit) {      // OC <= 4: its one chain already yields the four clamped PE sums, so the hybrid runs the GEN_STD kernel
                 p.fam = FAM_H5P;
                 if (p.mode == HYB) p.mode = GEN_STD;
                 return 0;
             }
             p.nv = last_nv(a.oc);      // real rows per lane group (must match pack_mfma_frags)
-            if (tap) return 0;
+            if (c.tap) return 0;
             {   // FAST = the width of the PixelShuffle byte runs (the x2 pair map; 16 rows at x2 / x4) + 10 x the one-fma requant form;
                 // OUTF = the fp32 frame alone (1), with the x2 anchor add (2: the pair map of a 16-channel layer only)
                 const bool pair = last_pairmap(a.oc, a.ps);
@@ -1158,13 +1153,6 @@ static int select_mfma(const LayerPlan &lp, const ConvArgs &a, int src, int epi,
         default: set_error("mfma: layer shape not supported by the MFMA engine"); return 1;
     }
 }
-
-// pick(f, Of<V...>{}, v, ...) calls f(std::integral_constant<int, V>...) with, per list, the member equal to its run-time value; false if
-// a value is in no list or f returns false (no such instance)
-template <int... V> struct Of {};
-template <int V, class F> static auto bind(F &f) { return [&f](auto... c) { return f(std::integral_constant<int, V>{}, c...); }; }
-template <class F> static bool pick(F &&f) { return f(); }
-template <class F, int... V, class... R> static bool pick(F &&f, Of<V...>, int v, R... r) { return ((v == V && pick(bind<V>(f), r...)) || ...); }
 
 static bool dispatch_mfma(const Pick &p, const ConvArgs &a, hipStream_t st) {
     using Modes = Of<MERGED, GEN_STD, GEN_ANY, HYB, GEN_TAP, HYBS>;
@@ -1196,19 +1184,19 @@ static bool dispatch_mfma(const Pick &p, const ConvArgs &a, hipStream_t st) {
     return false;
 }
 
-int launch_mfma(const LayerPlan &lp, const ConvArgs &a_in, int src, int epi, bool general, hipStream_t st, bool one_risky_pe, bool tap) {
+int launch_mfma(const LayerPlan &lp, const LayerChoice &c, const ConvArgs &a_in, hipStream_t st) {
+#ifndef SESRQ_STAMPS
+    const ConvArgs &a = a_in;
+#else
     ConvArgs a = a_in;
-#ifdef SESRQ_STAMPS
     if (!g_stampbuf) { (void)hipMalloc((void **)&g_stampbuf, 1 << 22); (void)hipMemset(g_stampbuf, 0, 1 << 22); }
-    if (epi == (getenv("SESRQ_STAMP_EPI") ? atoi(getenv("SESRQ_STAMP_EPI")) : 0) && lp.mfma_kind == (getenv("SESRQ_STAMP_KIND") ? atoi(getenv("SESRQ_STAMP_KIND")) : MFMA_H3)) a.dbg_pe = g_stampbuf;
+    if (c.epi == (getenv("SESRQ_STAMP_EPI") ? atoi(getenv("SESRQ_STAMP_EPI")) : 0) && lp.mfma_kind == (getenv("SESRQ_STAMP_KIND") ? atoi(getenv("SESRQ_STAMP_KIND")) : MFMA_H3)) a.dbg_pe = g_stampbuf;
 #endif
-    if ((size_t)a.H * a.W * 16 >= ((size_t)1 << 28)) { set_error("mfma: frame too large for 32-bit buffer offsets (H*W must stay below 2^24 pixels)"); return 1; }
+    if (!frame_fits_32bit_offsets(a.H, a.W)) { set_error("mfma: frame too large for 32-bit buffer offsets (H*W must stay below 2^24 pixels)"); return 1; }
     Pick p;
-    if (select_mfma(lp, a, src, epi, general, one_risky_pe, tap, p)) return 1;
+    if (select_mfma(lp, c, a, p)) return 1;
     if (!dispatch_mfma(p, a, st)) { set_error("mfma: no kernel instance for the selected template arguments"); return 1; }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("mfma launch failed: ") + hipGetErrorString(e)); return 1; }
-    return 0;
+    return check_launch("mfma");
 }
 
 }  // namespace sesrq

@@ -97,121 +97,133 @@ size_t sesrq_workspace_bytes(const sesrq_net *net, int N, int H, int W) {
 
 namespace sesrq {
 
-// ft != NULL: the launch's N = ft->n images are the frames ft->in[k] -> ft->out_q[k] / ft->out_f[k] (in / out_q / out_f = frame 0's,
-// for the null checks and as the "this output exists" flags)
-int forward_impl(const sesrq_net *net, const void *in, int in_dtype, void *out_q, void *out_f, int N, int H, int W, void *workspace,
-                 size_t workspace_bytes, void *stream, const sesrq_taps *taps, hipEvent_t *ev, const FrameTable *ft) {
-    if (!net || !in || !workspace) { set_error("sesrq_forward: null argument"); return 1; }
-    if (ft && (taps || !groupable(net) || ft->n != N || N > SESRQ_GROUP_MAX)) { set_error("sesrq_forward: frame table not applicable"); return 1; }
-    if (!out_q && !out_f) { set_error("sesrq_forward: both outputs are NULL"); return 1; }
-    if (net->anchor_add && in_dtype != SESRQ_F32) { set_error("sesrq_forward: anchor add needs the fp32 input frame"); return 1; }
-    if (N < 1 || H < 1 || W < 1) { set_error("sesrq_forward: N, H, W must be positive"); return 1; }
-    if ((size_t)N * H * W > (size_t)1 << 31) { set_error("sesrq_forward: frame batch too large (N*H*W > 2^31)"); return 1; }
-    if (in_dtype != SESRQ_F32 && in_dtype != SESRQ_I8) { set_error("sesrq_forward: in_dtype must be SESRQ_F32 or SESRQ_I8"); return 1; }
+// Step 1: the checks of the call's arguments, before anything is enqueued; wl = the workspace layout they needed
+static int validate_forward(const sesrq_net *net, const Call &c, void *workspace, size_t workspace_bytes, WsLayout &wl) {
+    if (!net || !c.in || !workspace) { set_error("sesrq_forward: null argument"); return 1; }
+    if (c.ft && (c.taps || !groupable(net) || c.ft->n != c.N || c.N > SESRQ_GROUP_MAX)) { set_error("sesrq_forward: frame table not applicable"); return 1; }
+    if (!c.out_q && !c.out_f) { set_error("sesrq_forward: both outputs are NULL"); return 1; }
+    if (net->anchor_add && c.in_dtype != SESRQ_F32) { set_error("sesrq_forward: anchor add needs the fp32 input frame"); return 1; }
+    if (c.N < 1 || c.H < 1 || c.W < 1) { set_error("sesrq_forward: N, H, W must be positive"); return 1; }
+    if ((size_t)c.N * c.H * c.W > (size_t)1 << 31) { set_error("sesrq_forward: frame batch too large (N*H*W > 2^31)"); return 1; }
+    if (c.in_dtype != SESRQ_F32 && c.in_dtype != SESRQ_I8) { set_error("sesrq_forward: in_dtype must be SESRQ_F32 or SESRQ_I8"); return 1; }
     if ((uintptr_t)workspace & 15) { set_error("sesrq_forward: workspace must be 16-byte aligned"); return 1; }
-    const WsLayout wl = ws_layout(net, N, H, W);
+    wl = ws_layout(net, c.N, c.H, c.W);
     if (workspace_bytes < wl.total) { set_error("sesrq_forward: workspace too small (see sesrq_workspace_bytes)"); return 1; }
-    {   // the net's device copy of the bundle lives on net->device: a launch from another current device would read foreign pointers
-        int dev = -1;
-        if (hipGetDevice(&dev) != hipSuccess || dev != net->device) {
-            set_error("sesrq_forward: the current HIP device (" + std::to_string(dev) + ") is not the device the net was created on (" +
-                      std::to_string(net->device) + ")");
-            return 1;
-        }
+    // the net's device copy of the bundle lives on net->device: a launch from another current device would read foreign pointers
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != net->device) {
+        set_error("sesrq_forward: the current HIP device (" + std::to_string(dev) + ") is not the device the net was created on (" +
+                  std::to_string(net->device) + ")");
+        return 1;
     }
-    hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace;
+    return 0;
+}
+
+// Step 2: the activation tensors inside the caller's workspace.  S = layer 0's output (kept for the residual), A / B = the hidden layers'
+// ping-pong, RC = the residual operand: S itself unless layer 0 writes a separate one (sesrq_net::rc_separate)
+struct WsBuffers {
+    void *S, *A, *B, *RC;
+    WsBuffers(const sesrq_net *net, void *workspace, const WsLayout &wl)
+        : S((char *)workspace + wl.off_s), A((char *)workspace + wl.off_a), B((char *)workspace + wl.off_b),
+          RC(net->rc_separate ? (void *)((char *)workspace + wl.off_rc) : S) {}
+    void *next(const void *cur) const { return cur == A ? B : A; }      // where a hidden layer reading `cur` writes
+};
+
+// Step 3, per layer that runs on its own: kernel family, accumulation mode and weight images.  Pure: no HIP call, nothing written.
+static LayerChoice choose_layer(const sesrq_net *net, int k, const sesrq_taps *taps, int in_dtype) {
+    const LayerPlan &lp = net->layers[k];
     const int L = net->L;
+    const bool pesplit = lp.d_afrag_pesplit.get() != nullptr;      // last layer with OC <= 4: the MFMA_H5P image exists
+    // any debug tap of this layer's PE sums; the taps only the dot4 kernels write: the overflow counters, layer 0's quantised input
+    // (input.0.pt) and un-rounded output (shortcut_tensor.pt), the merging layer's ic (input.4.spcial.pt)
+    const bool dbg = taps && (taps->pe_out[k] || taps->pe_add[k] || taps->overflow);
+    const bool dot4_tap = taps && (taps->overflow || (k == 0 && (taps->act[0] || taps->shortcut)) || (k == L - 2 && taps->ic));
+    // the layer has an MFMA kernel: the engine option, its shape, and for the first layer the proven division form
+    const bool mfma_ok = net->engine != SESRQ_ENGINE_DOT4 && lp.mfma_kind != MFMA_NONE && (k > 0 || net->fd.ok);
+    LayerChoice c{};
+    c.tap = dbg && !dot4_tap && mfma_ok && !pesplit;      // PE taps the per-PE MFMA kernels write themselves; the pe-split kernel has none
+    c.mfma = mfma_ok && !dot4_tap && (!dbg || c.tap);     // every other tapped layer runs on the dot4 kernels
+    c.general = lp.general || net->force_general || dbg || (lp.wide && c.mfma);      // a wide layer has no merged MFMA kernel (LayerPlan::wide)
+    c.one_pe = c.mfma && lp.hybrid && !net->force_general && !dbg;      // the hybrid unless something forces the full per-PE path
+    c.src = k > 0 ? SRC_NHWC16 : in_dtype == SESRQ_F32 ? SRC_F32 : net->i8_in_scale > 0.f ? SRC_I8D : SRC_I8;      // I8D: an upstream net's domain
+    c.epi = k == L - 1 ? EPI_LAST : k == L - 2 ? EPI_PRERES : EPI_MID;
+    c.wpk = (c.general ? lp.d_wpk_general : lp.d_wpk_merged).get();
+    if (!c.mfma) return c;
+    c.afrag = pesplit ? lp.d_afrag_pesplit.get() : c.one_pe ? lp.d_afrag_others.get() : (c.general ? lp.d_afrag_general : lp.d_afrag_merged).get();
+    if (c.one_pe) {
+        c.afrag2 = lp.d_afrag_general.get(); c.afrag_sp = lp.d_afrag_sparse.get();
+        c.risky_pe = __builtin_ctz(lp.risky_mask); c.risky_reg = lp.risky_reg;
+    }
+    return c;
+}
+
+// Step 4, per layer: the per-call fields of its arguments (LayerPlan::base holds the constant ones).  cur -> dst: the layer's activations
+static ConvArgs fill_conv_args(const sesrq_net *net, int k, const LayerChoice &ch, const Call &c, const WsBuffers &buf, const void *cur, void *dst) {
+    const int L = net->L;
+    ConvArgs a = net->layers[k].base;
+    a.wpk = ch.wpk; a.afrag = ch.afrag; a.afrag2 = ch.afrag2; a.afrag_sp = ch.afrag_sp; a.risky_pe = ch.risky_pe; a.risky_reg = ch.risky_reg;
+    a.N = c.N; a.H = c.H; a.W = c.W;
+    a.wg_budget = net->wg_budget;
+    a.s_prev = net->i8_in_scale; a.z_prev = (float)net->i8_in_zero;
+    a.in = cur; a.out = dst;
+    a.rc_in = buf.RC;
+    if (k == 0 && net->rc_separate) a.rc_out = buf.RC;
+    a.out_q = c.out_q; a.out_f = (float *)c.out_f;
+    a.anchor = (net->anchor_add && c.in_dtype == SESRQ_F32) ? (const float *)c.in : nullptr;
+    if (c.ft && (k == 0 || k == L - 1)) a.ft = *c.ft;
+    if (const sesrq_taps *t = c.taps) {
+        a.dbg_pe = (int *)t->pe_out[k];
+        a.dbg_add = (int *)t->pe_add[k];
+        a.dbg_ovf = t->overflow ? (int *)t->overflow + 2 * k : nullptr;
+        if (k == L - 2) a.dbg_ic = (signed char *)t->ic;
+        if (k == 0) { a.dbg_q0 = (signed char *)t->act[0]; a.dbg_t = (float *)t->shortcut; }
+    }
+    return a;
+}
+
+// One kernel launch of the forward: refuses a launch sesrq_launch_plan does not announce (ev[] holds two events per announced launch),
+// and makes ev's pair the begin / end events of exactly this launch (launch_kernel reads tl_kernel_events) -- cleared on every way out
+struct LaunchSlot {
+    const bool ok;
+    LaunchSlot(int launch, int announced, hipEvent_t *ev) : ok(launch < announced) {
+        if (!ok) set_error("sesrq_forward: more launches than sesrq_launch_plan reports");
+        else if (ev) tl_kernel_events = KernelEvents{ev[2 * launch], ev[2 * launch + 1]};
+    }
+    ~LaunchSlot() { tl_kernel_events = KernelEvents{}; }
+};
+
+int forward_impl(const sesrq_net *net, const Call &c, void *workspace, size_t workspace_bytes, void *stream, hipEvent_t *ev) {
+    WsLayout wl;
+    if (validate_forward(net, c, workspace, workspace_bytes, wl)) return 1;
+    const sesrq_taps *taps = c.taps;
+    const int L = net->L, N = c.N, H = c.H, W = c.W;
+    hipStream_t st = (hipStream_t)stream;
     if (taps && taps->overflow && hipMemsetAsync(taps->overflow, 0, (size_t)L * 2 * sizeof(int), st) != hipSuccess) {
         set_error("sesrq_forward: clearing the overflow counters failed"); return 1;
     }
-    // buffers: S = layer-0 output (kept for the residual), A/B ping-pong, RC optional
-    void *bufS = ws + wl.off_s, *bufA = ws + wl.off_a, *bufB = ws + wl.off_b;
-    void *bufRC = net->rc_separate ? (void *)(ws + wl.off_rc) : bufS;
-    const void *cur = in;
-    int launch = 0;
-    const int NL = taps ? L : sesrq_launch_plan(net, nullptr, nullptr);       // launches this forward may issue (ev[] holds 2 per launch)
-    struct ClearKernelEvents { ~ClearKernelEvents() { tl_kernel_events = KernelEvents{}; } } clear_on_any_exit;
-    for (int k = 0; k < L; ++launch) {
-        const LayerPlan &lp = net->layers[k];
+    const WsBuffers buf(net, workspace, wl);
+    const int announced = taps ? L : sesrq_launch_plan(net, nullptr, nullptr);
+    const void *cur = c.in;
+    for (int k = 0, launch = 0; k < L; ++launch) {
         if (trio_active(net, taps) && net->trio_len[k] == 3) {
             // ---- fused hidden trio: layers k, k+1, k+2 in one launch (sesrq_trio.hip)
-            TrioArgs t;
-            memset(&t, 0, sizeof(t));
-            void *dst = (cur == bufA) ? bufB : bufA;
-            t.in = cur; t.out = dst; t.rc_in = bufRC;
-            t.merge_lut = net->d_merge_lut.get();
+            TrioArgs t = net->layers[k].trio;
+            t.in = cur; t.out = buf.next(cur); t.rc_in = buf.RC;
             t.N = N; t.H = H; t.W = W;
-            t.wg_budget = net->wg_budget;
-            t.allow = net->reduced_forms;
-            t.pad_in = lp.base.pad_word;
-            t.Mres = lp.base.Mres; t.shres = lp.base.shres; t.z_merge = lp.base.z_merge;
-            for (int j = 0; j < 3; ++j) {
-                const LayerPlan &lj = net->layers[k + j];
-                t.l[j].afrag = lj.d_afrag_merged.get();
-                t.l[j].Mf = lj.base.Mf; t.l[j].sh = lj.base.sh; t.l[j].z_next = lj.base.z_next; t.l[j].Md = lj.base.Md; t.l[j].Cd = lj.base.Cd; t.l[j].direct = lj.base.direct;
-                t.l[j].zlo = lj.base.relu ? fmaxf(lj.base.z_next, -128.f) : -128.f;
-                t.l[j].pad_next = net->layers[k + j + 1].base.pad_word;
-            }
-            if (launch >= NL) { set_error("sesrq_forward: more launches than sesrq_launch_plan reports"); return 1; }
-            if (ev) tl_kernel_events = KernelEvents{ev[2 * launch], ev[2 * launch + 1]};     // begin / end events of the next kernel
-            if (launch_trio(t, (k + 2 == L - 2) ? EPI_PRERES : EPI_MID, st)) return 1;
-            tl_kernel_events = KernelEvents{};
-            cur = dst;
+            LaunchSlot slot(launch, announced, ev);
+            if (!slot.ok || launch_trio(t, (k + 2 == L - 2) ? EPI_PRERES : EPI_MID, st)) return 1;
+            cur = t.out;
             k += 3;
             continue;
         }
-        ConvArgs a = lp.base;
-        const bool dbg = taps && (taps->pe_out[k] || taps->pe_add[k] || taps->overflow);
-        // the quantised input of layer 0 (input.0.pt) is a tap of the dot4 kernel: with it layer 0 runs there
-        const bool q0tap = taps && k == 0 && (taps->act[0] || taps->shortcut);      // ... and so is shortcut_tensor.pt (layer 0's un-rounded output)
-        const bool ictap = taps && k == L - 2 && taps->ic;                          // input.4.spcial.pt: the merging layer's ic, dot4 kernel too
-        // PE taps on the MFMA engine: the per-PE kernels write them themselves (GEN_TAP); the overflow counters, the quantised
-        // input tap and the pe-split last layer (OC <= 4) stay with the dot4 kernels
-        const bool mfma_ok = net->engine != SESRQ_ENGINE_DOT4 && lp.mfma_kind != MFMA_NONE && (k > 0 || net->fd.ok);
-        const bool tap_mfma = dbg && !taps->overflow && !q0tap && !ictap && mfma_ok && !lp.d_afrag_pesplit.get();
-        const bool use_mfma = mfma_ok && (!dbg || tap_mfma) && !q0tap && !ictap;
-        // per-PE sums + clamps; a layer whose sums can leave the biased range (LayerPlan::wide) has no merged MFMA kernel
-        const bool general = lp.general || net->force_general || dbg || (lp.wide && use_mfma);
-        a.wpk = (general ? lp.d_wpk_general : lp.d_wpk_merged).get();
-        a.N = N; a.H = H; a.W = W;
-        a.wg_budget = net->wg_budget;
-        a.in = cur;
-        int src = (k == 0) ? (in_dtype == SESRQ_F32 ? SRC_F32 : (net->i8_in_scale > 0.f ? SRC_I8D : SRC_I8)) : SRC_NHWC16;
-        a.s_prev = net->i8_in_scale; a.z_prev = (float)net->i8_in_zero;
-        int epi = (k == L - 1) ? EPI_LAST : (k == L - 2 ? EPI_PRERES : EPI_MID);
-        void *dst = nullptr;
-        if (k == 0) { dst = bufS; a.rc_out = net->rc_separate ? bufRC : nullptr; }
-        else if (k < L - 1) dst = (cur == bufA) ? bufB : bufA;
-        a.out = dst;
-        a.rc_in = bufRC;
-        a.out_q = out_q; a.out_f = (float *)out_f;
-        a.anchor = (net->anchor_add && in_dtype == SESRQ_F32) ? (const float *)in : nullptr;
-        if (ft && (k == 0 || k == L - 1)) a.ft = *ft;
-        if (taps) {
-            a.dbg_pe = (int *)taps->pe_out[k];
-            a.dbg_add = (int *)taps->pe_add[k];
-            a.dbg_ovf = taps->overflow ? (int *)taps->overflow + 2 * k : nullptr;
-            if (k == L - 2) a.dbg_ic = (signed char *)taps->ic;
-            if (k == 0) { a.dbg_q0 = (signed char *)taps->act[0]; a.dbg_t = (float *)taps->shortcut; }
-            else if (taps->act[k] && launch_unpack_nhwc16(cur, (signed char *)taps->act[k], N, lp.ic, H, W, st)) {
-                set_error("sesrq_forward: debug unpack launch failed"); return 1;
-            }
+        const LayerChoice ch = choose_layer(net, k, taps, c.in_dtype);
+        void *dst = k == 0 ? buf.S : k < L - 1 ? buf.next(cur) : nullptr;      // the last layer writes the caller's frames
+        const ConvArgs a = fill_conv_args(net, k, ch, c, buf, cur, dst);
+        if (taps && k > 0 && taps->act[k] && launch_unpack_nhwc16(cur, (signed char *)taps->act[k], N, net->layers[k].ic, H, W, st)) {
+            set_error("sesrq_forward: debug unpack launch failed"); return 1;
         }
-        if (launch >= NL) { set_error("sesrq_forward: more launches than sesrq_launch_plan reports"); return 1; }
-        if (ev) tl_kernel_events = KernelEvents{ev[2 * launch], ev[2 * launch + 1]};     // begin / end events of the next kernel
-        if (use_mfma) {
-            a.afrag = (general ? lp.d_afrag_general : lp.d_afrag_merged).get();
-            // the hybrid (merged chain + the risky PE's chain) unless something forces the full per-PE path
-            const bool one_pe = lp.hybrid && !net->force_general && !dbg;
-            if (one_pe) {
-                a.afrag = lp.d_afrag_others.get(); a.afrag2 = lp.d_afrag_general.get(); a.risky_pe = __builtin_ctz(lp.risky_mask); a.afrag_sp = lp.d_afrag_sparse.get();
-                a.risky_reg = lp.risky_reg;
-            }
-            if (lp.d_afrag_pesplit.get()) a.afrag = lp.d_afrag_pesplit.get();
-            if (launch_mfma(lp, a, src, epi, general, st, one_pe, tap_mfma)) return 1;
-        } else if (launch_dot4(lp, general, a, src, epi, st)) return 1;
-        tl_kernel_events = KernelEvents{};
+        LaunchSlot slot(launch, announced, ev);
+        if (!slot.ok || (ch.mfma ? launch_mfma(net->layers[k], ch, a, st) : launch_dot4(net->layers[k], ch, a, st))) return 1;
         cur = dst;
         ++k;
     }
@@ -224,12 +236,12 @@ extern "C" {
 
 int sesrq_forward_debug(const sesrq_net *net, const void *in, int in_dtype, void *out_q, void *out_f, int N, int H, int W,
                         void *workspace, size_t workspace_bytes, void *stream, const sesrq_taps *taps) {
-    return forward_impl(net, in, in_dtype, out_q, out_f, N, H, W, workspace, workspace_bytes, stream, taps, nullptr);
+    return forward_impl(net, {in, in_dtype, out_q, out_f, N, H, W, taps, nullptr}, workspace, workspace_bytes, stream, nullptr);
 }
 
 int sesrq_forward(const sesrq_net *net, const void *in, int in_dtype, void *out_q, void *out_f, int N, int H, int W,
                   void *workspace, size_t workspace_bytes, void *stream) {
-    return forward_impl(net, in, in_dtype, out_q, out_f, N, H, W, workspace, workspace_bytes, stream, nullptr, nullptr);
+    return forward_impl(net, {in, in_dtype, out_q, out_f, N, H, W, nullptr, nullptr}, workspace, workspace_bytes, stream, nullptr);
 }
 
 int sesrq_forward_timed(const sesrq_net *net, const void *in, int in_dtype, void *out_q, void *out_f, int N, int H, int W,
@@ -241,8 +253,7 @@ int sesrq_forward_timed(const sesrq_net *net, const void *in, int in_dtype, void
     for (auto &e : ev)
         if (hipEventCreate(&e) != hipSuccess) { set_error("sesrq_forward_timed: hipEventCreate failed"); e = nullptr; rc = 1; break; }
     for (int it = 0; it < iters && !rc; ++it)
-        rc = forward_impl(net, in, in_dtype, out_q, out_f, N, H, W, workspace, workspace_bytes, stream, nullptr,
-                          ev.data() + (size_t)2 * NL * it);
+        rc = forward_impl(net, {in, in_dtype, out_q, out_f, N, H, W, nullptr, nullptr}, workspace, workspace_bytes, stream, ev.data() + (size_t)2 * NL * it);
     if (!rc && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) { set_error("hipStreamSynchronize failed"); rc = 1; }
     if (!rc) {
         for (int k = 0; k < NL; ++k) launch_ms[k] = 0.f;

@@ -55,8 +55,7 @@ static bool job_step(SubmitJob &j) {
         ft.n = g > 1 ? g : 0;
     }
     const sesrq_frame_io &f = j.frames[k];
-    if (forward_impl(j.net, f.in, j.in_dtype, f.out_q, f.out_f, ft.n ? g : j.N, j.H, j.W, j.ws, j.ws_bytes, j.stream, nullptr, nullptr,
-                     ft.n ? &ft : nullptr)) {
+    if (forward_impl(j.net, {f.in, j.in_dtype, f.out_q, f.out_f, ft.n ? g : j.N, j.H, j.W, nullptr, ft.n ? &ft : nullptr}, j.ws, j.ws_bytes, j.stream, nullptr)) {
         j.rc = 1; j.bad = k; j.err = sesrq_last_error();
         return false;
     }

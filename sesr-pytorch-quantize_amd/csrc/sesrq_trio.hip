@@ -363,18 +363,14 @@ template <auto KERN>
 static void launch_trio_k(TrioArgs a, hipStream_t st) {
     // 4 workgroups per CU: the LDS size a plain launch accepts and the kernel's registers allow (3 and 5 measured slower, rounds 2-3)
     constexpr int occ = 4;
-    const int num_cu = device_cu_count();
     const int lds = std::max(TRIO_LDS_BYTES, ((160 * 1024 / occ) & ~1023) - TRIO_LUT_I4 * 16);      // static + dynamic: exactly occ workgroups per 160 KiB
     const int strips = (a.W + TV - 1) / TV, steps = (a.H + TH - 1) / TH;
-    long long k = (a.wg_budget > 0 ? (long long)a.wg_budget : (long long)occ * num_cu) / ((long long)strips * a.N);
-    k = std::max(1LL, std::min<long long>(k, steps));                     // a run is at least one full step on average
-    a.chunk_steps = (int)((steps + k - 1) / k);
-    a.run_unit = (steps < 3 * k) ? TH / 2 : TH;                           // short runs (< 3 steps) are cut in half-step units
-    const int units_total = (a.H + a.run_unit - 1) / a.run_unit;
-    a.run_q = (int)(units_total / k);
-    a.run_rem = (int)(units_total % k);
-    a.inv_nx = ((long long)strips * k < 65536 && strips < 65536) ? (unsigned)((0x100000000ULL + (unsigned)strips - 1) / (unsigned)strips) : 0u;
-    dim3 grid(strips, (int)k, a.N);
+    const RunCut c = cut_runs(strips, steps, a.N, a.wg_budget, occ * device_cu_count());      // a run is at least one full step on average
+    a.chunk_steps = c.chunk; a.inv_nx = c.inv_nx;
+    a.run_unit = (steps < 3 * c.k) ? TH / 2 : TH;                         // short runs (< 3 steps) are cut in half-step units,
+    const int units = (a.H + a.run_unit - 1) / a.run_unit;                // ... the same k runs (whole steps: c.run_q, c.run_rem)
+    a.run_q = units / c.k; a.run_rem = units % c.k;
+    dim3 grid(strips, c.k, a.N);
     launch_kernel<KERN>(grid, dim3(256), (unsigned)lds, st, a);
 }
 
@@ -384,32 +380,33 @@ extern "C" int sesrq_debug_fetch_trio_stamps(void *host, size_t bytes) {
 }
 #endif
 
-int launch_trio(const TrioArgs &a, int epi_c, hipStream_t st) {
-    if ((size_t)a.H * a.W * 16 >= ((size_t)1 << 28)) { set_error("trio: frame too large for 32-bit buffer offsets (H*W must stay below 2^24 pixels)"); return 1; }
+// The instances the library builds: epilogue mode U8 = 0 / 1 / 3 / 7 (select_trio) for a plain and for the residual-merging trio, 15 for
+// the latter only
+constexpr bool trio_built(int epi, int u8) {
+    return (epi == EPI_MID || epi == EPI_PRERES) && (u8 == 0 || u8 == 1 || u8 == 3 || u8 == 7 || (u8 == 15 && epi == EPI_PRERES));
+}
+// Which epilogue mode a launch runs: the reduced forms whose precondition holds AND sesrq_options.reduced_forms (TrioArgs::allow) admits,
+// each on top of the one before.  1 = the cvt_pk_u8 epilogues, 2 = one-fma requants of layers a and b, 4 = of the third layer, 8 = the
+// residual operand out of the input window
+static int select_trio(const TrioArgs &a, int epi_c) {
     // zero points all -128 (and ReLU's clamp therefore the int8 clamp): the cvt_pk_u8 epilogues
     bool u8 = a.l[0].z_next == -128.f && a.l[1].z_next == -128.f && a.l[0].zlo == -128.f && a.l[1].zlo == -128.f;
     if (epi_c == EPI_PRERES) u8 = u8 && a.z_merge == -128.f;
     else u8 = u8 && a.l[2].z_next == -128.f && a.l[2].zlo == -128.f;
-    // sesrq_options.reduced_forms (TrioArgs::allow): 1 = the cvt_pk_u8 epilogues, 2 = one-fma requants of layers a and b, 4 = of the third
-    // layer, 8 = the residual operand out of the input window -- each only where its proof / precondition holds
     u8 = u8 && (a.allow & 1);
     const bool ab = u8 && (a.allow & 2) && a.l[0].direct && a.l[1].direct, abc = ab && (a.allow & 4) && a.l[2].direct;      // one-fma requants (proof per layer)
-    const int mode = abc ? 7 : (ab ? 3 : (u8 ? 1 : 0));
-    if (epi_c == EPI_PRERES) {
-        if (mode == 7 && a.rc_in == a.in && (a.allow & 8)) launch_trio_k<mfma_trio_kernel<EPI_PRERES, 15>>(a, st);      // the residual operand out of the input window
-        else if (mode == 7) launch_trio_k<mfma_trio_kernel<EPI_PRERES, 7>>(a, st);
-        else if (mode == 3) launch_trio_k<mfma_trio_kernel<EPI_PRERES, 3>>(a, st);
-        else if (mode == 1) launch_trio_k<mfma_trio_kernel<EPI_PRERES, 1>>(a, st);
-        else launch_trio_k<mfma_trio_kernel<EPI_PRERES, 0>>(a, st);
-    } else if (epi_c == EPI_MID) {
-        if (mode == 7) launch_trio_k<mfma_trio_kernel<EPI_MID, 7>>(a, st);
-        else if (mode == 3) launch_trio_k<mfma_trio_kernel<EPI_MID, 3>>(a, st);
-        else if (mode == 1) launch_trio_k<mfma_trio_kernel<EPI_MID, 1>>(a, st);
-        else launch_trio_k<mfma_trio_kernel<EPI_MID, 0>>(a, st);
-    } else { set_error("trio: the third layer must be a hidden layer"); return 1; }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("trio launch failed: ") + hipGetErrorString(e)); return 1; }
-    return 0;
+    if (abc && epi_c == EPI_PRERES && a.rc_in == a.in && (a.allow & 8)) return 15;
+    return abc ? 7 : (ab ? 3 : (u8 ? 1 : 0));
+}
+
+int launch_trio(const TrioArgs &a, int epi_c, hipStream_t st) {
+    if (!frame_fits_32bit_offsets(a.H, a.W)) { set_error("trio: frame too large for 32-bit buffer offsets (H*W must stay below 2^24 pixels)"); return 1; }
+    const bool built = pick([&](auto E, auto U) {
+        if constexpr (trio_built(E, U)) return launch_trio_k<mfma_trio_kernel<E, U>>(a, st), true; else return false;
+    }, Of<EPI_MID, EPI_PRERES>{}, epi_c, Of<0, 1, 3, 7, 15>{}, select_trio(a, epi_c));
+    // select_trio returns built modes only, so the one way to get here is an epi_c outside the list
+    if (!built) { set_error("trio: the third layer must be a hidden layer"); return 1; }
+    return check_launch("trio");
 }
 
 }  // namespace sesrq
