@@ -180,6 +180,18 @@ int sesrq_saturation_verdict(const int8_t *w, int k, int ic, int oc, const int32
  * caller needs to size the output of sesrq_forward, (N, cout / r^2, H * r, W * r) (csrc/torch_op/sesrq_torch_op.cpp does). */
 int sesrq_net_shape(const sesrq_net *net, int *cin, int *cout, int *pixel_shuffle);
 
+/* Caller buffers of the forward family (sesrq_forward, sesrq_forward_many, sesrq_forward_debug, sesrq_forward_timed), pinned by
+ * tests/test_caller_buffers.py:
+ *   - a frame (in, out_q, out_f, every frames[k] pointer, every tap buffer) may start at ANY address aligned to its element type: 1 byte
+ *     for int8, 4 bytes for fp32 / int32.  Frames packed back to back in one pool are fine; no 16-byte alignment is asked for and
+ *     none is assumed (the kernels' wide stores -- 2 / 4 bytes of int8, 8 / 16 bytes of fp32 per run -- are issued at element-aligned
+ *     addresses as they come);
+ *   - the workspace must be 16-byte aligned (checked: a misaligned one is refused) and hold sesrq_workspace_bytes() bytes, no more;
+ *   - nothing outside [ptr, ptr + size) of an output, a tap buffer or the workspace is written, and the inputs are not written at all;
+ *   - nothing outside [in, in + size) affects the result: what surrounds a frame (NaN, the next frame of a pool) is never used where
+ *     the pad value belongs;
+ *   - the workspace's prior contents do not matter, and every byte of an output that was asked for is written by every call. */
+
 /* Bytes of device workspace sesrq_forward needs for N frames of H x W (caller-owned). */
 size_t sesrq_workspace_bytes(const sesrq_net *net, int N, int H, int W);
 
@@ -313,6 +325,12 @@ int sesrq_calib_histogram(const float *x, size_t n, float lo, float hi, int bins
 int sesrq_calib_fakequant(const float *in, float *out, size_t n, float scale, int zero, void *stream);
 /* (clamp_b(rint(x/scale + zero)) - zero) * scale at width quan_bits (2..8) */
 int sesrq_calib_fakequant_q(const float *in, float *out, size_t n, float scale, int zero, int quan_bits, void *stream);
+
+/* Caller buffers of the calibration entry points (above and below): in, skip, out and x are fp32 tensors at any 4-byte aligned
+ * address; a slot is a sesrq_calib_slot (8-byte aligned: it holds a double).  Nothing outside [out, out + size) and the slot is written,
+ * nothing outside an input affects the result (NaN beside a frame does not reach the ranges), and there is no workspace besides
+ * scratch8 / the slot's own keys, which the call resets.  tests/test_caller_buffers.py pins this for the whole pass
+ * (sesrq/calibrate.py Calibrator.enqueue*) on frames at odd element offsets. */
 
 /* ---- device-resident calibration pass: no host round trip until the caller reads the slots back ---------------------
  * The entry points above take each batch's (scale, zero) from the host, so a calibration forward waits on the host once per

@@ -42,6 +42,12 @@ size_t sesrq_eval_workspace_bytes(int N, int C, int H, int W);
  * out: device double[N][3] = {mse, psnr, ssim} per frame.  No allocation, no synchronisation: two kernels enqueued on `stream`
  * (a hipStream_t; NULL = the default stream).  Bitwise reproducible: a frame's result has the same bits alone or inside a batch,
  * on any stream.  Arguments are checked before any HIP call; 0 on success, non-zero with sesrq_eval_last_error() set otherwise. */
+/* Caller buffers (sesrq_eval and sesrq_eval_anchored): gt, an fp32 pred and lr may start at any 4-byte aligned address, an int8 pred
+ * at any address; the 16-byte loads are used only where W % 4 == 0 and gt and pred happen to be aligned for them (16 bytes; 4 for an
+ * int8 pred), per launch -- the results are the same either way.  out and the workspace hold doubles: 8-byte aligned (16 is always
+ * enough), the workspace of sesrq_eval_workspace_bytes() bytes, no more.  Nothing outside [out, out + 3 N doubles) and the workspace is
+ * written, pred / gt / lr are not written, nothing outside them affects the scores (a NaN beside a frame does not reach them), and the
+ * workspace's prior contents do not matter (tests/test_caller_buffers.py). */
 int sesrq_eval(const sesrq_eval_desc *desc, const void *pred, const float *gt, int N, int C, int H, int W,
                double *out, void *workspace, size_t workspace_bytes, void *stream);
 

@@ -42,12 +42,19 @@ void sesrq_image_destroy(sesrq_image_ctx ctx);
  * NULL); C = 1 for SESRQ_IMAGE_Y, 3 for SESRQ_IMAGE_RGB.  Any N, H, W >= 1.  One kernel enqueued on `stream` (a hipStream_t; NULL =
  * the default stream); no allocation, no synchronisation.  The context's device must be current.  Arguments are checked before any
  * HIP call; 0 on success, non-zero with sesrq_image_last_error() set otherwise. */
+/* Caller buffers of decode: img and q0 may start at any address, x at any 4-byte aligned one.  The 16-byte path is chosen per run of 16
+ * pixels and per frame, only where source, q0 and x of that run happen to be 16-byte aligned (a batch whose H * W is no multiple of 16
+ * mixes both paths in one launch); the per-pixel path gives the same bytes.  Nothing outside the N C H W elements of q0 and x is
+ * written, img is not written, nothing outside img's N H W 3 bytes affects the result; no workspace (tests/test_caller_buffers.py). */
 int sesrq_image_decode(sesrq_image_ctx ctx, const uint8_t *img, int form, int order, int8_t *q0, float *x, int N, int H, int W,
                        void *stream);
 
 /* pred: device (N, C, H, W) fp32 (pred_dtype SESRQ_IMAGE_F32; scale / zero ignored) or int8 (SESRQ_IMAGE_I8, output domain scale > 0,
  * zero in [-128, 127]); out: device (N, H, W, C) uint8 in `order` (C = 3; ignored for C = 1).  C = 1 or 3, any N, H, W >= 1.  One
  * kernel enqueued on `stream`; no allocation, no synchronisation.  Arguments are checked before any HIP call. */
+/* Caller buffers of export: pred may start at any address aligned to its element type (4 bytes for fp32, 1 for int8), out at any
+ * address; the 16-byte path is chosen per run as in decode.  Nothing outside out's N H W C bytes is written, pred is not written, nothing
+ * outside pred affects the result; no workspace (tests/test_caller_buffers.py). */
 int sesrq_image_export(const void *pred, int pred_dtype, float scale, int zero, int C, int order, uint8_t *out, int N, int H, int W,
                        void *stream);
 

@@ -35,6 +35,10 @@ void sesrq_raw_destroy(sesrq_raw_ctx ctx);
  * Any N, H, W >= 1.  One kernel enqueued on `stream` (a hipStream_t; NULL = the default stream); no allocation, no synchronisation.
  * The context's device must be current.  Arguments are checked before any HIP call; 0 on success, non-zero with
  * sesrq_raw_last_error() set otherwise. */
+/* Caller buffers: raw may start at any 2-byte aligned address, q0 at any address, spread at any 4-byte aligned one.  The kernel takes
+ * its 16-byte path only where W % 8 == 0 and raw, q0 (8 bytes) and spread happen to be aligned for it, per launch; otherwise the
+ * per-pixel path gives the same bytes.  Nothing outside [q0, q0 + 3 N H W) and [spread, spread + 3 N H W floats) is written, raw is not
+ * written, nothing outside raw's N H W codes affects the result, and there is no workspace (tests/test_caller_buffers.py). */
 int sesrq_raw_unpack(sesrq_raw_ctx ctx, const uint16_t *raw, int8_t *q0, float *spread, int N, int H, int W, void *stream);
 
 /* The kernel instantiations sesrq_raw_unpack can launch (a fixed set), and how often each has been launched in this process. */

@@ -268,6 +268,7 @@ class Engine:
                     inp = self._in[key] = torch.empty(in_shape, dtype=torch.float32 if dt == _lib.F32 else torch.int8,
                                                       device=self.device)
             shp = self.out_shape(N, H, W)
+            self._check_out(out_q, out_f, shp)
             if want_q and out_q is None:
                 out_q = torch.empty(shp, dtype=torch.int8, device=self.device)
             if want_f and out_f is None:
@@ -281,6 +282,15 @@ class Engine:
                                           st.cuda_stream)
         _lib.check(rc)
         return out_q, out_f
+
+    def _check_out(self, out_q, out_f, shp):
+        """A caller-supplied output is written through its data_ptr(): anything but a contiguous tensor of the output shape, of its
+        dtype, on this device would be a device-memory overrun (or land in the wrong place), so it is refused before any launch."""
+        for o, dtp, what in ((out_q, torch.int8, "int8"), (out_f, torch.float32, "fp32")):
+            if o is not None and (not isinstance(o, torch.Tensor) or tuple(o.shape) != tuple(shp) or o.dtype != dtp
+                                  or o.device != self.device or not o.is_contiguous()):
+                raise ValueError(f"forward: every {what} output must be a contiguous tensor of the forward's output shape "
+                                 f"{tuple(shp)} on {self.device}")
 
     def _check_in(self, x: torch.Tensor):
         if x.dim() != 4:
@@ -310,6 +320,7 @@ class Engine:
             if not x.is_contiguous() or (want_q and out_q is None) or (want_f and out_f is None) or stream is None:
                 raise ValueError("assume_ordered=True needs a contiguous input, caller-owned output buffers and a stream")
             N, _, H, W = x.shape
+            self._check_out(out_q if want_q else None, out_f if want_f else None, self.out_shape(N, H, W))
             ws = self.workspace(N, H, W, slot)
             _lib.check(_lib.lib().sesrq_forward(self._h, x.data_ptr(), dt, out_q.data_ptr() if want_q else None,
                                                 out_f.data_ptr() if want_f else None, N, H, W, ws.data_ptr(), ws.numel(),
