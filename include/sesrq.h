@@ -31,8 +31,10 @@ extern "C" {
 /* data types of the frame buffers handed over the boundary (always NCHW, like the reference) */
 enum { SESRQ_F32 = 0, SESRQ_I8 = 1 };
 
-/* kernel families (sesrq_options.engine): AUTO = MFMA kernels where a layer shape has one, else dot4 */
-enum { SESRQ_ENGINE_AUTO = 0, SESRQ_ENGINE_DOT4 = 1, SESRQ_ENGINE_MFMA = 2 };
+/* kernel families (sesrq_options.engine): AUTO = MFMA kernels where a layer shape has one, else dot4.  A net of width b < 8
+ * (sesrq_create_q) runs on the dot4 kernels under AUTO, DOT4 and MFMA; MFMA_Q (opt-in) gives its layers their MFMA kinds on the
+ * width-aware kernel flavours (engine names "mfma-...-q<b>"), and is exactly MFMA at b = 8. */
+enum { SESRQ_ENGINE_AUTO = 0, SESRQ_ENGINE_DOT4 = 1, SESRQ_ENGINE_MFMA = 2, SESRQ_ENGINE_MFMA_Q = 3 };
 
 /* Options of a net, fixed at sesrq_create (there is no setter: a created net is immutable).
  * sesrq_default_options() fills the defaults; a NULL options pointer means the defaults too. */
@@ -288,6 +290,11 @@ int sesrq_forward_timed(const sesrq_net *net, const void *in, int in_dtype, void
 int sesrq_instance_count(void);
 const char *sesrq_instance_name(int i);
 long long sesrq_instance_launches(int i);
+/* The same for the width-aware kernels of SESRQ_ENGINE_MFMA_Q at b < 8: a list of their own, with a test matrix of their own
+ * (tests/test_quan_bits_mfma.py); none of them appears in sesrq_instance_*. */
+int sesrq_narrow_instance_count(void);
+const char *sesrq_narrow_instance_name(int i);
+long long sesrq_narrow_instance_launches(int i);
 
 /* Name of the kernel the net resolved to for layer k ("dot4-general", "mfma-h3-merged", "mfma-trio-merged", ...). */
 const char *sesrq_layer_engine(const sesrq_net *net, int k);

@@ -24,19 +24,22 @@ extern thread_local KernelEvents tl_kernel_events;
 // reached it yet.  sesrq_instance_count / _name / _launches (include/sesrq.h) expose the table and a per-process launch counter;
 // tests/test_gpu_parity.py:test_every_kernel_instance_runs_on_reference_data fails for an instantiation no case of its matrix launched.
 // (Round 4 shipped 9.5 M wrong bytes in an instantiation -- the int8-only last layer -- that 168 green tests never selected.)
-int register_instance(const void *host_fn, const char *pretty_function);
-void count_launch(int id);
-template <auto KERN>
+// REG: which list the kernel is entered in.  REG_NARROW = the width-aware kernels of SESRQ_ENGINE_MFMA_Q (sesrq_narrow_instance_*): a list
+// of their own with a matrix of their own (tests/test_quan_bits_mfma.py), so that sesrq_instance_* stays the list tests/test_instances.py drives.
+enum { REG_MAIN = 0, REG_NARROW = 1, REG_LISTS = 2 };
+int register_instance(const void *host_fn, const char *pretty_function, int reg = REG_MAIN);
+void count_launch(int id, int reg = REG_MAIN);
+template <auto KERN, int REG = REG_MAIN>
 struct KernelInstance {
     static const char *pretty() { return __PRETTY_FUNCTION__; }      // "... [KERN = &sesrq::mfma_h5_kernel<1, 2, 22, 3>]"
     static const int id;
 };
-template <auto KERN>
-const int KernelInstance<KERN>::id = register_instance((const void *)KERN, KernelInstance<KERN>::pretty());
+template <auto KERN, int REG>
+const int KernelInstance<KERN, REG>::id = register_instance((const void *)KERN, KernelInstance<KERN, REG>::pretty(), REG);
 
-template <auto KERN, typename... A>
+template <auto KERN, int REG = REG_MAIN, typename... A>
 inline void launch_kernel(dim3 grid, dim3 block, unsigned lds, hipStream_t st, const A &...a) {
-    count_launch(KernelInstance<KERN>::id);
+    count_launch(KernelInstance<KERN, REG>::id, REG);
     if (tl_kernel_events.start) hipExtLaunchKernelGGL(KERN, grid, block, lds, st, tl_kernel_events.start, tl_kernel_events.stop, 0, a...);
     else hipLaunchKernelGGL(KERN, grid, block, lds, st, a...);
 }
@@ -229,9 +232,9 @@ struct ConvArgs {
     int add_const[SESRQ_MAX_CH];
     const float2 *mn_oc;     // dot4 kernels: per-output-channel ((float)M, 2^-n) [oc] of a per-channel layer (sesrq_layer_desc.M_oc), or NULL
     FrameTable ft;           // MFMA first / last layer kernels only (ft.n == 0: one contiguous batch at in / out_q / out_f)
-    // activation width b (sesrq_create_q; dot4 kernels only -- a net with b < 8 runs no other kernel): every activation clamp is
-    // clamp(., qlo, qhi) = [-2^(b-1), 2^(b-1) - 1], the residual merge offsets are qhalf = 2^(b-1) and qspan = 2^b (quan_func.py:250-252).
-    // b = 8: [-128, 127], 128, 256 -- the constants the MFMA kernels and the trio keep as literals
+    // activation width b (sesrq_create_q; the dot4 kernels, and the width-aware MFMA kernels of SESRQ_ENGINE_MFMA_Q): every activation clamp
+    // is clamp(., qlo, qhi) = [-2^(b-1), 2^(b-1) - 1], the residual merge offsets are qhalf = 2^(b-1) and qspan = 2^b (quan_func.py:250-252).
+    // b = 8: [-128, 127], 128, 256 -- the constants the 8-bit MFMA kernels and the trio keep as literals
     float qlo, qhi, qhalf, qspan;
 };
 
@@ -353,6 +356,7 @@ struct LayerChoice {
 int launch_dot4(const LayerPlan &lp, const LayerChoice &c, const ConvArgs &a, hipStream_t st);
 int launch_mfma(const LayerPlan &lp, const LayerChoice &c, const ConvArgs &a, hipStream_t st);
 int launch_trio(const TrioArgs &a, int epi_c, hipStream_t st);
+int launch_trio_q(const TrioArgs &a, const ConvArgs &width, int epi_c, hipStream_t st);      // width b < 8: qlo .. qspan of `width` (any layer's base)
 int launch_unpack_nhwc16(const void *nhwc, signed char *nchw, int N, int C, int H, int W, hipStream_t st);
 
 }  // namespace sesrq
@@ -376,6 +380,7 @@ struct sesrq_net {
     float i8_in_scale = 0.f;            // > 0: int8 input frames are in this (scale, zero) domain of an upstream net
     int i8_in_zero = 0;
     sesrq::DevBuf<int> d_merge_lut;     // 512-byte table of the residual merge (see TrioArgs::merge_lut)
+    std::string trio_engine;            // what sesrq_layer_engine reports for a layer inside a fused trio
     std::vector<int> trio_len;          // trio_len[k] == 3: layers k..k+2 are eligible for the fused hidden trio
     int device = 0;
     int quan_bits = 8;          // activation / weight width b (sesrq_create_q), 2..8

@@ -201,9 +201,11 @@ static bool one_risky_pe(const LayerPlan &lp) { return lp.mfma_kind != MFMA_NONE
 static bool pe_split(const LayerPlan &lp, bool last) { return last && lp.mfma_kind == MFMA_H5 && lp.oc <= 4; }
 
 // Step 1, per layer: what its weights can do to the accumulators (load-time proofs, sesrq_verify.hip), and the kernel family that follows.
-// narrow (width b < 8) and per-channel layers: the dot4 kernels only -- their clamps and constants are runtime arguments, the MFMA
-// kernels and the fused trio keep the 8-bit literals and one (M, n)
-static void analyse_layer(const sesrq_net_desc *d, int k, bool narrow, LayerPlan &lp) {
+// Per-channel layers: the dot4 kernels only (the MFMA kernels hold one (M, n)).  A net of width b < 8 too -- the dot4 kernels' clamps are
+// run-time arguments, the MFMA kernels and the fused trio keep the 8-bit literals -- unless the net asks for SESRQ_ENGINE_MFMA_Q: its
+// layers then get their MFMA kinds and run on the width-aware flavours (mfma_*_kernel_q).  Those have no unbiased hybrid and no
+// literal-bounds form: a layer with one risky PE is a general one there, and a wide layer (reach >= 2^22) stays on the dot4 kernels.
+static void analyse_layer(const sesrq_net_desc *d, int k, bool narrow, int engine, LayerPlan &lp) {
     const sesrq_layer_desc &l = d->layers[k];
     const bool last = k == d->n_layers - 1;
     lp.k = l.k; lp.ic = l.ic; lp.oc = l.oc;
@@ -212,12 +214,13 @@ static void analyse_layer(const sesrq_net_desc *d, int k, bool narrow, LayerPlan
     // the biased accumulator of the MFMA kernels is exact for |s| < 2^22 only (never reached at 18 / 20 bits with a 16-bit constant)
     lp.reach = reachable_sum(lp.worst_sum, d->pe_add_bits, l.add_const, l.oc);
     lp.wide = lp.reach >= BIASED_LIMIT;
-    lp.mfma_kind = (narrow || l.M_oc) ? MFMA_NONE
+    const bool narrow_dot4 = narrow && (engine != SESRQ_ENGINE_MFMA_Q || lp.wide);
+    lp.mfma_kind = (narrow_dot4 || l.M_oc) ? MFMA_NONE
                  : k == 0             ? (l.k == 5 && l.ic <= 4 ? MFMA_F5 : MFMA_NONE)
                  : l.k == 3           ? (last ? MFMA_NONE : MFMA_H3)
                                       : MFMA_H5;
     // the hybrid kernels hold the reference's 18 / 20-bit clamps as literals
-    lp.hybrid = one_risky_pe(lp) && d->pe_acc_bits == 18 && d->pe_add_bits == 20 && !lp.wide;
+    lp.hybrid = one_risky_pe(lp) && d->pe_acc_bits == 18 && d->pe_add_bits == 20 && !lp.wide && !narrow;
     // hidden-layer rows: channel o sits in register o >> 2 of lane group o & 3.  If every channel that can saturate lives in
     // ONE register, the hybrid first layer clamps that register only (risky_reg), else all four (4)
     for (int i = 0; i < 4; ++i)
@@ -225,7 +228,7 @@ static void analyse_layer(const sesrq_net_desc *d, int k, bool narrow, LayerPlan
 }
 
 // Step 2, per layer: its weight images, one upload each.  false = the device refused one.
-static bool upload_images(const sesrq_layer_desc &l, bool first, bool last, int ps, LayerPlan &lp) {
+static bool upload_images(const sesrq_layer_desc &l, bool first, bool last, int ps, bool narrow, LayerPlan &lp) {
     std::vector<int> gen, mer, fr;
     pack_weights(l, lp.ocp, first, gen, mer);
     if (!lp.d_wpk_general.upload(gen) || !lp.d_wpk_merged.upload(mer)) return false;
@@ -241,7 +244,7 @@ static bool upload_images(const sesrq_layer_desc &l, bool first, bool last, int 
         return dst.upload(fr);
     };
     if (!frags(lp.d_afrag_merged, lp.mfma_kind, false, lastnv, -1) || !frags(lp.d_afrag_general, lp.mfma_kind, true, lastnv, -1)) return false;
-    if (one_risky_pe(lp)) {      // hybrid kernels: merged chain without the risky PE; a 3-channel first layer: the sparse images too
+    if (one_risky_pe(lp) && !narrow) {      // (the width-aware kernels run such a layer on the per-PE image)      // hybrid kernels: merged chain without the risky PE; a 3-channel first layer: the sparse images too
         const int risky = __builtin_ctz(lp.risky_mask);
         if (!frags(lp.d_afrag_others, lp.mfma_kind, false, lastnv, risky)) return false;
         if (lp.mfma_kind == MFMA_F5 && l.ic == 3 && risky < 3) {
@@ -303,23 +306,29 @@ static void engine_name(LayerPlan &lp, bool per_channel, int quan_bits, bool on_
     lp.engine_dot4 = std::string(lp.general ? "dot4-general" : "dot4-merged") + (per_channel ? "-perchannel" : "") +
                      (quan_bits < 8 ? "-q" + std::to_string(quan_bits) : "");
     lp.engine_mfma = lp.mfma_kind == MFMA_NONE ? lp.engine_dot4 : std::string(pesplit ? "mfma-h5p" : kn[lp.mfma_kind]) +
-                     (lp.wide ? "-unbiased" : (lp.hybrid && !pesplit) ? "-hybrid" : lp.general ? "-general" : "-merged");
+                     (lp.wide ? "-unbiased" : (lp.hybrid && !pesplit) ? "-hybrid" : lp.general ? "-general" : "-merged") +
+                     (quan_bits < 8 ? "-q" + std::to_string(quan_bits) : "");      // the width-aware flavours (SESRQ_ENGINE_MFMA_Q)
     lp.engine = on_dot4 ? lp.engine_dot4 : lp.engine_mfma;
 }
 
 // Step 5: residual merge (myQL/quan_func.py:256-270): q4 = clamp8(rint(fl(fl(u * M_res) * 2^-n_res + zero[L-1]))) is a function of the
 // 9-bit integer u = rc + ic + 256 alone: a 511-entry byte table (512 bytes = 128 dwords) replaces the second requant of the fused trio's
 // last phase (2 fma + add + cvt per value) by one LDS byte read.  Same fp32 operations, same order, as requant4<true> + round_pack.
-static std::vector<int> merge_table(uint32_t M_res, uint32_t n_res, int zero_merge) {
+// Width b < 8: u = rc + ic + 2^b and the clamp is the width's.  The kernels keep the table's index rc + ic + 256, so entry i holds
+// q4(u = i - 256 + 2^b); a width reaches i in [256 - 2^b, 254 + 2^b] only, entries below 256 - 2^b (u < 0) stay 0.
+static std::vector<int> merge_table(uint32_t M_res, uint32_t n_res, int zero_merge, int quan_bits) {
     std::vector<int> lut(128);
     unsigned char *bytes = reinterpret_cast<unsigned char *>(lut.data());
     const float Mres = (float)M_res, shres = ldexpf(1.0f, -(int)n_res), zm = (float)zero_merge;
-    for (int u = 0; u < 512; ++u) {
+    const float qlo = (float)-(1 << (quan_bits - 1)), qhi = (float)((1 << (quan_bits - 1)) - 1);
+    for (int i = 0; i < 512; ++i) {
+        const int u = i - 256 + (1 << quan_bits);
+        if (u < 0) continue;
         const float prod = (float)u * Mres;              // one rounding of the exact product, as fma(MAGIC + u, M, -MAGIC * M)
         float v = prod * shres;                          // exact (power of two)
         v = v + zm;                                      // one rounding, as fma(prod, 2^-n, z)
-        v = fminf(fmaxf(v, -128.f), 127.f);
-        bytes[u] = (unsigned char)(signed char)(int)nearbyintf(v);
+        v = fminf(fmaxf(v, qlo), qhi);
+        bytes[i] = (unsigned char)(signed char)(int)nearbyintf(v);
     }
     return lut;
 }
@@ -350,7 +359,7 @@ static std::vector<int> plan_trios(sesrq_net &net) {
             TrioLayer &tl = t.l[j];
             tl.afrag = layers[k + j].d_afrag_merged.get();
             tl.Mf = b.Mf; tl.sh = b.sh; tl.z_next = b.z_next; tl.Md = b.Md; tl.Cd = b.Cd; tl.direct = b.direct;
-            tl.zlo = b.relu ? fmaxf(b.z_next, -128.f) : -128.f;
+            tl.zlo = b.relu ? fmaxf(b.z_next, b.qlo) : b.qlo;      // qlo = -128 at 8 bits
             tl.pad_next = layers[k + j + 1].base.pad_word;
         }
     }
@@ -368,13 +377,14 @@ static bool build_layers(sesrq_net &net, const sesrq_net_desc *d) {
     for (int k = 0; k < L; ++k) {
         const sesrq_layer_desc &l = d->layers[k];
         LayerPlan &lp = net.layers[k];
-        analyse_layer(d, k, net.quan_bits < 8, lp);
-        if (!upload_images(l, k == 0, k == L - 1, d->pixel_shuffle, lp)) return false;
+        analyse_layer(d, k, net.quan_bits < 8, net.engine, lp);
+        if (!upload_images(l, k == 0, k == L - 1, d->pixel_shuffle, net.quan_bits < 8, lp)) return false;
         prefill_args(d, k, net.quan_bits, net.reduced_forms, lp);
         engine_name(lp, l.M_oc != nullptr, net.quan_bits, net.engine == SESRQ_ENGINE_DOT4 || (k == 0 && !net.fd.ok));
     }
     net.layers[0].base.fd = net.fd;
-    if (!net.d_merge_lut.upload(merge_table(d->M_res, d->n_res, d->zero[L - 1]))) return false;
+    if (!net.d_merge_lut.upload(merge_table(d->M_res, d->n_res, d->zero[L - 1], net.quan_bits))) return false;
+    net.trio_engine = "mfma-trio-merged" + (net.quan_bits < 8 ? "-q" + std::to_string(net.quan_bits) : std::string());
     net.trio_len = plan_trios(net);
     return true;
 }
@@ -407,7 +417,7 @@ int sesrq_create_q(const sesrq_net_desc *d, const sesrq_options *opts, int quan_
     if (opts) o = *opts;
     std::string err;
     if (quan_bits < 2 || quan_bits > 8) err = "sesrq_create: quan_bits must be 2..8 (define.py QUAN_BIT)";
-    else if (o.engine < SESRQ_ENGINE_AUTO || o.engine > SESRQ_ENGINE_MFMA) err = "sesrq_create: bad engine option";
+    else if (o.engine < SESRQ_ENGINE_AUTO || o.engine > SESRQ_ENGINE_MFMA_Q) err = "sesrq_create: bad engine option";
     else err = validate_desc(d, quan_bits);
     if (err.empty()) err = validate_options(o, d, quan_bits < 8);
     if (!err.empty()) { set_error(err); return 1; }
@@ -429,7 +439,8 @@ int sesrq_create_q(const sesrq_net_desc *d, const sesrq_options *opts, int quan_
     net->quan_bits = quan_bits;
     net->rc_separate = (d->zero[1] != qlo);      // layer 0's output IS the residual operand only in the domain zero[1] == -2^(b-1)
     net->device = device;
-    net->engine = o.engine;
+    // MFMA_Q at 8 bits IS the MFMA engine: same kinds, same instantiations, same names
+    net->engine = (o.engine == SESRQ_ENGINE_MFMA_Q && quan_bits == 8) ? SESRQ_ENGINE_MFMA : o.engine;
     net->force_general = o.force_general ? 1 : 0;
     net->div_mode = o.exact_div;
     net->fuse_hidden = o.fuse_hidden;

@@ -106,10 +106,12 @@ struct LastStore {
     // f32(scale_L) (quan_func.py:594) -- with the same run structure as the int8 flavours: one 8-byte store per 2-value run, one 16-byte
     // store per 4-value run (the every-output-kind path issues one dword store per value behind output-kind branches: 66 us per 1080p
     // frame, 1.5 TB/s).  No anchor add here (that keeps the general path).
+    // QW: the width-aware kernels -- the upper clamp is ConvArgs::qhi instead of the literal 127 (the one-fma forms are 8-bit only)
     // OUTF == 2: ... plus the x2 anchor add, y + x (one fp32 add per value; x01 / x2 from fetch_anchor): the pair map only (3 -> 12 channels,
     // PixelShuffle 2 -- the reference's one anchor topology, models/sesr_arch.py:171-205); other shapes keep the general path
-    template <bool BIASED, int FASTD = 0, int NV = 4, int OUTF = 0>
+    template <bool BIASED, int FASTD = 0, int NV = 4, int OUTF = 0, bool QW = false>
     __device__ __forceinline__ void store(const int s[4], const ConvArgs &a, int gy, float zlo, bool row_ok = true, float x01 = 0.f, float x2 = 0.f) const {
+        const float hi = QW ? a.qhi : 127.f;      // the upper activation clamp, 2^(b-1) - 1
         constexpr int FAST = FASTD % 10;
         static_assert(!OUTF || FAST != 0, "fp32-only store: FAST flavours");
         static_assert(OUTF != 2 || (NV == 3 && FAST == 2), "anchor flavour: the pair map only");
@@ -132,7 +134,7 @@ struct LastStore {
                 const float v[4] = {v01[0], v01[1], v23[0], v23[1]};
                 const float zo = in_vgpr(a.z_out);
 #pragma unroll
-                for (int i = 0; i < NV; ++i) yv[i] = __fmul_rn(__fsub_rn(__builtin_rintf(med3(v[i], zlo, 127.f)), zo), sv);
+                for (int i = 0; i < NV; ++i) yv[i] = __fmul_rn(__fsub_rn(__builtin_rintf(med3(v[i], zlo, hi)), zo), sv);
             }
             if constexpr (OUTF == 2) { yv[0] = __fadd_rn(yv[0], x01); yv[1] = __fadd_rn(yv[1], x01); yv[2] = __fadd_rn(yv[2], x2); }
             const int so = __builtin_amdgcn_readfirstlane(row_ok ? gy * (FAST * FAST * a.W) * 4 : 0x7fff0000);
@@ -192,7 +194,7 @@ struct LastStore {
             requant4<BIASED>(s3, a.Mf, a.sh, a.z_out, v01, v23);
         }
         const v2f mg = {MAGIC, MAGIC};
-        v2f c01 = {med3(v01[0], zlo, 127.f), med3(v01[1], zlo, 127.f)}, c23 = {med3(v23[0], zlo, 127.f), NV == 4 ? med3(v23[1], zlo, 127.f) : 0.f};
+        v2f c01 = {med3(v01[0], zlo, hi), med3(v01[1], zlo, hi)}, c23 = {med3(v23[0], zlo, hi), NV == 4 ? med3(v23[1], zlo, hi) : 0.f};
         c01 = c01 + mg;                    // low mantissa bits = rint(value), two's complement
         if constexpr (NV == 4) c23 = c23 + mg; else c23[0] = c23[0] + MAGIC;
         // scalar offset of the row: gy is wave-uniform by contract, but derives from threadIdx (the wave index), so the
@@ -442,85 +444,21 @@ struct StageNHWC16 {
     }
 
 // ------------------------------------------------------------------ hidden 3x3, 16 -> 16 channels
-template <int MODE, int EPI>
-__global__ __launch_bounds__(256) void mfma_h3_kernel(const ConvArgs a) {
-    constexpr bool GENERAL = mode_general(MODE);
-    constexpr int SW = MTW + 4;                      // 1 left halo + 64 + 1 right halo + over-read
-    constexpr int SH = MTH + 2 + (MODE != MERGED ? 1 : 0);  // per-PE chains read row y+3 with zero weights
-    constexpr int PW = GENERAL ? SW : 0;             // planar image: row pitch 4*68 = 272 dwords = 16 mod 64 banks
-    __shared__ int4 buf0[SH * SW], buf1[SH * SW];
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
-    kernarg_warm<ConvArgs>();
-    const BlockXY bxy = xcd_block(a.inv_nx);
-    const int x0 = bxy.x * MTW, n_img = blockIdx.z;
-    const int4 *fr = a.afrag;
-    constexpr bool BIASED = mode_biased(MODE);     // requant without v_cvt: sums carry + MAGIC_I (needs |s| < 2^22)
-    int4 ac = fr[g];
-    if constexpr (BIASED) { ac.x += MAGIC_I; ac.y += MAGIC_I; ac.z += MAGIC_I; ac.w += MAGIC_I; }
-    v4i A[GENERAL ? 4 : 3];
-#pragma unroll
-    for (int f = 0; f < (GENERAL ? 4 : 3); ++f) A[f] = ld_frag(fr + 4 + f * 64 + l);
-    v4i AR = {0, 0, 0, 0};
-    if constexpr (MODE == HYB) AR = ld_frag(a.afrag2 + 4 + a.risky_pe * 64 + l);
-    const float zlo = a.relu ? fmaxf(a.z_next, -128.f) : -128.f;
-    const int gx = x0 + 16 * w + n;
-    auto compute = [&](const int4 *tile, int y0) __attribute__((always_inline)) {
-        const RowIO io = make_rowio(a, n_img, y0, gx, g);
-        if constexpr (!GENERAL) {
-            const int col = 16 * w + n + g;
-            const v4i zero = {0, 0, 0, 0};
-            const v4i acc0 = {ac.x, ac.y, ac.z, ac.w};
-            const int *t32 = reinterpret_cast<const int *>(tile);
-            const int rbase = (g * SW + 16 * w + n) * 4 + a.risky_pe;      // HYB: word risky_pe of pixel (row g, col)
-            v4i B0 = ld_frag(tile + col), B1 = ld_frag(tile + SW + col);
-#pragma unroll
-            for (int y4 = 0; y4 < MTH; y4 += 4) {
-                int s4[4][4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const v4i B2 = ld_frag(tile + (y4 + r + 2) * SW + col);
-                    v4i acc[MODE == HYB ? 2 : 1];
-                    acc[0] = mfma(A[0], B0, acc0);
-                    acc[0] = mfma(A[1], B1, acc[0]);
-                    acc[0] = mfma(A[2], B2, acc[0]);
-                    B0 = B1; B1 = B2;
-                    if constexpr (MODE == HYB) {
-                        const int o = rbase + (y4 + r) * SW * 4;
-                        const v4i br = {t32[o], t32[o + 4], t32[o + 8], t32[o + 12]};
-                        acc[1] = mfma(AR, br, zero);
-                    }
-                    finish_sums<MODE>(s4[r], acc, ac, a);
-                }
-                emit_rows4<EPI, false, BIASED>(s4, a, io, y4, zlo);
-            }
-        } else {
-            const int col = 16 * w + n;
-#pragma unroll 1
-            for (int y4 = 0; y4 < MTH; y4 += 4) {
-                int s4[4][4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int *row = reinterpret_cast<const int *>(tile) + (y4 + r + g) * (4 * PW) + col;   // lane group g = kernel row ky
-                    const v4i zero = {0, 0, 0, 0};
-                    v4i acc[4];
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        const int *q = row + p * PW;                       // plane p: 4 horizontally adjacent pixels of PE p
-                        const v4i b = {q[0], q[1], q[2], q[3]};
-                        acc[p] = mfma(A[p], b, zero);
-                    }
-                    if constexpr (MODE == GEN_TAP) tap_sums<4>(acc, a, n_img, y0 + y4 + r, gx, g, 0);
-                    finish_sums<MODE>(s4[r], acc, ac, a);
-                }
-                emit_rows4<EPI, false, BIASED>(s4, a, io, y4, zlo);
-            }
-        }
-    };
-#define SESRQ_COMPUTE(B) compute(B, y0);
-    using Stage = StageNHWC16<SH, SW, 1, PW>;
-    SESRQ_TILE_WALK(Stage, buf0, buf1, SESRQ_COMPUTE)
-#undef SESRQ_COMPUTE
-}
+// Each hidden / last-layer kernel's text lives in a file of its own (sesrq_mfma_h3.inc, _h5.inc, _h5p.inc), included twice: as the 8-bit
+// kernel and as its width-aware flavour mfma_*_kernel_q (NARROW: activation range from ConvArgs::qlo .. qspan, epilogues epi_*_q), which
+// sits in a registry of its own so that the 8-bit instantiations keep theirs
+constexpr int H3_SW = MTW + 4;                       // 1 left halo + 64 + 1 right halo + over-read
+constexpr int h3_sh(int mode) { return MTH + 2 + (mode != MERGED ? 1 : 0); }      // per-PE chains read row y+3 with zero weights
+#define SESRQ_KERNEL mfma_h3_kernel
+#define SESRQ_NARROW 0
+#include "sesrq_mfma_h3.inc"
+#undef SESRQ_KERNEL
+#undef SESRQ_NARROW
+#define SESRQ_KERNEL mfma_h3_kernel_q
+#define SESRQ_NARROW 1
+#include "sesrq_mfma_h3.inc"
+#undef SESRQ_KERNEL
+#undef SESRQ_NARROW
 
 // ------------------------------------------------------------------ 5x5, 16 input channels
 // FAST (EPI_LAST only): 2 / 4 = PixelShuffle factor, int8 output only (LastStore::store); 0 = every output kind
@@ -528,180 +466,18 @@ __global__ __launch_bounds__(256) void mfma_h3_kernel(const ConvArgs a) {
 // CU) ran the last layer 5 % SLOWER than 4 (29.3 vs 27.7 us) and the fused trio 13 % slower (47.1 vs 41.6 us).
 // NV (EPI_LAST only): real accumulator rows per lane group, 3 for up to 12 output channels (last_slot_oc, sesrq_common.h)
 // OUTF (EPI_LAST, FAST != 0): 1 = the fp32 frame instead of the int8 one, 2 = ... with the x2 anchor add (LastStore::store)
-template <int MODE, int EPI, int FAST = 0, int NV = 4, int OUTF = 0>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void mfma_h5_kernel(const ConvArgs a) {
-    constexpr bool GENERAL = mode_general(MODE);
-    constexpr int SW = MTW + 8;          // 2 + 64 + 2 halo, + over-read of the kx = 4..7 group
-    constexpr int SH = MTH + 4;
-    // per-PE (general) kernels: column-major PE-planar image [PE][col][row] (StageNHWC16, CP > 0), column pitch CS = 12 dwords (the tile's
-    // rows), plane pitch CP = 72 columns.  A lane's operand per PE and K-chunk = two vertical pixel pairs that start on EVEN tile rows
-    // (h5_pair, sesrq_common.h): 8-byte-aligned LDS accesses straight into the four operand registers -- K-chunk 0 one ds_read2_b64 of four
-    // consecutive rows, K-chunk 1 two ds_read_b64 (round 3: four ds_read2_b32 of pairs of any alignment, 1.75 x the LDS cycles).  That needs
-    // output rows of one parity per wave: wave w works on rows (w & 1) + 2t, t = 0..3, of TWO 16-column groups (w >> 1), with the A
-    // fragments of its parity.  All 4 PEs x 4 rows of a column group are reached by immediate offsets from three lane-constant addresses;
-    // the planes are more than a ds_read2_b64's offset range apart, so hipcc cannot pair reads of different PEs (it did, and then moved
-    // 192 registers per tile into operand order).  Banks: h5_pair; the staging writes (dword stores 12 apart) are 4-way.
-    constexpr int CS = GENERAL ? SH : 0;
-    constexpr int CP = SW * CS;
-    static_assert(!GENERAL || (CS % 8 == 4 && CP * 4 > 2040), "aligned pairs / bank rule / no ds_read2 across PE planes");
-    constexpr int SHB = SH + (MODE == HYB ? 1 : 0);      // hybrid: the risky PE's pairs reach one row below the tile (zero weights)
-    __shared__ int4 buf0[GENERAL ? CP : SHB * SW], buf1[GENERAL ? CP : SHB * SW];      // general: 4 planes of CP dwords
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
-    kernarg_warm<ConvArgs>();
-    const BlockXY bxy = xcd_block(a.inv_nx);
-    const int x0 = bxy.x * MTW, n_img = blockIdx.z;
-    using Stage = StageNHWC16<SH, SW, 2, 0, CP, CS>;
-    SESRQ_TILE_WALK_BEGIN(MTH, Stage)
-    const int4 *fr = a.afrag;
-    constexpr bool BIASED = mode_biased(MODE);     // requant without v_cvt: sums carry + MAGIC_I (needs |s| < 2^22)
-    int4 ac = fr[g];
-    if constexpr (BIASED) { ac.x += MAGIC_I; ac.y += MAGIC_I; ac.z += MAGIC_I; ac.w += MAGIC_I; }
-    const float zlo = a.relu ? fmaxf(EPI == EPI_LAST ? a.z_out : a.z_next, -128.f) : -128.f;
-    const int gx = x0 + 16 * w + n;
-    // merged: K-chunks 0..4 = kernel row f, lane group g = kx 0..3;  5 = column 4, lane group g = ky 0..3;  6 = tap (4,4)
-    // general, per PE p two K-chunks of two vertical pixel pairs per lane group (h5_pair; pack_mfma_frags, MFMA_H5), one set per row parity
-    constexpr int NF = GENERAL ? 8 : 7;
-    // general: this wave's row parity and pair of 16-column groups -- wave-uniform, and TOLD so (readfirstlane): everything derived from
-    // them (row offsets of the stores, column bases) is then scalar arithmetic instead of VALU + v_readfirstlane per row
-    const int wu = __builtin_amdgcn_readfirstlane(w);
-    const int par = GENERAL ? (wu & 1) : 0, cg = wu >> 1;
-    v4i A[NF];
-#pragma unroll
-    for (int f = 0; f < NF; ++f) A[f] = ld_frag(fr + 4 + (par * 8 + f) * 64 + l);
-    // per-PE chains (general, and the risky PE's chain of the hybrid mode); must match pack_mfma_frags (MFMA_H5 general)
-    int pcol[2][2], prow[2][2];                         // [chunk][pair]: column and first row of lane group g's pixel pair
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) h5_pair(c, g, q, pcol[c][q], prow[c][q]);
-    LastStore ls, ls1;                                  // general: one per column group of the wave
-    if constexpr (EPI == EPI_LAST) {
-        if constexpr (GENERAL) { ls.template init<NV, FAST % 10>(a, n_img, g, x0 + 32 * cg + n); ls1.template init<NV, FAST % 10>(a, n_img, g, x0 + 32 * cg + 16 + n); }
-        else ls.template init<NV, FAST % 10>(a, n_img, g, gx);
-    }
-    v4i AR[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-    if constexpr (MODE == HYB) {
-        AR[0] = ld_frag(a.afrag2 + 4 + (0 * 4 + a.risky_pe) * 64 + l);
-        AR[1] = ld_frag(a.afrag2 + 4 + (1 * 4 + a.risky_pe) * 64 + l);
-    }
-    // lane-constant byte offsets of the four pixel pairs inside a tile for both column groups, computed ONCE (pinned: hipcc re-derived them
-    // -- 8 v_mul_lo + a dozen adds -- at the top of every tile)
-    unsigned pboff[2][2][2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                pboff[j][c][q] = GENERAL ? (unsigned)(((32 * cg + 16 * j + n + pcol[c][q]) * CS + prow[c][q]) * 4) : 0u;      // [0][1] unused: pair 1 of K-chunk 0 = pair 0 + 2 rows
-                asm volatile("" : "+v"(pboff[j][c][q]));
-            }
-    auto compute = [&](const int4 *tile, int y0) __attribute__((always_inline)) {
-        RowIO io;
-        if constexpr (EPI != EPI_LAST) io = make_rowio(a, n_img, y0, gx, g);
-        if constexpr (!GENERAL) {
-            const int col = 16 * w + n + g, colc = 16 * w + n + 4;
-            const v4i zero = {0, 0, 0, 0};
-            const v4i acc0 = {ac.x, ac.y, ac.z, ac.w};
-            const int *t32 = reinterpret_cast<const int *>(tile);
-            const int cb = (16 * w + n) * 4 + a.risky_pe;       // HYB: word risky_pe of column (16w + n), row 0
-            v4i B[5];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) B[r] = ld_frag(tile + r * SW + col);
-#pragma unroll
-            for (int y4 = 0; y4 < MTH; y4 += 4) {
-                int s4[4][4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int y = y4 + r;
-                    float x01 = 0.f, x2 = 0.f;
-                    if constexpr (OUTF == 2) ls.fetch_anchor(a, y0 + y, x01, x2);
-                    B[(y + 4) % 5] = ld_frag(tile + (y + 4) * SW + col);
-                    const v4i C5 = ld_frag(tile + (y + g) * SW + colc);      // column 4: lane group g = kernel row g
-                    const v4i C6 = ld_frag(tile + (y + 4) * SW + colc);      // tap (4,4)
-                    v4i acc[MODE == HYB ? 2 : 1];
-                    acc[0] = acc0;
-#pragma unroll
-                    for (int ky = 0; ky < 5; ++ky) acc[0] = mfma(A[ky], B[(y + ky) % 5], acc[0]);
-                    acc[0] = mfma(A[5], C5, acc[0]);
-                    acc[0] = mfma(A[6], C6, acc[0]);
-                    if constexpr (MODE == HYB) {
-                        int o[2][2];                                   // word risky_pe of the first pixel of pair [chunk][pair]
-#pragma unroll
-                        for (int c = 0; c < 2; ++c)
-#pragma unroll
-                            for (int q = 0; q < 2; ++q) o[c][q] = cb + ((y + prow[c][q]) * SW + pcol[c][q]) * 4;
-                        const v4i b0 = {t32[o[0][0]], t32[o[0][0] + SW * 4], t32[o[0][1]], t32[o[0][1] + SW * 4]};
-                        const v4i b1 = {t32[o[1][0]], t32[o[1][0] + SW * 4], t32[o[1][1]], t32[o[1][1] + SW * 4]};
-                        acc[1] = mfma(AR[0], b0, zero);
-                        acc[1] = mfma(AR[1], b1, acc[1]);
-                    }
-                    finish_sums<MODE, NV>(s4[r], acc, ac, a);
-                    if constexpr (EPI == EPI_LAST) {
-                        // a row below the frame is dropped by its offsets (FAST: the scalar one, else the lanes'), not by a
-                        // branch: the four rows stay one basic block
-                        ls.template store<BIASED, FAST, NV, OUTF>(s4[r], a, y0 + y, zlo, y0 + y < a.H, x01, x2);
-                    }
-                }
-                if constexpr (EPI != EPI_LAST) emit_rows4<EPI, false, BIASED>(s4, a, io, y4, zlo);
-            }
-        } else {
-            typedef int v2ia __attribute__((ext_vector_type(2)));                  // two adjacent dwords, 8-byte aligned: ds_read_b64
-            typedef const v2ia __attribute__((address_space(3))) *lds_pair_t;
-            const unsigned tb = (unsigned)(size_t)(const __attribute__((address_space(3))) void *)tile;     // LDS byte address of the tile
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {                                // the wave's two 16-column groups
-                const int gxj = x0 + 32 * cg + 16 * j + n;
-                // LDS byte addresses (row 0, PE 0) of the four pairs.  K-chunk 0's second pair is the first one two rows down, but it gets an
-                // address register of its own: reads off ONE register 8 bytes apart become a ds_read2_b64, which the LDS serves 16 lanes at a
-                // time over 32 banks (column pitch 12: two-way conflicts, half the rate) where a ds_read_b64 goes 32 lanes at a time over 64
-                unsigned pa0 = tb + pboff[j][0][0], pa1 = tb + pboff[j][0][0] + 8, p0 = tb + pboff[j][1][0], p1 = tb + pboff[j][1][1];
-                int s4[4][4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {                            // tile rows par + 2t
-                    const int gy = y0 + par + 2 * t;
-                    float x01 = 0.f, x2 = 0.f;
-                    if constexpr (OUTF == 2) { if (j == 0) ls.fetch_anchor(a, gy, x01, x2); else ls1.fetch_anchor(a, gy, x01, x2); }
-                    const v4i zero = {0, 0, 0, 0};
-                    v4i acc[4];
-                    // a pair of row t + 1 is a pair of row t in another operand slot: hide the relation between the rows' addresses from the
-                    // compiler, which otherwise keeps the pair and MOVES it into place (the reads are not what bounds this loop, vector issue is)
-                    asm("" : "+v"(pa0), "+v"(pa1), "+v"(p0), "+v"(p1));
-                    v4i b0[4], b1[4];
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        const int o = 4 * (2 * t + p * CP);
-                        const v2ia a0 = *(lds_pair_t)(size_t)(pa0 + o), a1 = *(lds_pair_t)(size_t)(pa1 + o);
-                        const v2ia c0 = *(lds_pair_t)(size_t)(p0 + o), c1 = *(lds_pair_t)(size_t)(p1 + o);
-                        b0[p] = (v4i){a0[0], a0[1], a1[0], a1[1]};
-                        b1[p] = (v4i){c0[0], c0[1], c1[0], c1[1]};
-                    }
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        acc[p] = mfma(A[p], b0[p], zero);
-                        acc[p] = mfma(A[4 + p], b1[p], acc[p]);
-                    }
-                    if constexpr (MODE == GEN_TAP) tap_sums<NV>(acc, a, n_img, gy, gxj, g, EPI == EPI_LAST ? NV : 0);
-                    finish_sums<MODE, NV>(s4[t], acc, ac, a);
-                    if constexpr (EPI == EPI_LAST) {
-                        // a row below the frame is dropped by its offsets (FAST: the scalar one, else the lanes'), not by a branch
-                        if (j == 0) ls.template store<BIASED, FAST, NV, OUTF>(s4[t], a, gy, zlo, gy < a.H, x01, x2);
-                        else ls1.template store<BIASED, FAST, NV, OUTF>(s4[t], a, gy, zlo, gy < a.H, x01, x2);
-                    }
-                }
-                if constexpr (EPI != EPI_LAST) {
-                    // hidden 5x5 layer: the wave's four rows are two apart: lane (n, r' = g) stores pixel row y0 + par + 2g
-                    RowIO ioj = make_rowio(a, n_img, y0, gxj, g);
-                    ioj.voff = (gxj < a.W) ? ((y0 + par + 2 * g) * a.W + gxj) * 16 : (int)0x80000000;
-                    emit_rows4<EPI, false, BIASED>(s4, a, ioj, 0, zlo);
-                }
-            }
-        }
-    };
-#define SESRQ_COMPUTE(B) compute(B, y0);
-    SESRQ_TILE_WALK_REST(MTH, buf0, buf1, SESRQ_COMPUTE)
-#undef SESRQ_COMPUTE
-}
+constexpr int H5_SW = MTW + 8;           // 2 + 64 + 2 halo, + over-read of the kx = 4..7 group
+constexpr int H5_SH = MTH + 4;
+#define SESRQ_KERNEL mfma_h5_kernel
+#define SESRQ_NARROW 0
+#include "sesrq_mfma_h5.inc"
+#undef SESRQ_KERNEL
+#undef SESRQ_NARROW
+#define SESRQ_KERNEL mfma_h5_kernel_q
+#define SESRQ_NARROW 1
+#include "sesrq_mfma_h5.inc"
+#undef SESRQ_KERNEL
+#undef SESRQ_NARROW
 
 // ------------------------------------------------------------------ last layer 5x5, 16 -> OC <= 4 (x2 nets), "pe-split"
 // The 16 accumulator rows are (PE p, output channel o) = row 4p + o (pack_mfma_frags, MFMA_H5P): ONE chain
@@ -709,83 +485,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void m
 // After the 18-bit clamp, a transpose-reduce over four pixel rows (12 permlane swaps + 12 adds) puts the
 // complete adder sum of row r in lane group r: every lane then requantises and stores 4 real outputs.
 //   K-chunk f < 5: lane group g = tap (ky f, kx g)     f = 5: (ky g, kx 4)     f = 6: g0 = (4, 4)
-template <int MODE>
-__global__ __launch_bounds__(256) void mfma_h5p_kernel(const ConvArgs a) {
-    constexpr int SW = MTW + 8;
-    constexpr int SH = MTH + 4;
-    __shared__ int4 buf0[SH * SW], buf1[SH * SW];
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
-    kernarg_warm<ConvArgs>();
-    const BlockXY bxy = xcd_block(a.inv_nx);
-    const int x0 = bxy.x * MTW, n_img = blockIdx.z;
-    const int4 *fr = a.afrag;
-    constexpr bool BIASED = mode_biased(MODE);
-    int4 ac = fr[0];
-    if constexpr (BIASED) { ac.x += MAGIC_I; ac.y += MAGIC_I; ac.z += MAGIC_I; ac.w += MAGIC_I; }
-    const float zlo = a.relu ? fmaxf(a.z_out, -128.f) : -128.f;
-    const int gx = x0 + 16 * w + n;
-    v4i A[7];
-#pragma unroll
-    for (int f = 0; f < 7; ++f) A[f] = ld_frag(fr + 4 + f * 64 + l);
-    LastStore ls;
-    ls.init(a, n_img, 0, gx, g);
-    auto compute = [&](const int4 *tile, int y0) __attribute__((always_inline)) {
-        const int col = 16 * w + n + g, colc = 16 * w + n + 4;
-        const v4i zero = {0, 0, 0, 0};
-        // merged: nothing can clamp -> the add constant rides in PE 0's accumulator rows
-        const v4i acc0 = (MODE == MERGED && g == 0) ? (v4i){ac.x, ac.y, ac.z, ac.w} : zero;
-        v4i B[5];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) B[r] = ld_frag(tile + r * SW + col);
-#pragma unroll
-        for (int y4 = 0; y4 < MTH; y4 += 4) {
-            unsigned s[4][4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int y = y4 + r;
-                B[(y + 4) % 5] = ld_frag(tile + (y + 4) * SW + col);
-                const v4i C5 = ld_frag(tile + (y + g) * SW + colc);
-                const v4i C6 = ld_frag(tile + (y + 4) * SW + colc);
-                v4i acc = acc0;
-#pragma unroll
-                for (int ky = 0; ky < 5; ++ky) acc = mfma(A[ky], B[(y + ky) % 5], acc);
-                acc = mfma(A[5], C5, acc);
-                acc = mfma(A[6], C6, acc);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if constexpr (MODE == MERGED) s[r][i] = (unsigned)acc[i];
-                    else if constexpr (MODE == GEN_ANY) s[r][i] = (unsigned)clampi3(acc[i], a.acc_lo, a.acc_hi);
-                    else s[r][i] = (unsigned)clampi3(acc[i], -131072, 131071);
-                }
-            }
-            int t[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                // lane halves trade rows {0,1} against {2,3}: u0 = row 0 | row 2, u1 = row 1 | row 3 (PE g + PE g^2)
-                v2u x = __builtin_amdgcn_permlane32_swap(s[0][i], s[2][i], false, false);
-                const unsigned u0 = x[0] + x[1];
-                x = __builtin_amdgcn_permlane32_swap(s[1][i], s[3][i], false, false);
-                const unsigned u1 = x[0] + x[1];
-                // odd lane groups trade with even ones: lane group r ends up with row r, all four PEs
-                x = __builtin_amdgcn_permlane16_swap(u0, u1, false, false);
-                t[i] = (int)(x[0] + x[1]);
-            }
-            int sf[4];
-            const int acv[4] = {ac.x, ac.y, ac.z, ac.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if constexpr (MODE == MERGED) sf[i] = t[i];
-                else if constexpr (MODE == GEN_ANY) sf[i] = clampi3(t[i], a.add_lo, a.add_hi) + acv[i];
-                else sf[i] = clampi3(t[i], -524288, 524287) + acv[i];
-            }
-            if (y0 + y4 < a.H) ls.store<BIASED>(sf, a, y0 + y4, zlo, y0 + y4 + g < a.H);
-        }
-    };
-#define SESRQ_COMPUTE(B) compute(B, y0);
-    using Stage = StageNHWC16<SH, SW, 2>;
-    SESRQ_TILE_WALK(Stage, buf0, buf1, SESRQ_COMPUTE)
-#undef SESRQ_COMPUTE
-}
+#define SESRQ_KERNEL mfma_h5p_kernel
+#define SESRQ_NARROW 0
+#include "sesrq_mfma_h5p.inc"
+#undef SESRQ_KERNEL
+#undef SESRQ_NARROW
+#define SESRQ_KERNEL mfma_h5p_kernel_q
+#define SESRQ_NARROW 1
+#include "sesrq_mfma_h5p.inc"
+#undef SESRQ_KERNEL
+#undef SESRQ_NARROW
 
 // ------------------------------------------------------------------ first layer 5x5, IC <= 4
 // The frame is quantised while it is staged (q0 = clamp8(rint(x/s0 + z0)), quan_func.py:225);
@@ -795,7 +504,10 @@ __global__ __launch_bounds__(256) void mfma_h5p_kernel(const ConvArgs a) {
 // distinct even banks and the two lane groups of a 32-lane half an odd number of rows apart, i.e. on the odd banks.
 // NCH: input channels as a compile-time count (1 and 3 are the reference's nets), or 4 = "a.ic of them, tested per channel":
 // the wave-uniform test put every channel's load and quantise code into a block of its own.
-template <int SRC, int SH, int SWP, int PITCH, int NCH>
+// NARROW: q0 is clamped to the width while staged (fp32 frames: quantize_in_bits_q; int8 frames: clipped, as the dot4 kernel does), and
+// pixels outside the frame get the pad word like an int8 frame's: the pad value is max(z0, -128) at EVERY width (quan_func.py:290),
+// which q0(0.0) = clamp_b(z0) is not when z0 < -2^(b-1)
+template <int SRC, int SH, int SWP, int PITCH, int NCH, bool NARROW = false>
 struct StageFrame {
     __device__ __forceinline__ static bool has_channel(const ConvArgs &a, int c) { return NCH < 4 ? c < NCH : c < a.ic; }
     static constexpr int NIT = (SH * SWP + 255) / 256;
@@ -804,13 +516,14 @@ struct StageFrame {
     // above (negative total offset) or below (past the plane: the range check sees voffset + soffset, tools/oob_probe.hip) -- then
     // loads 0.0f, and q0(0.0) = clamp8(z0) IS the pad value of the first layer (the zero point stands for 0.0): no row test, no
     // select of a pad word.  With one descriptor over the whole image a row below plane c would read plane c + 1.
-    static constexpr bool ZPAD = SRC == SRC_F32;
+    static constexpr bool ZPAD = SRC == SRC_F32 && !NARROW;
     unsigned raw[NIT][4];
     bool ok[NIT];
     int voff[NIT], ty[NIT];
     __amdgpu_buffer_rsrc_t rs, rsp[ZPAD ? (NCH < 4 ? NCH : 4) : 1];
     int row_bytes, plane_bytes;
     InQuantV qc;
+    float qlo_v, qhi_v;      // NARROW, fp32 frames: the width's clamp, pinned like qc
     __device__ __forceinline__ static float pin(float x) { float r = x; asm volatile("" : "+v"(r)); return r; }      // see in_vgpr()
     __device__ __forceinline__ void init(const ConvArgs &a, int n_img, int x0, int tid) {
         const size_t HW = (size_t)a.H * a.W;
@@ -827,6 +540,7 @@ struct StageFrame {
         if constexpr (SRC != SRC_I8) {
             qc.xlo = pin(a.fd.xlo); qc.xhi = pin(a.fd.xhi); qc.r = pin(a.fd.r); qc.ns = pin(-a.s_in); qc.r2 = pin(a.fd.r2); qc.z = pin(a.z_in);
             qc.magic = pin(MAGIC);
+            if constexpr (NARROW) { qlo_v = pin(a.qlo); qhi_v = pin(a.qhi); }
         }
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
@@ -882,7 +596,11 @@ struct StageFrame {
             unsigned b[4];
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                if constexpr (SRC == SRC_F32)
+                if constexpr (SRC == SRC_F32 && NARROW)
+                    b[c] = quantize_in_bits_q(__builtin_bit_cast(float, raw[it][c]), qc, qlo_v, qhi_v);
+                else if constexpr (NARROW)
+                    b[c] = (unsigned)clampi3((int)raw[it][c], (int)a.qlo, (int)a.qhi);
+                else if constexpr (SRC == SRC_F32)
                     b[c] = quantize_in_bits(__builtin_bit_cast(float, raw[it][c]), qc);
                 else if constexpr (SRC == SRC_I8D)      // upstream net's int8 output: its float value, then this net's input quantiser
                     b[c] = quantize_in_bits(__fmul_rn((float)(int)raw[it][c] - a.z_prev, a.s_prev), qc);
@@ -919,15 +637,16 @@ constexpr int F5_SWP = MTW + 8;         // staged pixel columns (2 halo + 64 + 2
 constexpr int F5_PITCH = F5_SH + 2;     // LDS column pitch in dwords (>= rows, = 2 mod 4)
 static_assert(F5_PITCH % 4 == 2 && 3 * F5_PITCH + F5_SH < 256, "column pitch: bank rule / ds_read2_b32 offset range");
 // RR (HYBS): the accumulator register whose rows can saturate (LayerPlan::risky_reg, sesrq_create), 4 = clamp all four
-template <int MODE, int SRC, bool RC, int NCH, int RR = 4>
+template <int MODE, int SRC, bool RC, int NCH, int RR = 4, bool NARROW = false>
 __device__ __forceinline__ void mfma_f5_body(const ConvArgs &a, int4 *buf0, int4 *buf1) {
+    static_assert(!NARROW || (SRC != SRC_I8D && (MODE == MERGED || MODE == GEN_ANY)), "width-aware first layer: fp32 / int8 frames, merged or per-PE sums");
     constexpr bool GENERAL = mode_general(MODE);
     constexpr int SH = F5_SH, SWP = F5_SWP, PITCH = F5_PITCH;
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, n = l & 15, g = l >> 4;
     kernarg_warm<ConvArgs>();
     const BlockXY bxy = xcd_block(a.inv_nx);
     const int x0 = bxy.x * MTW, n_img = blockIdx.z;
-    using Stage = StageFrame<SRC, SH, SWP, PITCH, NCH>;
+    using Stage = StageFrame<SRC, SH, SWP, PITCH, NCH, NARROW>;
     static_assert(F5_SH - F5_TH == 4, "StageFrame carries SH - TH = 4 rows");
     SESRQ_TILE_WALK_BEGIN(F5_TH, Stage)      // the frame loads of the first tile go out before anything else is fetched
     const int4 *fr = a.afrag;
@@ -961,7 +680,10 @@ __device__ __forceinline__ void mfma_f5_body(const ConvArgs &a, int4 *buf0, int4
     int tr_r, tr_c;
     f5_tr(g, tr_r, tr_c);
     const int addr0 = ((16 * w + n) * PITCH + g) * 4, addr1 = ((16 * w + n + tr_c) * PITCH + tr_r) * 4;     // bytes
-    const float zlo = a.relu ? fmaxf(a.z_next, -128.f) : -128.f;
+    const float qlo = NARROW ? a.qlo : -128.f;
+    const float zlo = a.relu ? fmaxf(a.z_next, qlo) : qlo;
+    QRange qr = {};
+    if constexpr (NARROW) qr = qrange(a);
     const int gx = x0 + 16 * w + n;
     // hybrid: s = (add constant + the three safe PEs) + clamp18(risky PE).  The risky PE's chain runs FIRST with the add constant as
     // its C input, is clamped against per-row bounds shifted by that constant, and is then the C input of the other chain: one
@@ -1022,7 +744,9 @@ __device__ __forceinline__ void mfma_f5_body(const ConvArgs &a, int4 *buf0, int4
                 }
             }
             // no separate residual tensor <=> zero[1] == -128 (sesrq_create) <=> this layer's z_next == -128: the cvt_pk_u8 epilogue
-            if constexpr (!RC && BIASED) {      // wave-uniform: the one-fma requant where (M, n) passed its proof
+            if constexpr (NARROW) {             // the generic epilogues with the width's range
+                emit_rows4_q<EPI_MID, RC, BIASED>(s4, a, io, y4, zlo, qr);
+            } else if constexpr (!RC && BIASED) {      // wave-uniform: the one-fma requant where (M, n) passed its proof
                 if (a.direct) emit_rows4<EPI_MID, RC, BIASED, 2>(s4, a, io, y4, zlo);
                 else emit_rows4<EPI_MID, RC, BIASED, 1>(s4, a, io, y4, zlo);
             } else {
@@ -1050,6 +774,17 @@ __global__ __launch_bounds__(256) void mfma_f5_kernel(const ConvArgs a) {
     __shared__ int4 buf0[(F5_SWP * F5_PITCH + 3) / 4], buf1[(F5_SWP * F5_PITCH + 3) / 4];
     mfma_f5_body<MODE, SRC, RC, NCH>(a, buf0, buf1);
 }
+// the width-aware first layer: merged sums on the 4-waves form, per-PE sums (run-time bounds) on the plain one, as at 8 bits
+template <int SRC, bool RC, int NCH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void mfma_f5_kernel_w4_q(const ConvArgs a) {
+    __shared__ int4 buf0[(F5_SWP * F5_PITCH + 3) / 4], buf1[(F5_SWP * F5_PITCH + 3) / 4];
+    mfma_f5_body<MERGED, SRC, RC, NCH, 4, true>(a, buf0, buf1);
+}
+template <int SRC, bool RC, int NCH>
+__global__ __launch_bounds__(256) void mfma_f5_kernel_q(const ConvArgs a) {
+    __shared__ int4 buf0[(F5_SWP * F5_PITCH + 3) / 4], buf1[(F5_SWP * F5_PITCH + 3) / 4];
+    mfma_f5_body<GEN_ANY, SRC, RC, NCH, 4, true>(a, buf0, buf1);
+}
 
 #ifdef SESRQ_STAMPS
 static int *g_stampbuf = nullptr;
@@ -1061,7 +796,7 @@ extern "C" int sesrq_debug_fetch_stamps(void *host, size_t bytes) {
 // co-resident workgroups per CU comes from the occupancy API for THIS kernel (registers / LDS differ a
 // lot between the merged and general variants), asked once per instantiation; a strip's row tiles are then cut into the largest
 // number of equal vertical runs that still fits.
-template <auto KERN>
+template <auto KERN, int REG = REG_MAIN>
 static void launch(ConvArgs a, hipStream_t st, int tile_h = MTH) {
     static const int blocks_per_cu = [] {
         int b = 0;
@@ -1071,7 +806,7 @@ static void launch(ConvArgs a, hipStream_t st, int tile_h = MTH) {
     const RunCut c = cut_runs(strips, row_tiles, a.N, a.wg_budget, blocks_per_cu * device_cu_count());
     a.chunk_tiles = c.chunk; a.run_q = c.run_q; a.run_rem = c.run_rem; a.inv_nx = c.inv_nx;
     dim3 grid(strips, c.k, a.N);
-    launch_kernel<KERN>(grid, dim3(256), 0, st, a);
+    launch_kernel<KERN, REG>(grid, dim3(256), 0, st, a);
 }
 
 // ---- Kernel selection: select_mfma names the instance a launch runs as plain template-argument values; dispatch_mfma maps them onto the
@@ -1081,6 +816,7 @@ struct Pick {
     int fam = FAM_H3, mode = MERGED, epi = EPI_MID;
     int src = SRC_F32, rc = 0, nch = 4, rr = 4;      // first layer: input form, writes the separate residual tensor, channels, HYBS register
     int fast = 0, nv = 4, outf = 0;                  // last layer's store form (LastStore); other layers keep these defaults
+    bool narrow = false;                             // width b < 8 (SESRQ_ENGINE_MFMA_Q): the width-aware kernels mfma_*_kernel_q
 };
 
 constexpr bool h3_built(int m, int e) { return m != HYBS && e != EPI_LAST; }                 // no 3x3 output layer; HYBS: first layer only
@@ -1100,6 +836,21 @@ constexpr bool h5_built(int m, int e, int fast, int nv, int outf) {
 constexpr bool f5_built(int m, int nch) { return m == GEN_STD || m == GEN_ANY || (m == GEN_TAP && nch == 4); }
 constexpr bool f5_w4_built(int m, int nch, int rr) { return m == HYBS ? nch == 3 : rr == 4 && (m == MERGED || (m == HYB && nch != 3)); }
 
+// The width-aware instances (mfma_*_kernel_q, registry REG_NARROW): merged sums, or per-PE sums with run-time bounds (GEN_ANY: any PE
+// widths, and what a one-risky-PE layer runs too -- no hybrid, no literal-bounds form, no taps: a debug forward of a narrow net runs on
+// the dot4 kernels).  Last layer: the merged kernel has the byte-run stores of the reference's two shuffles (the x2 pair map, 16
+// channels at x4) and their fp32 forms; everything else, and every per-PE last layer, the every-output-kind store.  Only what
+// select_mfma can ask for is built: tests/test_quan_bits_mfma.py fails for an instance no checked case launched.
+constexpr bool narrow_mode(int m) { return m == MERGED || m == GEN_ANY; }
+constexpr bool h3q_built(int m, int e) { return narrow_mode(m) && e != EPI_LAST; }
+constexpr bool h5q_built(int m, int e, int fast, int nv, int outf) {
+    if (!narrow_mode(m)) return false;
+    if (e != EPI_LAST) return fast == 0 && nv == 4 && outf == 0;
+    if (fast == 0) return outf == 0;
+    if (m != MERGED || !((fast == 2 && nv == 3) || (fast == 4 && nv == 4))) return false;
+    return outf == 0 || outf == 1 || (outf == 2 && nv == 3);
+}
+
 // Which kernel a launch runs.  c: choose_layer's per-call decisions (per-PE sums; the one-risky-PE hybrid applies; PE taps).  Returns 1
 // (set_error) where no MFMA kernel fits.
 static int select_mfma(const LayerPlan &lp, const LayerChoice &c, const ConvArgs &a, Pick &p) {
@@ -1109,6 +860,11 @@ static int select_mfma(const LayerPlan &lp, const LayerChoice &c, const ConvArgs
     const bool std_bits = a.acc_lo == -131072 && a.acc_hi == 131071 && a.add_lo == -524288 && a.add_hi == 524287;
     // ... and for a layer whose sums can leave the biased accumulator's range (LayerPlan::wide; choose_layer asks for per-PE sums then)
     p.mode = c.tap ? GEN_TAP : !c.general ? MERGED : (!std_bits || lp.wide) ? GEN_ANY : c.one_pe ? HYB : GEN_STD;
+    p.narrow = a.qhi < 127.f;      // ConvArgs carries the net's width; choose_layer sends a narrow layer here on SESRQ_ENGINE_MFMA_Q only
+    if (p.narrow) {
+        if (c.tap || c.one_pe || lp.wide) { set_error("mfma: no width-aware kernel for PE taps, the hybrid or a wide layer"); return 1; }
+        if (p.mode != MERGED) p.mode = GEN_ANY;
+    }
     const bool pesplit = lp.d_afrag_pesplit.get() && a.afrag == lp.d_afrag_pesplit.get();
     if (c.tap && pesplit) { set_error("mfma: the pe-split last-layer kernel has no PE taps"); return 1; }
     switch (lp.mfma_kind) {
@@ -1141,10 +897,11 @@ static int select_mfma(const LayerPlan &lp, const LayerChoice &c, const ConvArgs
             {   // FAST = the width of the PixelShuffle byte runs (the x2 pair map; 16 rows at x2 / x4) + 10 x the one-fma requant form;
                 // OUTF = the fp32 frame alone (1), with the x2 anchor add (2: the pair map of a 16-channel layer only)
                 const bool pair = last_pairmap(a.oc, a.ps);
-                const int run = pair ? 2 : (p.nv == 4 && (a.ps == 2 || a.ps == 4)) ? a.ps : 0;
+                int run = pair ? 2 : (p.nv == 4 && (a.ps == 2 || a.ps == 4)) ? a.ps : 0;
+                if (p.narrow && (p.mode != MERGED || (!pair && a.ps != 4))) run = 0;      // h5q_built
                 if (a.out_q && !a.out_f) p.fast = run;
                 else if (!a.out_q && a.out_f && !a.anchor) { p.fast = run; p.outf = run ? 1 : 0; }
-                else if (!a.out_q && a.out_f && pair && a.ic == 16) { p.fast = run; p.outf = 2; }
+                else if (!a.out_q && a.out_f && pair && a.ic == 16) { p.fast = run; p.outf = run ? 2 : 0; }      // (run == 0: a width-aware per-PE layer)
                 // the output requant as one fma (ConvArgs::direct: proven for this layer's (M, n)) into zero point -128, from biased sums
                 // (GEN_ANY sums carry no bias); an anchored net's int8-only store keeps the two-step requant, its fp32 store does not
                 if (p.fast && p.mode != GEN_ANY && a.z_out == -128.f && (!a.anchor || p.outf == 2)) p.fast += 10 * a.direct;
@@ -1154,7 +911,36 @@ static int select_mfma(const LayerPlan &lp, const LayerChoice &c, const ConvArgs
     }
 }
 
+static bool dispatch_mfma_q(const Pick &p, const ConvArgs &a, hipStream_t st) {
+    using Modes = Of<MERGED, GEN_ANY>;
+    using Epis = Of<EPI_MID, EPI_PRERES, EPI_LAST>;
+    using Srcs = Of<SRC_F32, SRC_I8>;
+    using Nchs = Of<1, 3, 4>;
+    switch (p.fam) {
+        case FAM_H3:
+            return pick([&](auto M, auto E) {
+                if constexpr (h3q_built(M, E)) return launch<mfma_h3_kernel_q<M, E>, REG_NARROW>(a, st), true; else return false;
+            }, Modes{}, p.mode, Epis{}, p.epi);
+        case FAM_H5:
+            return pick([&](auto M, auto E, auto F, auto V, auto O) {
+                if constexpr (h5q_built(M, E, F, V, O)) return launch<mfma_h5_kernel_q<M, E, F, V, O>, REG_NARROW>(a, st), true; else return false;
+            }, Modes{}, p.mode, Epis{}, p.epi, Of<0, 2, 4>{}, p.fast, Of<3, 4>{}, p.nv, Of<0, 1, 2>{}, p.outf);
+        case FAM_H5P:
+            return pick([&](auto M) { return launch<mfma_h5p_kernel_q<M>, REG_NARROW>(a, st), true; }, Modes{}, p.mode);
+        case FAM_F5:
+            return p.mode == GEN_ANY && pick([&](auto S, auto R, auto C) {
+                return launch<mfma_f5_kernel_q<S, R == 1, C>, REG_NARROW>(a, st, F5_TH), true;
+            }, Srcs{}, p.src, Of<0, 1>{}, p.rc, Nchs{}, p.nch);
+        case FAM_F5_W4:
+            return p.mode == MERGED && pick([&](auto S, auto R, auto C) {
+                return launch<mfma_f5_kernel_w4_q<S, R == 1, C>, REG_NARROW>(a, st, F5_TH), true;
+            }, Srcs{}, p.src, Of<0, 1>{}, p.rc, Nchs{}, p.nch);
+    }
+    return false;
+}
+
 static bool dispatch_mfma(const Pick &p, const ConvArgs &a, hipStream_t st) {
+    if (p.narrow) return dispatch_mfma_q(p, a, st);
     using Modes = Of<MERGED, GEN_STD, GEN_ANY, HYB, GEN_TAP, HYBS>;
     using Epis = Of<EPI_MID, EPI_PRERES, EPI_LAST>;
     using Srcs = Of<SRC_F32, SRC_I8, SRC_I8D>;

@@ -59,6 +59,15 @@ __device__ __forceinline__ unsigned quantize_in_bits(float x, const InQuantV &c)
     return __builtin_bit_cast(unsigned, __fadd_rn(__fadd_rn(q1, c.z), c.magic));
 }
 
+// The same at a width b < 8: clamp_b of the un-rounded value in front of the rounding add (integer bounds and a monotone rounding
+// commute).  The division form's proof carries over: clamp_b = clamp_b o clamp8.
+__device__ __forceinline__ unsigned quantize_in_bits_q(float x, const InQuantV &c, float qlo, float qhi) {
+    const float xc = med3(x, c.xlo, c.xhi);
+    const float q = __fmul_rn(xc, c.r);
+    const float q1 = __builtin_fmaf(__builtin_fmaf(c.ns, q, xc), c.r2, q);
+    return __builtin_bit_cast(unsigned, __fadd_rn(med3(__fadd_rn(q1, c.z), qlo, qhi), c.magic));
+}
+
 // A wave-uniform float pinned to a VGPR.  Why a VGPR: (1) hipcc 7.2 (clang 22) un-packs a v_pk_fma_f32 that sits in the shadow of an MFMA
 // into two v_fma_f32; when the packed form read BOTH scalar operands out of one SGPR pair the halves become fma(v, s[n], s[n+1]) -- two
 // scalar operands, illegal on gfx9 (a build error, never silent); (2) a scalar-operand v_fma / v_mul costs 2.2 ns per wave, the all-VGPR
@@ -260,6 +269,67 @@ __device__ __forceinline__ unsigned epi_preres_lut(const int s[4], unsigned rcwo
     return __builtin_bit_cast(unsigned, x) | (__builtin_bit_cast(unsigned, y) << 8);
 }
 
+// ---- width-aware epilogues (SESRQ_ENGINE_MFMA_Q at b < 8): the generic forms above with the activation range as run-time values.
+// clamp_b = clamp(., lo, hi) = [-2^(b-1), 2^(b-1) - 1]; the residual merge's offsets are half = 2^(b-1) and span = 2^b
+// (myQL/quan_func.py:249-252).  No cvt_pk_u8, one-fma or single-rounding form: those are proven for the 8-bit clamp.  Functions of
+// their own, so that the 8-bit instantiations compile from the same text as before.
+struct QRange {
+    float lo, hi, half;
+    float mg;      // MAGIC + 2^b - 128: the merge's rounding constant (epi_preres_q)
+};
+template <class AT>
+__device__ __forceinline__ QRange qrange(const AT &a) { return {a.qlo, a.qhi, a.qhalf, MAGIC + (a.qspan - 128.f)}; }
+
+// hidden layer: q = clamp_b(rint(relu(t) + z_next)); zlo = relu ? max(z_next, lo) : lo
+template <bool BIASED, class AT>
+__device__ __forceinline__ unsigned epi_mid_q(const int s[4], const AT &a, float zlo, const QRange &q) {
+    v2f v01, v23;
+    requant4<BIASED>(s, a.Mf, a.sh, a.z_next, v01, v23);
+    return round_pack(v01, v23, zlo, q.hi);
+}
+// layer-0 residual operand rc = clamp_b(rint(relu(t) - 2^(b-1)))
+template <bool BIASED, class AT>
+__device__ __forceinline__ unsigned epi_rc_q(const int s[4], const AT &a, const QRange &q) {
+    v2f v01, v23;
+    requant4<BIASED>(s, a.Mf, a.sh, -q.half, v01, v23);
+    return round_pack(v01, v23, q.lo, q.hi);
+}
+// layer L-2: u = rc + ic + 2^b.  The rounding constant MAGIC + (2^b - 128) leaves ic + 2^b - 128 in the low mantissa bits (two's
+// complement: it may be negative, the sum stays inside the binade), the integer add of the byte rc + 128 then gives the bit pattern of
+// the float MAGIC + u, u in [0, 2^(b+1) - 2] -- the input of the cvt-free second requant, as in epi_preres
+template <bool BIASED, class AT>
+__device__ __forceinline__ unsigned epi_preres_q(const int s[4], unsigned rcword, const AT &a, const QRange &q) {
+    v2f v01, v23;
+    requant4<BIASED>(s, a.Mf, a.sh, -q.half, v01, v23);
+    const unsigned rcx = rcword ^ 0x80808080u;                 // rc + 128 as unsigned bytes
+    const v2f mg = {q.mg, q.mg};
+    v2f c01 = {med3(v01[0], q.lo, q.hi), med3(v01[1], q.lo, q.hi)}, c23 = {med3(v23[0], q.lo, q.hi), med3(v23[1], q.lo, q.hi)};
+    c01 = c01 + mg; c23 = c23 + mg;
+    const int u[4] = {(int)(fbits(c01[0]) + (rcx & 0xffu)), (int)(fbits(c01[1]) + ((rcx >> 8) & 0xffu)),
+                      (int)(fbits(c23[0]) + ((rcx >> 16) & 0xffu)), (int)(fbits(c23[1]) + (rcx >> 24))};
+    v2f w01, w23;
+    requant4<true>(u, a.Mres, a.shres, a.z_merge, w01, w23);
+    return round_pack(w01, w23, q.lo, q.hi);
+}
+// The same with the second requant out of the table in LDS (fused trio).  The table keeps the 8-bit kernels' index rc + ic + 256 --
+// sesrq_create fills the window [256 - 2^b, 254 + 2^b] a width can reach with q4(u = index - 256 + 2^b) -- so the rounding constant
+// MAGIC + 256 + lut_addr and the signed-byte add are those of epi_preres_lut
+template <bool BIASED, class AT>
+__device__ __forceinline__ unsigned epi_preres_lut_q(const int s[4], unsigned rcword, const AT &a, float lut_magic, const QRange &q) {
+    typedef const unsigned char __attribute__((address_space(3))) *lds_u8_t;
+    v2f v01, v23;
+    requant4<BIASED>(s, a.Mf, a.sh, -q.half, v01, v23);
+    const v2f mg = {lut_magic, lut_magic};
+    v2f c01 = {med3(v01[0], q.lo, q.hi), med3(v01[1], q.lo, q.hi)}, c23 = {med3(v23[0], q.lo, q.hi), med3(v23[1], q.lo, q.hi)};
+    c01 = c01 + mg; c23 = c23 + mg;
+    const unsigned a0 = (fbits(c01[0]) & 0xffffu) + (unsigned)(int)(signed char)(rcword), a1 = (fbits(c01[1]) & 0xffffu) + (unsigned)(int)(signed char)(rcword >> 8);
+    const unsigned a2 = (fbits(c23[0]) & 0xffffu) + (unsigned)(int)(signed char)(rcword >> 16), a3 = (fbits(c23[1]) & 0xffffu) + (unsigned)((int)rcword >> 24);
+    typedef unsigned short v2us __attribute__((ext_vector_type(2)));
+    const v2us x = {(unsigned short)*(lds_u8_t)(size_t)a0, (unsigned short)*(lds_u8_t)(size_t)a2};
+    const v2us y = {(unsigned short)*(lds_u8_t)(size_t)a1, (unsigned short)*(lds_u8_t)(size_t)a3};
+    return __builtin_bit_cast(unsigned, x) | (__builtin_bit_cast(unsigned, y) << 8);
+}
+
 // PE clamp / sum / adder clamp / add constant               (myQL/quan_func.py:370,380-386,437,491)
 // NV: real rows of the lane (the last layer's three-row map leaves s[3] untouched: padding, never read)
 template <int MODE, int NV = 4, class AT>
@@ -434,6 +504,30 @@ __device__ __forceinline__ void emit_rows4_preres_rc(const int s4[4][4], const u
 #pragma unroll
     for (int r = 0; r < 4; ++r) w[r] = epi_preres<BIASED>(s4[r], rcw[r], a);
     store_rows4(io.out, io, y4, w);
+}
+
+// the width-aware rows (emit_rows4 with the epilogues epi_*_q)
+template <int EPI, bool RC, bool BIASED, class AT>
+__device__ __forceinline__ void emit_rows4_q(const int s4[4][4], const AT &a, const RowIO &io, int y4, float zlo, const QRange &q) {
+    unsigned w[4];
+    if constexpr (EPI == EPI_PRERES) {
+        unsigned rcw[4];
+        const v4u rv = __builtin_amdgcn_raw_buffer_load_b128(io.rc_in, io.voff, y4 * io.row_bytes, 0);
+        rcw[0] = rv[0]; rcw[1] = rv[1]; rcw[2] = rv[2]; rcw[3] = rv[3];
+        transpose4(rcw);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w[r] = epi_preres_q<BIASED>(s4[r], rcw[r], a, q);
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w[r] = epi_mid_q<BIASED>(s4[r], a, zlo, q);
+    }
+    store_rows4(io.out, io, y4, w);
+    if constexpr (RC) {
+        unsigned rw[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rw[r] = epi_rc_q<BIASED>(s4[r], a, q);
+        store_rows4(io.rc_out, io, y4, rw);
+    }
 }
 
 }  // namespace sesrq

@@ -49,7 +49,7 @@ int sesrq_net_quan_bits(const sesrq_net *net) { return net ? net->quan_bits : 0;
 const char *sesrq_layer_engine(const sesrq_net *net, int k) {
     if (!net || k < 0 || k >= net->L) return "";
     for (int j = std::max(1, k - 2); j <= k; ++j)
-        if (trio_active(net, nullptr) && net->trio_len[j] == 3 && k < j + 3) return "mfma-trio-merged";
+        if (trio_active(net, nullptr) && net->trio_len[j] == 3 && k < j + 3) return net->trio_engine.c_str();
     return net->layers[k].engine.c_str();
 }
 
@@ -139,7 +139,9 @@ static LayerChoice choose_layer(const sesrq_net *net, int k, const sesrq_taps *t
     const bool dbg = taps && (taps->pe_out[k] || taps->pe_add[k] || taps->overflow);
     const bool dot4_tap = taps && (taps->overflow || (k == 0 && (taps->act[0] || taps->shortcut)) || (k == L - 2 && taps->ic));
     // the layer has an MFMA kernel: the engine option, its shape, and for the first layer the proven division form
-    const bool mfma_ok = net->engine != SESRQ_ENGINE_DOT4 && lp.mfma_kind != MFMA_NONE && (k > 0 || net->fd.ok);
+    // a net of width b < 8 has MFMA kinds under SESRQ_ENGINE_MFMA_Q only (analyse_layer); its debug forward runs on the dot4 kernels
+    // (the width-aware flavours write no taps)
+    const bool mfma_ok = net->engine != SESRQ_ENGINE_DOT4 && lp.mfma_kind != MFMA_NONE && (k > 0 || net->fd.ok) && !(net->quan_bits < 8 && taps);
     LayerChoice c{};
     c.tap = dbg && !dot4_tap && mfma_ok && !pesplit;      // PE taps the per-PE MFMA kernels write themselves; the pe-split kernel has none
     c.mfma = mfma_ok && !dot4_tap && (!dbg || c.tap);     // every other tapped layer runs on the dot4 kernels
@@ -211,7 +213,8 @@ int forward_impl(const sesrq_net *net, const Call &c, void *workspace, size_t wo
             t.in = cur; t.out = buf.next(cur); t.rc_in = buf.RC;
             t.N = N; t.H = H; t.W = W;
             LaunchSlot slot(launch, announced, ev);
-            if (!slot.ok || launch_trio(t, (k + 2 == L - 2) ? EPI_PRERES : EPI_MID, st)) return 1;
+            const int epi_c = (k + 2 == L - 2) ? EPI_PRERES : EPI_MID;
+            if (!slot.ok || (net->quan_bits < 8 ? launch_trio_q(t, net->layers[k].base, epi_c, st) : launch_trio(t, epi_c, st))) return 1;
             cur = t.out;
             k += 3;
             continue;

@@ -25,14 +25,17 @@ struct Registry {
     std::mutex mu;
     std::deque<Entry> entries;      // deque: growth never moves an element (the atomics are addressed while others register)
 };
-Registry &registry() { static Registry r; return r; }      // constructed on first use: initialisation order of the translation units does not matter
+Registry &registry(int reg = REG_MAIN) {      // constructed on first use: initialisation order of the translation units does not matter
+    static Registry r[REG_LISTS];
+    return r[reg >= 0 && reg < REG_LISTS ? reg : REG_MAIN];
+}
 }  // namespace
 
 // The name of an instantiation: __PRETTY_FUNCTION__ prints a pointer-to-function template argument without ITS template arguments
 // ("&sesrq::mfma_h5_kernel"), so the name comes from the host stub's own symbol -- the kernels are namespace-scope templates, their stubs
 // weak symbols of the library's dynamic symbol table: dladdr + the C++ demangler give "void sesrq::__device_stub__mfma_h5_kernel<1, 2, 22,
 // 3>(sesrq::ConvArgs)", the same spelling a rocprofv3 kernel trace prints.  Fallback: the pretty-function text + the stub's address.
-int register_instance(const void *host_fn, const char *pretty_function) {
+int register_instance(const void *host_fn, const char *pretty_function, int reg) {
     std::string s;
     Dl_info info;
     if (dladdr(host_fn, &info) && info.dli_sname && info.dli_saddr == host_fn) {
@@ -64,7 +67,7 @@ int register_instance(const void *host_fn, const char *pretty_function) {
     for (size_t p; (p = s.find("sesrq::")) != std::string::npos;) s.erase(p, 7);
     for (size_t p; (p = s.find("__device_stub__")) != std::string::npos;) s.erase(p, 15);
     for (size_t p; (p = s.find("(anonymous namespace)::")) != std::string::npos;) s.erase(p, 23);
-    Registry &r = registry();
+    Registry &r = registry(reg);
     std::lock_guard<std::mutex> lk(r.mu);
     for (size_t i = 0; i < r.entries.size(); ++i)
         if (r.entries[i].fn == host_fn) return (int)i;
@@ -72,8 +75,8 @@ int register_instance(const void *host_fn, const char *pretty_function) {
     return (int)r.entries.size() - 1;
 }
 
-void count_launch(int id) {
-    Registry &r = registry();
+void count_launch(int id, int reg) {
+    Registry &r = registry(reg);
     if (id >= 0 && (size_t)id < r.entries.size()) r.entries[(size_t)id].launches.fetch_add(1, std::memory_order_relaxed);
 }
 
@@ -81,24 +84,30 @@ void count_launch(int id) {
 
 using namespace sesrq;
 
-extern "C" {
-
-int sesrq_instance_count(void) {
-    Registry &r = registry();
+static int list_count(int reg) {
+    Registry &r = registry(reg);
     std::lock_guard<std::mutex> lk(r.mu);
     return (int)r.entries.size();
 }
-
-const char *sesrq_instance_name(int i) {
-    Registry &r = registry();
+static const char *list_name(int reg, int i) {
+    Registry &r = registry(reg);
     std::lock_guard<std::mutex> lk(r.mu);
     return (i >= 0 && (size_t)i < r.entries.size()) ? r.entries[(size_t)i].name.c_str() : "";
 }
-
-long long sesrq_instance_launches(int i) {
-    Registry &r = registry();
+static long long list_launches(int reg, int i) {
+    Registry &r = registry(reg);
     std::lock_guard<std::mutex> lk(r.mu);
     return (i >= 0 && (size_t)i < r.entries.size()) ? r.entries[(size_t)i].launches.load(std::memory_order_relaxed) : -1;
 }
+
+extern "C" {
+
+int sesrq_instance_count(void) { return list_count(REG_MAIN); }
+const char *sesrq_instance_name(int i) { return list_name(REG_MAIN, i); }
+long long sesrq_instance_launches(int i) { return list_launches(REG_MAIN, i); }
+
+int sesrq_narrow_instance_count(void) { return list_count(REG_NARROW); }
+const char *sesrq_narrow_instance_name(int i) { return list_name(REG_NARROW, i); }
+long long sesrq_narrow_instance_launches(int i) { return list_launches(REG_NARROW, i); }
 
 }  // extern "C"

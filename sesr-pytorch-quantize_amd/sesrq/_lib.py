@@ -16,7 +16,8 @@ LIB_PATH = os.environ.get("SESRQ_LIB") or os.path.normpath(os.path.join(_HERE, "
 MAX_LAYERS = 16
 MAX_CH = 16
 F32, I8 = 0, 1
-ENGINE_AUTO, ENGINE_DOT4, ENGINE_MFMA = 0, 1, 2
+ENGINE_AUTO, ENGINE_DOT4, ENGINE_MFMA, ENGINE_MFMA_Q = 0, 1, 2, 3
+ENGINE_NAMES = {"auto": ENGINE_AUTO, "dot4": ENGINE_DOT4, "mfma": ENGINE_MFMA, "mfma-q": ENGINE_MFMA_Q}      # the --engine flag of sim.py / test.py
 VERDICT_SATURATION_FREE, VERDICT_BIASED_OK = 1, 2
 ABI_VERSION = 4
 
@@ -92,6 +93,9 @@ SYMBOLS = {
     "sesrq_instance_count": (C.c_int, []),
     "sesrq_instance_name": (C.c_char_p, [C.c_int]),
     "sesrq_instance_launches": (C.c_longlong, [C.c_int]),
+    "sesrq_narrow_instance_count": (C.c_int, []),
+    "sesrq_narrow_instance_name": (C.c_char_p, [C.c_int]),
+    "sesrq_narrow_instance_launches": (C.c_longlong, [C.c_int]),
     "sesrq_forward_debug": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                       C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(Taps)]),
     "sesrq_forward_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -187,6 +191,13 @@ class Library:
 
 _core = Library(LIB_PATH, SYMBOLS, "sesrq", "sesrq")
 lib, last_error, instances = _core.lib, _core.last_error, _core.instances
+
+
+def narrow_instances():
+    """{name: launches so far} of the width-aware kernels of ENGINE_MFMA_Q at quan_bits < 8: a list of their own."""
+    l = lib()
+    return {l.sesrq_narrow_instance_name(i).decode(): int(l.sesrq_narrow_instance_launches(i))
+            for i in range(l.sesrq_narrow_instance_count())}
 
 
 def check(rc: int, exc=RuntimeError) -> None:

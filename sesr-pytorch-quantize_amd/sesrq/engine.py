@@ -146,7 +146,8 @@ class Engine:
                                "there is no CPU fallback in this package")
         self.bundle = bundle
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
-        # define.py QUAN_BIT of the bundle: b < 8 is created by sesrq_create_q and runs on the dot4 kernels
+        # define.py QUAN_BIT of the bundle: b < 8 is created by sesrq_create_q and runs on the dot4 kernels, or, with
+        # engine=_lib.ENGINE_MFMA_Q, on the width-aware MFMA kernels and the fused trio (same bits; grouped submissions work there)
         self.quan_bits = int(getattr(bundle, "quan_bits", 8))
         if self.quan_bits != 8 and upstream is not None:
             raise ValueError(f"chained engines (upstream=) need 8-bit nets; this bundle is {self.quan_bits}-bit")

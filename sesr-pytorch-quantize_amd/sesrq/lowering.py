@@ -165,11 +165,13 @@ class SesrqGraphModule(torch.fx.GraphModule):
 
     def _sesrq_engine(self, device):
         cache = self.__dict__.setdefault("_sesrq_cache", {})
-        key = str(device)
+        # sesrq_engine_option: the kernel family (sesrq_options.engine) the model's engines are created with -- sim.py --engine
+        opt = int(self.__dict__.get("sesrq_engine_option", 0))
+        key = (str(device), opt)
         if key not in cache:
             from .engine import Engine
             bundle = lower(self)
-            cache[key] = Engine(bundle, device)
+            cache[key] = Engine(bundle, device, engine=opt)
         return cache[key]
 
     def sesrq_bundle(self) -> Bundle:

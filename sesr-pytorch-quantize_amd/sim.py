@@ -141,6 +141,9 @@ def main(argv=None):
                                    "switches select, plus weights and activation domains); all dump switches are turned on")
     ap.add_argument("--quan-bit", type=int, default=None, help="define.py QUAN_BIT for this run (2..8; default: define.QUAN_BIT): "
                                                                "the width of weights and activations")
+    ap.add_argument("--engine", choices=("auto", "dot4", "mfma", "mfma-q"), default="auto",
+                    help="kernel family of the integer path (sesrq_options.engine).  With --quan-bit below 8, auto, dot4 and mfma run the "
+                         "dot4 kernels; mfma-q runs the width-aware MFMA kernels and the fused trio (same bits, several times the rate)")
     args = ap.parse_args(argv)
     if args.quan_bit is not None:
         define.QUAN_BIT = args.quan_bit
@@ -151,6 +154,8 @@ def main(argv=None):
     if args.calib:
         STORE.load_output_pt(args.calib)
     model = splice(float_model(args.mflag, args.ckpt, args.params))
+    from sesrq import _lib
+    model.__dict__["sesrq_engine_option"] = _lib.ENGINE_NAMES[args.engine]
     as_image = is_image(args.input, args.image)
     if not args.input.endswith(".raw") and not as_image:
         inps = torch.load(args.input, weights_only=True, map_location="cpu") if args.input.endswith(".pt") else \

@@ -68,6 +68,10 @@ def main(argv=None):
     ap.add_argument("--save-output-pt", help="directory to write input.K.{min_val,max_val,scale,zero}.pt like the reference")
     ap.add_argument("--quan-bit", type=int, default=None, help="define.py QUAN_BIT for this run (2..8; default: define.QUAN_BIT): "
                                                                "the width the activation domains are calibrated for")
+    ap.add_argument("--engine", choices=("auto", "dot4", "mfma", "mfma-q"), default="auto",
+                    help="kernel family (sesrq_options.engine) the calibrated net is created with once its domains are known: other than "
+                         "auto, the net is built on the device and the kernels its layers resolve to are printed (mfma-q with --quan-bit "
+                         "below 8: the width-aware MFMA kernels, what sim.py --engine mfma-q then runs)")
     args = ap.parse_args(argv)
     if args.quan_bit is not None:
         define.QUAN_BIT = args.quan_bit
@@ -110,6 +114,10 @@ def report(args, model, scale, zero):
         STORE.save_output_pt(args.save_output_pt)
     if args.save_bundle:
         model._sesrq_cal.bundle(name=f"mflag{args.mflag}").save(args.save_bundle)
+    if args.engine != "auto":
+        from sesrq import Engine, _lib
+        cal = model._sesrq_cal
+        print("engines:", Engine(cal.bundle(name=f"mflag{args.mflag}"), cal.device, engine=_lib.ENGINE_NAMES[args.engine]).layer_engines())
     return scale, zero
 
 
