@@ -295,6 +295,11 @@ long long sesrq_instance_launches(int i);
 int sesrq_narrow_instance_count(void);
 const char *sesrq_narrow_instance_name(int i);
 long long sesrq_narrow_instance_launches(int i);
+/* ... and for the calibration convs with the quantised long-skip merge (sesrq_calib_conv_qadd / _slot_qadd below;
+ * tests/test_qat_calib_kernels.py): a list of their own as well, so that sesrq_instance_* lists what it listed before them. */
+int sesrq_qadd_instance_count(void);
+const char *sesrq_qadd_instance_name(int i);
+long long sesrq_qadd_instance_launches(int i);
 
 /* Name of the kernel the net resolved to for layer k ("dot4-general", "mfma-h3-merged", "mfma-trio-merged", ...). */
 const char *sesrq_layer_engine(const sesrq_net *net, int k);
@@ -386,6 +391,24 @@ int sesrq_calib_conv_slot(const sesrq_calib_conv_desc *d, const sesrq_calib_slot
  * (out: (N, C / r^2, H r, W r); r = 1: unshuffled; C must be a multiple of r^2). */
 int sesrq_calib_fakequant_slot(const float *in, float *out, int N, int C, int H, int W, int r, const sesrq_calib_slot *slot,
                                int quan_bits, void *stream);
+
+/* ---- quantised long-skip merge: the calibration pass of a QAT net ---------------------------------------------------
+ * quantize.prepare() replaces the long skip's AddOp of a QAT net by a QuantAdd (reference models/quantize_utils_pt.py:654-711):
+ * both operands pass an 8-bit symmetric fake-quantiser (SymmetricQuantizer.update_qparams :299-312, Round :150-166) before they are
+ * added.  Its scale is a constant of the net: test.py traces the prepared model in training mode, so the union of the two observers'
+ * ranges (:700-707) is evaluated once, on the state the checkpoint holds, and baked into the graph:
+ *   s = max(f32(max(|min(res.min, shortcut.min)|, |max(res.max, shortcut.max)|)) / f32(127.5), FLT_EPSILON)
+ * (sesr-pytorch-quantize_amd/models/quantize_utils_pt.py skip_quant_scale).  The two entry points below are sesrq_calib_conv_q and
+ * sesrq_calib_conv_slot with that merge in the conv's epilogue, in place of `+ skip`:
+ *   fq(t) = clamp(sign(t / s) * floor(|t / s| + 0.5), -128, 127) * s        fp32; round half away from zero; 8-bit at every quan_bits
+ *   out   = fq(act(conv)) + fq(skip)                                        fp32
+ * skip must not be NULL; skip_scale must be positive and finite -- otherwise 1 is returned and nothing is launched.  They run on
+ * kernels of their own (sesrq_qadd_instance_*); the plain entry points launch what they launched before.  Bit for bit
+ * tests/qat_calib_oracle.py. */
+int sesrq_calib_conv_qadd(const sesrq_calib_conv_desc *d, const float *in, const float *skip, float *out,
+                          int N, int H, int W, int quan_bits, float skip_scale, void *stream);
+int sesrq_calib_conv_slot_qadd(const sesrq_calib_conv_desc *d, const sesrq_calib_slot *slot, const float *in, const float *skip,
+                               float *out, int N, int H, int W, int quan_bits, float skip_scale, void *stream);
 
 /* ---- host scalar code of the path (load time) -------------------------------------- */
 

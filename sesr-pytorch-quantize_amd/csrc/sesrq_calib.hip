@@ -16,6 +16,12 @@
 // unspecified order); here the integer sum is exact and scaled once, so results agree to fp32 rounding
 // -- calibration is pinned to the reference within a tolerance, not bit for bit, and to
 // oracle/calib_oracle.py (the definition above) bit for bit.
+//
+// Quantised long-skip merge (QADD; the reference's QuantAdd, models/quantize_utils_pt.py:654-711, which quantize.prepare() puts in
+// place of the long skip's AddOp of a QAT net): with the constant 8-bit symmetric scale s of the net (a launch argument),
+//   fq(t) = clamp(sign(t/s) * floor(|t/s| + 0.5), -128, 127) * s        fp32, round half away from zero (Round, :150-166)
+//   v     = fq(v) + fq(skip)                                            in place of v + skip
+// fused into the same epilogue; tests/qat_calib_oracle.py is its definition, bit for bit.
 #include <algorithm>
 #include <cmath>
 
@@ -37,10 +43,17 @@ struct CalibArgs {
     float acc_lo, acc_hi, add_lo, add_hi;
     int relu;
     const sesrq_calib_slot *slot;   // device-resident pass: scale, zero, ss, the bounds and qbias come from here (NULL: the fields above)
+    float skip_s;           // QADD instantiations only: the QuantAdd's scale s
 };
 
-template <int K>
-__global__ __launch_bounds__(256) void calib_conv_kernel(const CalibArgs a) {
+// The QuantAdd's 8-bit symmetric fake-quantiser at scale s (NaN takes the lower clamp, as fmaxf(NaN, lo) = lo)
+__device__ __forceinline__ float skip_fakequant(float t, float s) {
+    const float u = __fdiv_rn(t, s), r = floorf(__fadd_rn(fabsf(u), 0.5f));
+    return __fmul_rn(fminf(fmaxf(u < 0.f ? -r : r, -128.f), 127.f), s);
+}
+
+template <int K, bool QADD>
+__device__ __forceinline__ void calib_conv_body(const CalibArgs a) {
     constexpr int R = K / 2, TW = 32, TH = 8, SW = TW + K - 1, SH = TH + K - 1;
     __shared__ int tile[SESRQ_MAX_CH][SH * SW];     // q = r - zero: |q| <= 2^30 + 2^7 (K = 5: 27 KiB)
     const int tid = threadIdx.x, lx = tid & 31, ly = tid >> 5;
@@ -83,10 +96,16 @@ __global__ __launch_bounds__(256) void calib_conv_kernel(const CalibArgs a) {
         float v = __fadd_rn(fminf(fmaxf(sum, add_lo), add_hi), qbias[o]);
         if (a.relu) v = fmaxf(v, 0.f);
         const size_t off = ((size_t)n * a.oc + o) * HW + (size_t)gy * a.W + gx;
-        if (a.skip) v = __fadd_rn(v, a.skip[off]);
+        if constexpr (QADD) v = __fadd_rn(skip_fakequant(v, a.skip_s), skip_fakequant(a.skip[off], a.skip_s));
+        else if (a.skip) v = __fadd_rn(v, a.skip[off]);
         a.out[off] = v;
     }
 }
+template <int K>
+__global__ __launch_bounds__(256) void calib_conv_kernel(const CalibArgs a) { calib_conv_body<K, false>(a); }
+// the same conv with the QuantAdd merge in its epilogue: kernels of their own (list REG_QADD), so that the plain ones stay as they are
+template <int K>
+__global__ __launch_bounds__(256) void calib_conv_qadd_kernel(const CalibArgs a) { calib_conv_body<K, true>(a); }
 
 // order-preserving float <-> uint map so that min/max can use integer atomics
 __device__ __forceinline__ unsigned f2ord(float f) { const unsigned u = __builtin_bit_cast(unsigned, f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
@@ -224,8 +243,30 @@ int sesrq_calib_minmax(const float *x, size_t n, float *out_min_max, void *scrat
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
-int sesrq_calib_conv_q(const sesrq_calib_conv_desc *d, const float *in, const float *skip, float *out, int N, int H, int W, int quan_bits,
-                       void *stream) {
+// One launch of the conv: the plain instantiation, or -- qadd -- the one whose epilogue merges the skip through the QuantAdd.
+static int launch_conv(const CalibArgs &a, int k, bool qadd, void *stream, const char *who) {
+    dim3 grid((a.W + 31) / 32, (a.H + 7) / 8, a.N);
+    hipStream_t st = (hipStream_t)stream;
+    if (qadd) {
+        if (k == 3) launch_kernel<calib_conv_qadd_kernel<3>, REG_QADD>(grid, dim3(256), 0, st, a);
+        else launch_kernel<calib_conv_qadd_kernel<5>, REG_QADD>(grid, dim3(256), 0, st, a);
+    } else {
+        if (k == 3) launch_kernel<calib_conv_kernel<3>>(grid, dim3(256), 0, st, a);
+        else launch_kernel<calib_conv_kernel<5>>(grid, dim3(256), 0, st, a);
+    }
+    if (hipGetLastError() != hipSuccess) { set_error(std::string(who) + ": launch failed"); return 1; }
+    return 0;
+}
+
+// The QuantAdd arguments of the _qadd entry points, refused before any launch
+static bool bad_skip_scale(const float *skip, float skip_scale, const char *who) {
+    if (!skip) { set_error(std::string(who) + ": the quantised merge needs a skip tensor"); return true; }
+    if (!(skip_scale > 0.f) || !std::isfinite(skip_scale)) { set_error(std::string(who) + ": skip_scale must be positive and finite"); return true; }
+    return false;
+}
+
+static int calib_conv_host(const sesrq_calib_conv_desc *d, const float *in, const float *skip, float *out, int N, int H, int W, int quan_bits,
+                           bool qadd, float skip_scale, void *stream) {
     if (quan_bits < 2 || quan_bits > 8) { set_error("sesrq_calib_conv_q: quan_bits must be 2..8"); return 1; }
     if (!d || !in || !out || !d->w || !d->qbias) { set_error("sesrq_calib_conv: null argument"); return 1; }
     if ((d->k != 3 && d->k != 5) || d->ic < 1 || d->ic > SESRQ_MAX_CH || d->oc < 1 || d->oc > SESRQ_MAX_CH) { set_error("sesrq_calib_conv: unsupported layer shape"); return 1; }
@@ -238,11 +279,19 @@ int sesrq_calib_conv_q(const sesrq_calib_conv_desc *d, const float *in, const fl
     a.qlo = -(float)(1 << (quan_bits - 1)); a.qhi = (float)((1 << (quan_bits - 1)) - 1);
     a.acc_lo = d->acc_lo; a.acc_hi = d->acc_hi; a.add_lo = d->add_lo; a.add_hi = d->add_hi; a.relu = d->relu;
     a.slot = nullptr;
-    dim3 grid((W + 31) / 32, (H + 7) / 8, N);
-    if (d->k == 3) launch_kernel<calib_conv_kernel<3>>(grid, dim3(256), 0, (hipStream_t)stream, a);
-    else launch_kernel<calib_conv_kernel<5>>(grid, dim3(256), 0, (hipStream_t)stream, a);
-    if (hipGetLastError() != hipSuccess) { set_error("sesrq_calib_conv: launch failed"); return 1; }
-    return 0;
+    a.skip_s = skip_scale;
+    return launch_conv(a, d->k, qadd, stream, "sesrq_calib_conv");
+}
+
+int sesrq_calib_conv_q(const sesrq_calib_conv_desc *d, const float *in, const float *skip, float *out, int N, int H, int W, int quan_bits,
+                       void *stream) {
+    return calib_conv_host(d, in, skip, out, N, H, W, quan_bits, false, 0.f, stream);
+}
+
+int sesrq_calib_conv_qadd(const sesrq_calib_conv_desc *d, const float *in, const float *skip, float *out, int N, int H, int W, int quan_bits,
+                          float skip_scale, void *stream) {
+    if (bad_skip_scale(skip, skip_scale, "sesrq_calib_conv_qadd")) return 1;
+    return calib_conv_host(d, in, skip, out, N, H, W, quan_bits, true, skip_scale, stream);
 }
 
 int sesrq_calib_conv(const sesrq_calib_conv_desc *d, const float *in, const float *skip, float *out, int N, int H, int W, void *stream) {
@@ -305,8 +354,8 @@ int sesrq_calib_observe_slot(const float *x, size_t n, sesrq_calib_slot *slot, c
     return 0;
 }
 
-int sesrq_calib_conv_slot(const sesrq_calib_conv_desc *d, const sesrq_calib_slot *slot, const float *in, const float *skip, float *out,
-                          int N, int H, int W, int quan_bits, void *stream) {
+static int calib_conv_slot(const sesrq_calib_conv_desc *d, const sesrq_calib_slot *slot, const float *in, const float *skip, float *out,
+                           int N, int H, int W, int quan_bits, bool qadd, float skip_scale, void *stream) {
     if (quan_bits < 2 || quan_bits > 8) { set_error("sesrq_calib_conv_slot: quan_bits must be 2..8"); return 1; }
     if (!d || !slot || !in || !out || !d->w) { set_error("sesrq_calib_conv_slot: null argument"); return 1; }
     if ((d->k != 3 && d->k != 5) || d->ic < 1 || d->ic > SESRQ_MAX_CH || d->oc < 1 || d->oc > SESRQ_MAX_CH) { set_error("sesrq_calib_conv_slot: unsupported layer shape"); return 1; }
@@ -317,11 +366,19 @@ int sesrq_calib_conv_slot(const sesrq_calib_conv_desc *d, const sesrq_calib_slot
     a.qlo = -(float)(1 << (quan_bits - 1)); a.qhi = (float)((1 << (quan_bits - 1)) - 1);
     a.relu = d->relu;
     a.slot = slot;
-    dim3 grid((W + 31) / 32, (H + 7) / 8, N);
-    if (d->k == 3) launch_kernel<calib_conv_kernel<3>>(grid, dim3(256), 0, (hipStream_t)stream, a);
-    else launch_kernel<calib_conv_kernel<5>>(grid, dim3(256), 0, (hipStream_t)stream, a);
-    if (hipGetLastError() != hipSuccess) { set_error("sesrq_calib_conv_slot: launch failed"); return 1; }
-    return 0;
+    a.skip_s = skip_scale;
+    return launch_conv(a, d->k, qadd, stream, "sesrq_calib_conv_slot");
+}
+
+int sesrq_calib_conv_slot(const sesrq_calib_conv_desc *d, const sesrq_calib_slot *slot, const float *in, const float *skip, float *out,
+                          int N, int H, int W, int quan_bits, void *stream) {
+    return calib_conv_slot(d, slot, in, skip, out, N, H, W, quan_bits, false, 0.f, stream);
+}
+
+int sesrq_calib_conv_slot_qadd(const sesrq_calib_conv_desc *d, const sesrq_calib_slot *slot, const float *in, const float *skip, float *out,
+                               int N, int H, int W, int quan_bits, float skip_scale, void *stream) {
+    if (bad_skip_scale(skip, skip_scale, "sesrq_calib_conv_slot_qadd")) return 1;
+    return calib_conv_slot(d, slot, in, skip, out, N, H, W, quan_bits, true, skip_scale, stream);
 }
 
 int sesrq_calib_fakequant_slot(const float *in, float *out, int N, int C, int H, int W, int r, const sesrq_calib_slot *slot, int quan_bits,

@@ -26,7 +26,8 @@ extern thread_local KernelEvents tl_kernel_events;
 // (Round 4 shipped 9.5 M wrong bytes in an instantiation -- the int8-only last layer -- that 168 green tests never selected.)
 // REG: which list the kernel is entered in.  REG_NARROW = the width-aware kernels of SESRQ_ENGINE_MFMA_Q (sesrq_narrow_instance_*): a list
 // of their own with a matrix of their own (tests/test_quan_bits_mfma.py), so that sesrq_instance_* stays the list tests/test_instances.py drives.
-enum { REG_MAIN = 0, REG_NARROW = 1, REG_LISTS = 2 };
+// REG_QADD = the calibration convs that merge the long skip through the QuantAdd (sesrq_qadd_instance_*; tests/test_qat_calib_kernels.py).
+enum { REG_MAIN = 0, REG_NARROW = 1, REG_QADD = 2, REG_LISTS = 3 };
 int register_instance(const void *host_fn, const char *pretty_function, int reg = REG_MAIN);
 void count_launch(int id, int reg = REG_MAIN);
 template <auto KERN, int REG = REG_MAIN>

@@ -110,4 +110,8 @@ int sesrq_narrow_instance_count(void) { return list_count(REG_NARROW); }
 const char *sesrq_narrow_instance_name(int i) { return list_name(REG_NARROW, i); }
 long long sesrq_narrow_instance_launches(int i) { return list_launches(REG_NARROW, i); }
 
+int sesrq_qadd_instance_count(void) { return list_count(REG_QADD); }
+const char *sesrq_qadd_instance_name(int i) { return list_name(REG_QADD, i); }
+long long sesrq_qadd_instance_launches(int i) { return list_launches(REG_QADD, i); }
+
 }  // extern "C"

@@ -15,11 +15,20 @@ constructor tests for, so both quantisers are per-TENSOR, :376-404):
                     return q * s
     y = conv2d(fq(x, -128, 127), fq(w, -127, 127), bias)
 
-Only this inference-time fold is implemented -- observers' running averages, the straight-through backward, the
-asymmetric / histogram / per-channel variants, QuantReLU / QuantAdd and BN fusing are training machinery outside the
-hot path ("out of scope").  The QuantAdd state of the two long-skip adds (``add_residual``,
-``add_upsampled_input``) that a QAT checkpoint also carries is accepted and ignored by the loader (sim.py): the
-integer path merges the skip in the integer domain and never evaluates it.
+Only this inference-time fold and the QuantAdd's constant scale (below) are implemented -- observers' running averages,
+the straight-through backward, the asymmetric / histogram / per-channel variants, QuantReLU and BN fusing are training
+machinery outside the hot path ("out of scope").
+
+QuantAdd (:654-711): ``prepare`` also replaces the long skip's ``AddOp`` by a ``QuantAdd`` (``add_residual``), and the
+reference's calibration pass (test.py, mode 0) therefore adds two fake-quantised tensors.  test.py traces the prepared
+model with torch.fx while it is in training mode; buffers are not proxied, so the union of the two observers' ranges
+(:700-707) and ``update_qparams`` (:299-312) run once, at trace time, on the observer state the checkpoint holds, and the
+scale enters the graph as a constant -- the moving-average updates of the observers are dead writes nothing reads back.
+``skip_quant_scale`` recomputes that constant from a state_dict (the ``activation_quantizer.scale`` the checkpoint stores
+differs from it in the last digits and is not what the trace uses); sesrq.calibrate.Calibrator(skip_quant_scale=...)
+applies it.  The integer path merges the skip in the integer domain and never evaluates the QuantAdd, so the loader
+(sim.py) still drops the ``add_residual.*`` / ``add_upsampled_input.*`` entries before ``load_state_dict``; the second add
+is commented out of the reference's forward.
 """
 import copy
 
@@ -97,6 +106,28 @@ def prepare(model, inplace=False, a_bits=8, w_bits=8, q_type=0, q_level=0, **uns
                 wrap(child)
     wrap(model)
     return model
+
+
+SKIP_ADD = "add_residual."
+SKIP_OBSERVER_KEYS = tuple(SKIP_ADD + k for k in ("observer_res.min_val", "observer_res.max_val", "observer_shortcut.min_val",
+                                                  "observer_shortcut.max_val"))
+
+
+def skip_quant_scale(sd):
+    """The constant scale of the long skip's QuantAdd, from the four observer extrema of a QAT state_dict (reference
+    QuantAdd.forward :700-707, SymmetricQuantizer.update_qparams :299-312, a_bits = 8: test.py:62), in fp32 as the reference
+    forms it:  s = max(max(|min(res.min, shortcut.min)|, |max(res.max, shortcut.max)|) / 127.5, eps_f32).
+    None for a state_dict without ``add_residual.*`` entries (not a QAT checkpoint); ValueError when some of the four are missing."""
+    if not any(k.startswith(SKIP_ADD) for k in sd):
+        return None
+    missing = [k for k in SKIP_OBSERVER_KEYS if k not in sd]
+    if missing:
+        raise ValueError(f"QAT state_dict: the QuantAdd's observer state is incomplete, missing {missing}")
+    r_min, r_max, s_min, s_max = (torch.as_tensor(sd[k], dtype=torch.float32).reshape(-1)[0] for k in SKIP_OBSERVER_KEYS)
+    lo, hi = torch.min(r_min, s_min), torch.max(r_max, s_max)
+    eps = torch.tensor(torch.finfo(torch.float32).eps, dtype=torch.float32)
+    s = torch.max(torch.max(torch.abs(lo), torch.abs(hi)) / 127.5, eps)
+    return float(s)
 
 
 def is_qat_state_dict(sd):

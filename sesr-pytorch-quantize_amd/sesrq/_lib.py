@@ -96,6 +96,9 @@ SYMBOLS = {
     "sesrq_narrow_instance_count": (C.c_int, []),
     "sesrq_narrow_instance_name": (C.c_char_p, [C.c_int]),
     "sesrq_narrow_instance_launches": (C.c_longlong, [C.c_int]),
+    "sesrq_qadd_instance_count": (C.c_int, []),
+    "sesrq_qadd_instance_name": (C.c_char_p, [C.c_int]),
+    "sesrq_qadd_instance_launches": (C.c_longlong, [C.c_int]),
     "sesrq_forward_debug": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                       C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(Taps)]),
     "sesrq_forward_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -115,6 +118,10 @@ SYMBOLS = {
     "sesrq_calib_observe_slot": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(CalibDomainDesc), C.c_void_p]),
     "sesrq_calib_conv_slot": (C.c_int, [C.POINTER(CalibConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                         C.c_int, C.c_int, C.c_void_p]),
+    "sesrq_calib_conv_qadd": (C.c_int, [C.POINTER(CalibConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, C.c_float, C.c_void_p]),
+    "sesrq_calib_conv_slot_qadd": (C.c_int, [C.POINTER(CalibConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                             C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "sesrq_calib_fakequant_slot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                              C.c_void_p]),
     "sesrq_requant_const": (C.c_int, [C.c_double, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
@@ -198,6 +205,12 @@ def narrow_instances():
     l = lib()
     return {l.sesrq_narrow_instance_name(i).decode(): int(l.sesrq_narrow_instance_launches(i))
             for i in range(l.sesrq_narrow_instance_count())}
+
+
+def qadd_instances():
+    """{name: launches so far} of the calibration convs with the quantised long-skip merge: a list of their own."""
+    l = lib()
+    return {l.sesrq_qadd_instance_name(i).decode(): int(l.sesrq_qadd_instance_launches(i)) for i in range(l.sesrq_qadd_instance_count())}
 
 
 def check(rc: int, exc=RuntimeError) -> None:

@@ -20,7 +20,13 @@ extrema, the running extrema and the domain derived from them (sesrq_calib_obser
 (sesrq_calib_conv_slot / _fakequant_slot).  Nothing waits on the host until `finalize()` (or `sync()`) reads the slots back.  Bit for
 bit the results of `observe` on the same frames: per-batch (scale, zero), mode-0 output, running min/max, domains, bundle.  Frames
 come as fp32 (N, C, H, W), 12-bit RGGB raw frames (decoded on the device into the reference's fp32 input, sesrq.raw) or 8-bit images
-(sesrq.image).  min/max only: the entropy variant keeps the host pass."""
+(sesrq.image).  min/max only: the entropy variant keeps the host pass.
+
+QAT nets (`skip_quant_scale`): quantize.prepare() replaces the long skip's AddOp of a QAT net by a fake-quantising QuantAdd (reference
+models/quantize_utils_pt.py:654-711), so the reference's mode-0 pass adds two quantised tensors: x_{L-1} = fq(a_{L-2}) + fq(a_0), fq
+the 8-bit symmetric quantiser at the constant scale the checkpoint's observer state gives (models/quantize_utils_pt.skip_quant_scale).
+With the scale set, the conv in front of the merge runs sesrq_calib_conv_qadd / _slot_qadd, which fuse it into their epilogue, on
+both passes and for every kind of frame."""
 from __future__ import annotations
 
 import ctypes as C
@@ -96,10 +102,22 @@ def entropy_range(hist: np.ndarray, lo: float, hi: float, levels: int = 256, str
 class Calibrator:
     def __init__(self, weights: Sequence[np.ndarray], biases: Sequence[np.ndarray], pixel_shuffle: int = 1,
                  device: Optional[torch.device] = None, pe_acc_bits: int = 18, pe_add_bits: int = 20, bias_bits: int = 16,
-                 quantized=None, method: str = "minmax", bins: int = 2048, quan_bits: int = 8):
+                 quantized=None, method: str = "minmax", bins: int = 2048, quan_bits: int = 8,
+                 skip_quant_scale: Optional[float] = None):
         """weights: float collapsed convs (quantised here), or None with `quantized` = [(Wq int8, weight scale)]
         when quantize_model_weight already did it.  quan_bits: define.py QUAN_BIT, the width b of weights and activations
-        (scale = range / (2^b - 1), zero = -2^(b-1) - round(min / scale), clamps to [-2^(b-1), 2^(b-1) - 1]; test.py:189-215)."""
+        (scale = range / (2^b - 1), zero = -2^(b-1) - round(min / scale), clamps to [-2^(b-1), 2^(b-1) - 1]; test.py:189-215).
+        skip_quant_scale: None = the float long skip x_{L-1} = a_{L-2} + a_0; a positive finite float s (taken as fp32) = the QuantAdd
+        of a QAT net, x_{L-1} = fq(a_{L-2}) + fq(a_0) with fq(t) = clamp(round_half_away(t / s), -128, 127) * s, in observe, enqueue,
+        enqueue_raw and enqueue_image alike.  The QuantAdd stays 8-bit at every quan_bits, as the reference's does (its test.py:62
+        prepares the model with a_bits=8 whatever QUAN_BIT is); no reference record of a QAT net exists below b = 8, so there this
+        is pinned to the oracle alone."""
+        if skip_quant_scale is not None:
+            s32 = float(np.float32(skip_quant_scale)) if isinstance(skip_quant_scale, (int, float, np.floating)) else float("nan")
+            if not (np.isfinite(s32) and s32 > 0.0):
+                raise ValueError("Calibrator: skip_quant_scale must be None or a positive finite float (in fp32)")
+            skip_quant_scale = s32
+        self.skip_quant_scale = skip_quant_scale
         if not torch.cuda.is_available():
             raise RuntimeError("sesrq.Calibrator needs a HIP device (no CPU fallback)")
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -230,9 +248,13 @@ class Calibrator:
                                       add_lo=float(np.float32((lo_s - zero) * scale * sw)), add_hi=float(np.float32((hi_s - zero) * scale * sw)),
                                       relu=int(k != L - 1))
             out = torch.empty((N, oc, H, W), dtype=torch.float32, device=self.device)
-            skip = first if k == L - 2 else None          # long skip: x_{L-1} = a_{L-2} + a_0 (float AddOp)
-            _lib.check(lib.sesrq_calib_conv_q(C.byref(desc), a.data_ptr(), skip.data_ptr() if skip is not None else None,
-                                              out.data_ptr(), N, H, W, self.quan_bits, st))
+            skip = first if k == L - 2 else None          # long skip: x_{L-1} = a_{L-2} + a_0 (float AddOp, or the QuantAdd)
+            if skip is not None and self.skip_quant_scale is not None:
+                _lib.check(lib.sesrq_calib_conv_qadd(C.byref(desc), a.data_ptr(), skip.data_ptr(), out.data_ptr(), N, H, W,
+                                                     self.quan_bits, self.skip_quant_scale, st))
+            else:
+                _lib.check(lib.sesrq_calib_conv_q(C.byref(desc), a.data_ptr(), skip.data_ptr() if skip is not None else None,
+                                                  out.data_ptr(), N, H, W, self.quan_bits, st))
             if k == 0:
                 first = out
             a = out
@@ -287,9 +309,13 @@ class Calibrator:
         for k in range(L):
             _lib.check(lib.sesrq_calib_observe_slot(a.data_ptr(), a.numel(), self._slot(k), C.byref(self._dom_desc[k]), st))
             dst = acts[k] if k < L - 1 else last
-            skip = acts[0] if k == L - 2 else None          # long skip: x_{L-1} = a_{L-2} + a_0 (float AddOp)
-            _lib.check(lib.sesrq_calib_conv_slot(C.byref(self._conv_desc[k]), self._slot(k), a.data_ptr(),
-                                                 skip.data_ptr() if skip is not None else None, dst.data_ptr(), N, H, W, qb, st))
+            skip = acts[0] if k == L - 2 else None          # long skip: x_{L-1} = a_{L-2} + a_0 (float AddOp, or the QuantAdd)
+            if skip is not None and self.skip_quant_scale is not None:
+                _lib.check(lib.sesrq_calib_conv_slot_qadd(C.byref(self._conv_desc[k]), self._slot(k), a.data_ptr(), skip.data_ptr(),
+                                                          dst.data_ptr(), N, H, W, qb, self.skip_quant_scale, st))
+            else:
+                _lib.check(lib.sesrq_calib_conv_slot(C.byref(self._conv_desc[k]), self._slot(k), a.data_ptr(),
+                                                     skip.data_ptr() if skip is not None else None, dst.data_ptr(), N, H, W, qb, st))
             a = dst
         _lib.check(lib.sesrq_calib_observe_slot(a.data_ptr(), a.numel(), self._slot(L), C.byref(self._dom_desc[L]), st))
         if r > 1:      # the quantiser in front of PixelShuffle, written shuffled (test.py:90-91)

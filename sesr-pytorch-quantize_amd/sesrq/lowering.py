@@ -127,7 +127,8 @@ def graph_mode(gm: torch.fx.GraphModule) -> int:
 
 def lower_calibration(gm: torch.fx.GraphModule, device, store=STORE):
     """A mode-0 graph (reference test.py:79-106: quantiser before every conv and before PixelShuffle, PE
-    split, bias bypass; float long skip) -> sesrq.calibrate.Calibrator."""
+    split, bias bypass; long skip) -> sesrq.calibrate.Calibrator.  The long skip is the float add, or -- the graph module carries
+    `sesrq_skip_quant_scale` (test.py sets it for a QAT checkpoint) -- the QuantAdd at that scale."""
     from .calibrate import Calibrator
     modules = dict(gm.named_modules())
     convs = [n for n in gm.graph.nodes if n.op == "call_module" and type(modules[n.target]) is nn.Conv2d]
@@ -156,7 +157,8 @@ def lower_calibration(gm: torch.fx.GraphModule, device, store=STORE):
             ps = int(modules[n.target].upscale_factor)
     import define
     return Calibrator(None, biases, ps, device, pe_acc_bits=widths[1], pe_add_bits=widths[0], bias_bits=widths[2],
-                      quantized=quantized, quan_bits=int(define.QUAN_BIT))
+                      quantized=quantized, quan_bits=int(define.QUAN_BIT),
+                      skip_quant_scale=gm.__dict__.get("sesrq_skip_quant_scale"))
 
 
 class SesrqGraphModule(torch.fx.GraphModule):

@@ -41,9 +41,10 @@ def float_model(mflag, ckpt=None, params=None):
         raise ValueError(f"MFLAG {mflag}: only 3 (nrdm_3), 4 (nrdm_6), 5 (SESR x4) and 6 (SESR x2) have an integer path")
     model = MODELS[mflag]()
     model.train()
-    if ckpt is not None:
-        load_checkpoint(model, ckpt, mflag)
+    skip_s = load_checkpoint(model, ckpt, mflag) if ckpt is not None else None
     model.collapse()
+    # a QAT checkpoint's QuantAdd scale, for the calibration pass (test.py); the integer path does not read it
+    model.__dict__["sesrq_skip_quant_scale"] = skip_s
     if params is not None:
         z = np.load(params, allow_pickle=False)
         convs = [model.conv_first.conv_expand] + [b.conv_expand for b in model.residual_block] + [model.conv_last.conv_expand]
@@ -68,13 +69,21 @@ def load_checkpoint(model, ckpt, mflag):
     the folded weights differ from a fold of the raw conv weights by tens to hundreds of INT8 weights per net.  The
     reference selects this with its ``qatf`` switch; here the checkpoint itself decides (models/quantize_utils_pt.py).
     Entries of the two long-skip adds' quantisers (``add_residual.*``, ``add_upsampled_input.*``: QuantAdd state) are
-    dropped: the integer path merges the skip in the integer domain and never evaluates them.  Any other key mismatch (a checkpoint of another net / --mflag) is refused -- nothing may leave
+    dropped: the integer path merges the skip in the integer domain and never evaluates them.  Returns the constant scale of
+    ``add_residual``'s QuantAdd (quantize.skip_quant_scale; None for a checkpoint without one), which the calibration pass
+    of a QAT net needs (test.py); for an incomplete observer state the ValueError of skip_quant_scale is returned in its
+    place, not raised -- the integer path has no use for the scale and loads such a checkpoint as before, test.py raises it
+    when it needs the scale.  Any other key mismatch (a checkpoint of another net / --mflag) is refused -- nothing may leave
     random-init weights behind."""
     sd = torch.load(ckpt, weights_only=True, map_location="cpu")
     if isinstance(sd, dict) and "state_dict" in sd:
         sd = sd["state_dict"]
     if not isinstance(sd, dict):
         raise ValueError(f"{ckpt}: not a state_dict")
+    try:
+        skip_s = quantize.skip_quant_scale(sd)
+    except ValueError as e:     # an incomplete QuantAdd state: no obstacle here, the integer path never evaluates it
+        skip_s = e
     if quantize.is_qat_state_dict(sd):
         quantize.prepare(model, inplace=True, a_bits=QUAN_BIT, w_bits=QUAN_BIT, q_type=0, q_level="C")
         sd = {k: v for k, v in sd.items() if not k.startswith(QAT_SKIP_ADDS)}
@@ -86,6 +95,7 @@ def load_checkpoint(model, ckpt, mflag):
         raise ValueError(f"{ckpt} does not fit the MFLAG {mflag} net ({type(model).__module__}): missing "
                          f"{res.missing_keys[:3]}{'...' if len(res.missing_keys) > 3 else ''}, unexpected "
                          f"{res.unexpected_keys[:3]}{'...' if len(res.unexpected_keys) > 3 else ''}")
+    return skip_s
 
 
 def splice(model, qmode=1):

@@ -10,6 +10,12 @@ the mean line) before the domains are printed.
                    --save-bundle x4.bundle.npz
     python test.py --mflag 3 --params tests/golden/nrdm_3.params.npz --input a_132_128.raw b_132_128.raw --gt gt16.npy
     python test.py --mflag 6 --params ... --input lr0.png lr1.png --gt hr0.png hr1.png
+    python test.py --mflag 3 --ckpt nrdm_3_qat_G.pth --input a_132_128.raw          # a QAT checkpoint: the long skip is its QuantAdd
+
+A QAT checkpoint (``*_qat_G.pth``) decides for itself, as it does for the fold: quantize.prepare() puts a fake-quantising QuantAdd in
+place of the long skip's add, and the pass merges the skip through it at the scale the checkpoint's observer state gives
+(models/quantize_utils_pt.skip_quant_scale; one line names the scale used).  ``--params`` files carry no such state:
+``--skip-quant-scale S`` gives it by hand, ``--float-skip`` forces the float add.
 """
 import argparse
 import types
@@ -72,6 +78,10 @@ def main(argv=None):
                     help="kernel family (sesrq_options.engine) the calibrated net is created with once its domains are known: other than "
                          "auto, the net is built on the device and the kernels its layers resolve to are printed (mfma-q with --quan-bit "
                          "below 8: the width-aware MFMA kernels, what sim.py --engine mfma-q then runs)")
+    ap.add_argument("--skip-quant-scale", type=float, default=None, metavar="S",
+                    help="merge the long skip through the QAT nets' QuantAdd at scale S (positive, finite): for --params files, which "
+                         "carry no QuantAdd state; a QAT --ckpt gives its own")
+    ap.add_argument("--float-skip", action="store_true", help="add the long skip in float even for a QAT checkpoint")
     args = ap.parse_args(argv)
     if args.quan_bit is not None:
         define.QUAN_BIT = args.quan_bit
@@ -80,7 +90,20 @@ def main(argv=None):
     STORE.clear()
     if (args.frames is None) == (args.input is None):
         raise SystemExit("test.py: give the frames with --frames or with --input (one of them)")
-    model = splice_calibration(sim.float_model(args.mflag, args.ckpt, args.params))
+    if args.float_skip and args.skip_quant_scale is not None:
+        raise SystemExit("test.py: --float-skip and --skip-quant-scale exclude each other")
+    if args.skip_quant_scale is not None and not (np.isfinite(args.skip_quant_scale) and args.skip_quant_scale > 0):
+        raise SystemExit("test.py: --skip-quant-scale must be positive and finite")
+    fmodel = sim.float_model(args.mflag, args.ckpt, args.params)
+    skip_s = None if args.float_skip else args.skip_quant_scale if args.skip_quant_scale is not None else \
+        fmodel.__dict__.get("sesrq_skip_quant_scale")
+    if isinstance(skip_s, Exception):
+        raise SystemExit(f"test.py: {skip_s}; give the scale with --skip-quant-scale or add the skip in float with --float-skip")
+    if skip_s is not None:
+        skip_s = float(np.float32(skip_s))
+    print("skip_quant_scale:", skip_s if skip_s is not None else "none (float long skip)")
+    model = splice_calibration(fmodel)
+    model.__dict__["sesrq_skip_quant_scale"] = skip_s         # read by sesrq.lowering.lower_calibration
     if args.input is not None or args.gt is not None:
         return dataset_pass(args, model)
     frames = torch.load(args.frames, weights_only=True, map_location="cpu") if args.frames.endswith(".pt") else torch.from_numpy(np.load(args.frames))
