@@ -125,7 +125,17 @@ typedef struct sesrq_net sesrq_net;
  * HIP device.  The net is immutable afterwards (options included): forward calls are thread-safe
  * and stream-ordered, on the device the net was created on (a forward issued while another device
  * is current is refused).  Replaces quantize_model_weight's file output + every torch.load of
- * the output_pt/ tree inside the five callables. */
+ * the output_pt/ tree inside the five callables.
+ *
+ * Accepted nets: 3..SESRQ_MAX_LAYERS convolutions, each 3x3 or 5x5 in any position, 1..SESRQ_MAX_CH input and output channels per layer
+ * (consecutive layers match), the first layer with at most 4 input channels, layers[0].oc == layers[L-2].oc (the long residual),
+ * layers[L-1].oc a multiple of pixel_shuffle^2 (pixel_shuffle 1..4).  Anything else is refused with a message (sesrq_last_error).
+ * Hidden tensors are 16 channels wide on the device whatever the layer's width: the weight images carry zeros for the channels a layer
+ * does not have, so a narrower net computes exactly what its descriptor says, at the cost of a 16-wide one.
+ * Launches: every run of three consecutive 3x3 16 -> 16 hidden layers whose load-time proof allows the merged accumulation, taken
+ * greedily from layer L-2 backwards, is ONE fused launch (sesrq_launch_plan, sesrq_options.fuse_hidden); the hidden layers left in
+ * front of the first such run (depths other than 5, 8, 11, 14), every hidden layer of a net with another width or with 5x5 hidden
+ * layers, and nets of depth 3 and 4 run layer by layer.  Same bytes either way. */
 int sesrq_create(const sesrq_net_desc *desc, const sesrq_options *opts, sesrq_net **out);
 /* The same at activation / weight width b = quan_bits (define.py QUAN_BIT, 2..8; sesrq_create is b = 8).  Every activation clamp of the
  * path becomes clamp_b = clamp(., -2^(b-1), 2^(b-1) - 1): the input quantiser, the hidden and output requants and the residual merge,

@@ -345,10 +345,11 @@ def synth_net(kind: str, seed: int = 0, n_blocks: int = 3, hard: bool = False, q
                name=f"synth_{kind}_{seed}{'_hard' if hard else ''}")
 
 
-def _synth_narrow(kind, seed, rng, cin, ps, shapes, hard, b) -> Net:
+def _synth_narrow(kind, seed, rng, cin, ps, shapes, hard, b, gain=1.3) -> Net:
     """synth_net at width b < 8.  plain: normal weights, every zero point at -2^(b-1).  hard: weights at the two extremes of the range,
     each output channel leaning to one of them; zero points anywhere in [-170, 2^(b-1) - 1], the last conv's input domain below -128
-    (its border pixels then read the pad value -128 under 5 x 5 taps of one sign: the 18-bit PE clamp fires from b = 6 on)."""
+    (its border pixels then read the pad value -128 under 5 x 5 taps of one sign: the 18-bit PE clamp fires from b = 6 on).
+    gain: where the 90th percentile of the probe frame's positive accumulators lands, in units of the next domain's span (synth_net: 1.3)."""
     assert 2 <= b < 8
     qlo, qhi = -(1 << (b - 1)), (1 << (b - 1)) - 1
     L = len(shapes)
@@ -381,7 +382,7 @@ def _synth_narrow(kind, seed, rng, cin, ps, shapes, hard, b) -> Net:
     def mult(v, span):
         v = np.asarray(v, np.float64)
         v = v[v > 0]
-        return qconst(1.3 * span / (float(np.percentile(v, 90)) if v.size else 1.0))
+        return qconst(gain * span / (float(np.percentile(v, 90)) if v.size else 1.0))
 
     q = quantize_input(x, scale[0], zero[0], quan_bits=b)
     short = None
