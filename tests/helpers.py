@@ -1,7 +1,10 @@
 """Shared test helpers (oracle <-> product glue).  The oracle is imported here and only here /
 in tests: the product package never sees it."""
+import ctypes
+import hashlib
 import json
 import os
+import sys
 
 import numpy as np
 
@@ -29,6 +32,132 @@ def rand_frame(shape, seed):
     import torch
     g = torch.Generator().manual_seed(seed)
     return torch.rand(shape, generator=g, dtype=torch.float32).numpy()
+
+
+# ---------------------------------------------------------------------------------------------------- device, tensors, hashing
+PIXEL_SHUFFLE = {3: 1, 5: 4, 6: 2}       # the reference's mflag -> PixelShuffle factor of the net
+
+
+def device():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    return torch.device("cuda:0")
+
+
+def to_device(a):
+    """A fresh contiguous copy of the array on the device: shared oracle results are read-only arrays."""
+    import torch
+    return torch.from_numpy(np.array(a, order="C", copy=True)).to(device())
+
+
+def stream_ptr():
+    """The current stream as the C ABI takes it."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(device()).cuda_stream)
+
+
+def sha256(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def full_input(meta):
+    """The reference's shared 80 x 960 random frame of a fixture's net."""
+    return np.load(os.path.join(GOLDEN, "rand_SR_Input_80x960.npy" if meta["mflag"] == 5 else "rand_DM_Input_80x960.npy"))
+
+
+def calib_params(case):
+    """(float weights, float biases, PixelShuffle) of a .params fixture, by golden case name or by path: what a Calibrator is made of."""
+    p, pm = load_fixture(case if case.endswith(".npz") else os.path.join(GOLDEN, f"{case}.params.npz"))
+    return [p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], PIXEL_SHUFFLE[pm["mflag"]]
+
+
+def pass_equals(what, cal, want):
+    """A Calibrator after its pass against calib_oracle.Pass: running extrema and the last batch's (scale, zero)."""
+    assert cal.run_min == want.run_min, (what, cal.run_min, want.run_min)
+    assert cal.run_max == want.run_max, (what, cal.run_max, want.run_max)
+    assert cal.last_scale == want.last_scale and cal.last_zero == want.last_zero, (what, cal.last_zero, want.last_zero)
+
+
+# ---------------------------------------------------------------------------------------------------- 12-bit RGGB raw frames
+def raw_frames():
+    return np.load(os.path.join(GOLDEN, "raw", "frames.npz"), allow_pickle=False)
+
+
+def sites(H, W):
+    """Site channel of every pixel: (0,0) R, (0,1) / (1,0) G, (1,1) B."""
+    yy, xx = np.meshgrid(np.arange(H) & 1, np.arange(W) & 1, indexing="ij")
+    return yy + xx
+
+
+def spread_like(raw, per_code, fill):
+    """(H, W) codes -> (3, H, W): per_code[min(code, 4095)] at the site channel, `fill` elsewhere."""
+    H, W = raw.shape
+    out = np.full((3, H, W), fill, per_code.dtype)
+    np.put_along_axis(out, sites(H, W)[None], per_code[np.minimum(raw, 4095)][None], 0)
+    return out
+
+
+def reference_levels():
+    """x(code) for every code 0 .. 4095 as the reference formed it in inp (read off frame (a), which holds every code at every phase)."""
+    return raw_frames()["levels_inp"]
+
+
+def raw_frames_sha():
+    return json.loads(str(raw_frames()["meta"]))["sha"]
+
+
+def raw_frame(f):
+    """(raw (H, W) uint16, ground truth (1, 3, H, W) uint16 RGB) of frame f, the bytes the reference ran on: frame (a) is stored,
+    (b) and (c) are regenerated (make_raw_golden.natural_raw)."""
+    if f == "a":
+        F = raw_frames()
+        raw, gt16 = F["raw_a"], F["gt16_a"]
+    else:
+        sys.path.insert(0, GOLDEN)
+        from make_raw_golden import natural_raw
+        raw, gt16 = natural_raw(f)
+        gt16 = gt16[None]
+    s = raw_frames_sha()
+    assert sha256(raw) == s[f"raw_{f}"] and sha256(gt16) == s[f"gt16_{f}"], f"frame {f} differs from the one the reference ran on"
+    return raw, gt16
+
+
+def ref_inp(f):
+    """The reference's fp32 input frame (1, 3, H, W) of frame f, rebuilt from its per-code values and checked against its SHA-256."""
+    x = spread_like(raw_frame(f)[0], reference_levels(), np.float32(0))[None]
+    assert sha256(x) == raw_frames_sha()[f"inp_{f}"], f
+    return x
+
+
+def ref_gt(f):
+    """The reference's fp32 ground truth (1, 3, H, W) of frame f, rebuilt the same way."""
+    g = raw_frames()["levels_gt"][np.minimum(raw_frame(f)[1], 4095)]
+    assert sha256(g) == raw_frames_sha()[f"gt_{f}"], f
+    return g
+
+
+# ---------------------------------------------------------------------------------------------------- the comparator
+def same(name, got, want, *, reshape=False, values=False, cast=None):
+    """Raise AssertionError unless `got` (a tensor or an array) IS `want`: identical shape, identical dtype, identical bits (floats are
+    compared as unsigned words: -0.0 is not +0.0, a NaN equals only its own payload).  A call site names each relaxation it needs:
+    reshape=True accepts equal size and compares in want's shape; values=True compares with != on values, not on words;
+    cast=dtype converts `want` first."""
+    got = got.cpu().numpy() if hasattr(got, "cpu") else np.asarray(got)
+    want = want.cpu().numpy() if hasattr(want, "cpu") else np.asarray(want)
+    if cast is not None:
+        want = want.astype(cast)
+    if reshape:
+        assert got.size == want.size, f"{name}: {got.size} elements {got.shape} != {want.size} elements {want.shape}"
+        got = got.reshape(want.shape)
+    assert got.shape == want.shape and got.dtype == want.dtype, f"{name}: {got.dtype} {got.shape} != {want.dtype} {want.shape}"
+    g, w = got, want
+    if not values and got.dtype.kind == "f":
+        words = np.dtype(f"u{got.dtype.itemsize}")
+        g, w = np.ascontiguousarray(got).view(words), np.ascontiguousarray(want).view(words)
+    bad = np.argwhere(g != w)
+    if len(bad):
+        i = tuple(int(j) for j in bad[0])
+        raise AssertionError(f"{name}: {len(bad)} of {got.size} differ, first at {i}: got {got[i]} want {want[i]}")
 
 
 # ---------------------------------------------------------------------------------------------------- caller buffers under watch

@@ -108,3 +108,23 @@ def forward(weights, biases, ps: int, frames: Sequence[np.ndarray], b: int, skip
         if keep_outputs:
             outs.append(O.pixel_shuffle(CO.fakequant(a, d, b, exact), ps) if ps > 1 else a)
     return CO.Pass(run_min, run_max, last_scale, last_zero, doms, outs, ins)
+
+
+def qat_state_dict(mflag, add=None):
+    """A synthetic state_dict shaped like the reference's *_qat_G.pth (seeded): conv weights + the buffers of both quantisers of every
+    conv + the QuantAdd state of the long-skip adds.  add: the add_residual.* observer extrema and stored scale of a checkpoint record
+    (tests/golden/qat_add.json); None leaves both adds with a unit scale."""
+    import sim
+    import torch
+    from models import quantize_utils_pt as quantize
+    torch.manual_seed(4)
+    sd = dict(quantize.prepare(sim.MODELS[mflag](), a_bits=8, w_bits=8, q_type=0, q_level="C").state_dict())
+    for name in ("add_residual", "add_upsampled_input"):
+        sd[f"{name}.activation_quantizer.scale"] = torch.ones(1)
+        sd[f"{name}.observer_res.min_val"] = torch.zeros(1)
+    if add is not None:
+        for k in OBSERVERS:
+            sd["add_residual." + k] = torch.tensor([add[k]], dtype=torch.float32)
+        sd["add_residual.activation_quantizer.scale"] = torch.tensor([add["stored_scale"]], dtype=torch.float32)
+        sd["add_residual.activation_quantizer.observer.max_val"] = torch.tensor([add["observer_res.max_val"]], dtype=torch.float32)
+    return sd

@@ -26,38 +26,17 @@ and fused-trio kernels alike; the dot4 kernels were right.  +-2^22 +- 1 itself c
 import numpy as np
 import pytest
 
-from helpers import bundle_from_oracle
+from helpers import bundle_from_oracle, device, same
 from oracle import sesrq_oracle as O
+from topologies import SEAM_FRAMES as SIZES
+from planner import LIMIT, expected_plan_and_engines, np_verdict, verdicts
 import sesrq
 from sesrq import _lib
 
 ONE = (1 << 15, 15)            # M * 2^-n == 1: the output byte moves with every LSB of the sum
 HALF = (1 << 15, 16)           # residual merge of two equal operands: (2 q + 256) / 2 - 128 == q
 TINY = (65024, 32)             # 63.5 * 2^-22: s = 2^22 lands on the tie 63.5, +-6.45 M on +-97.7
-LIMIT = 1 << 22                # |s| the biased accumulator cannot hold (one binade of 1.5 * 2^23 + s)
-SIZES = ((2, 21, 70), (1, 41, 130))      # cross a 64-column strip, a row tile and (N = 2) a frame seam
 MARGIN = 8                     # receptive radius of the five layers is 7: pixels further inside see no padding
-
-
-# ------------------------------------------------------------------------------------------------ numpy restatement of the load-time proof
-def np_verdict(wq, add_const, zero, acc_bits, add_bits):
-    """saturation_free + the biased-range guard, restated from their definition: per output channel and PE (input channels p mod 4) the
-    extreme sums over q in [-128, 127] are hi = 127 S+ + 128 S-, -lo = -(128 S+ + 127 S-)."""
-    oc, ic = wq.shape[:2]
-    w = wq.astype(np.int64).reshape(oc, ic, -1)
-    acc_hi, add_hi = (1 << (acc_bits - 1)) - 1, (1 << (add_bits - 1)) - 1
-    hi = np.zeros((oc, 4), np.int64)
-    lo = np.zeros((oc, 4), np.int64)
-    for p in range(4):
-        sp = np.clip(w[:, p::4], 0, None).sum((1, 2))
-        sn = np.clip(-w[:, p::4], 0, None).sum((1, 2))
-        hi[:, p], lo[:, p] = 127 * sp + 128 * sn, 128 * sp + 127 * sn
-    risky = (hi > acc_hi) | (lo > acc_hi + 1)
-    mask = sum(1 << p for p in range(4) if risky[:, p].any())
-    worst_pe, worst_sum = int(max(hi.max(), lo.max())), int(max(hi.sum(1).max(), lo.sum(1).max()))
-    free = -128 <= max(zero, -128) <= 127 and mask == 0 and not ((hi.sum(1) > add_hi) | (lo.sum(1) > add_hi + 1)).any()
-    reach = min(worst_sum, 1 << (add_bits - 1)) + int(np.abs(np.asarray(add_const, np.int64)).max())
-    return dict(saturation_free=bool(free), biased_ok=reach < LIMIT, risky_mask=mask, worst_pe=worst_pe, worst_sum=worst_sum, reach=reach)
 
 
 # ------------------------------------------------------------------------------------------------ bound-attaining construction
@@ -201,7 +180,6 @@ class Case:
                          acc_bits=bits[0], add_bits=bits[1], name=name)
         self.frame = frame
         self.cin, self.cout = cin, cout
-        self.kinds = ["f5", "h3", "h3", "h3", "h5p" if cout <= 4 else "h5"]
         self._want = {}
 
     def frames(self, N, H, W):
@@ -235,32 +213,11 @@ class Case:
                 assert got.tolist() == [s], f"{self.name}: layer {k} channel {o}: sum + constant {got.tolist()}, not {s}"
 
     def verdicts(self):
-        return [np_verdict(l.wq, l.add_const, self.net.zero[k], *self.bits) for k, l in enumerate(self.net.layers)]
+        return verdicts(self.net)
 
     def expected_engines(self, **kw):
-        return expected_engines(self.verdicts(), self.kinds, self.bits, **kw)
-
-
-def expected_engines(v, kinds, bits, engine=_lib.ENGINE_AUTO, force_general=False, fuse_hidden=1, **_):
-    """sesrq_layer_engine of every layer from the verdicts alone: -merged below the thresholds (the fused trio for three such 3x3 layers
-    before the last), -hybrid for one risky PE at 18 / 20 bits, -general otherwise, -unbiased beyond the biased range."""
-    std = tuple(bits) == (18, 20)
-    names = []
-    for k, kind in enumerate(kinds):
-        if engine == _lib.ENGINE_DOT4:
-            names.append("dot4-merged" if v[k]["saturation_free"] else "dot4-general")
-        elif not v[k]["biased_ok"]:
-            names.append(f"mfma-{kind}-unbiased")
-        elif v[k]["saturation_free"]:
-            names.append(f"mfma-{kind}-merged")
-        elif bin(v[k]["risky_mask"]).count("1") == 1 and std and kind != "h5p":
-            names.append(f"mfma-{kind}-hybrid")
-        else:
-            names.append(f"mfma-{kind}-general")
-    if engine != _lib.ENGINE_DOT4 and fuse_hidden and not force_general and \
-            all(v[k]["saturation_free"] and v[k]["biased_ok"] for k in (1, 2, 3)):
-        names[1:4] = ["mfma-trio-merged"] * 3
-    return names
+        """layer_engines() as the shared restatement predicts it (tests/planner.py), with a proven fast division."""
+        return expected_plan_and_engines(self.net, **kw)[1]
 
 
 # ---- the rows of cases A and B: (acc_bits, add_bits) -> probed channels.  c = -128 planes everywhere unless `hi` (channels 12..15 at 127)
@@ -591,21 +548,6 @@ def test_reference_bundles_stay_inside_the_biased_range():
 
 
 # ------------------------------------------------------------------------------------------------ GPU part
-def _dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
-
-
-def _eq(name, got, want):
-    got = got.cpu().numpy()
-    assert got.shape == want.shape, f"{name}: shape {got.shape} != {want.shape}"
-    bad = np.argwhere(got != want)
-    if len(bad):
-        i = tuple(bad[0])
-        raise AssertionError(f"{name}: {len(bad)} mismatches, first at {i}: got {got[i]} want {want[i]}")
-
-
 PLANS = [("trio", dict()), ("mfma", dict(fuse_hidden=0)), ("dot4", dict(engine=_lib.ENGINE_DOT4)), ("general", dict(force_general=True)),
          ("dot4-general", dict(engine=_lib.ENGINE_DOT4, force_general=True))]
 FORMS = [("forms-off", dict(reduced_forms=1 | 8)), ("forms-off-mfma", dict(reduced_forms=1 | 8, fuse_hidden=0))]      # PLANS run reduced_forms = 63
@@ -617,25 +559,25 @@ def run_case(case, plans, taps=True):
     import torch
     b = bundle_from_oracle(case.net)
     for tag, kw in plans:
-        e = sesrq.Engine(b, _dev(), **kw)
+        e = sesrq.Engine(b, device(), **kw)
         assert e.layer_engines() == case.expected_engines(**kw), f"{case.name} [{tag}]: {e.layer_engines()}"
         for size in SIZES:
             st = case.want(size)
             q0, x = case.frames(*size)
             for lbl, t in (("f32", torch.from_numpy(x)), ("i8", torch.from_numpy(q0))):
-                q, y = e.forward(t.to(_dev()))
-                _eq(f"{case.name} [{tag}] {size} {lbl} q_out", q, st["q_out"])
-                _eq(f"{case.name} [{tag}] {size} {lbl} y", y, st["y"])
+                q, y = e.forward(t.to(device()))
+                same(f"{case.name} [{tag}] {size} {lbl} q_out", q, st["q_out"])
+                same(f"{case.name} [{tag}] {size} {lbl} y", y, st["y"], values=True)      # z_out == 0: dot4 carries the sign of rint(-0.3) into y
         if taps and tag in ("mfma", "dot4"):
             size = SIZES[1]
             st = case.want(size)
-            res = e.forward_debug(torch.from_numpy(case.frames(*size)[0]).to(_dev()), pe=True, acts=(tag == "dot4"))
+            res = e.forward_debug(torch.from_numpy(case.frames(*size)[0]).to(device()), pe=True, acts=(tag == "dot4"))
             for k in range(5):
-                _eq(f"{case.name} [{tag}] pe_out{k}", res[f"pe_out{k}"][0], st[f"pe_out{k}"])
-                _eq(f"{case.name} [{tag}] pe_add{k}", res[f"pe_add{k}"], st[f"pe_add{k}"])
+                same(f"{case.name} [{tag}] pe_out{k}", res[f"pe_out{k}"][0], st[f"pe_out{k}"])
+                same(f"{case.name} [{tag}] pe_add{k}", res[f"pe_add{k}"], st[f"pe_add{k}"])
                 if tag == "dot4":
-                    _eq(f"{case.name} [{tag}] input{k}", res[f"input{k}"], st[f"input{k}"])
-            _eq(f"{case.name} [{tag}] q_out (debug)", res["q_out"], st["q_out"])
+                    same(f"{case.name} [{tag}] input{k}", res[f"input{k}"], st[f"input{k}"])
+            same(f"{case.name} [{tag}] q_out (debug)", res["q_out"], st["q_out"])
         e.close()
 
 
@@ -707,18 +649,15 @@ def test_reference_bundles_keep_their_kernels():
     for path, net in _golden_nets():
         if net.quan_bits != 8:
             continue
-        v = [np_verdict(l.wq, l.add_const, net.zero[k], net.acc_bits, net.add_bits) for k, l in enumerate(net.layers)]
-        kinds = ["f5", "h3", "h3", "h3", "h5p" if net.layers[4].wq.shape[0] <= 4 else "h5"]
         assert [l.wq.shape[2] for l in net.layers] == [5, 3, 3, 3, 5]
         for tag, kw in PLANS:
-            e = sesrq.Engine(bundle_from_oracle(net), _dev(), **kw)
+            e = sesrq.Engine(bundle_from_oracle(net), device(), **kw)
             names = e.layer_engines()
-            want = expected_engines(v, kinds, (net.acc_bits, net.add_bits), **kw)
+            plan, want = expected_plan_and_engines(net, **kw)
             if not e.fast_division_proven() and kw.get("engine") != _lib.ENGINE_DOT4:
                 want[0] = want[0].replace("mfma-f5", "dot4")        # no proven division form: layer 0 divides on the dot4 kernel
             assert names == want and not any("unbiased" in s_ for s_ in names), (path, tag, names, want)
-            trio = "mfma-trio-merged" in want
-            assert e.launch_plan() == ([(0, 1), (1, 3), (4, 1)] if trio else [(k, 1) for k in range(5)]), (path, tag)
+            assert e.launch_plan() == plan, (path, tag, e.launch_plan(), plan)
             e.close()
             n += 1
     assert n >= 5 * 20

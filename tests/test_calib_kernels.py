@@ -6,108 +6,22 @@ and the bias that fire, zero points at -2^(b-1), far below it, positive, and off
 more than 16 bits and whose PE sums need more than 32; sesrq_calib_minmax and sesrq_calib_observe_slot against numpy and
 calib_oracle.domain; the whole pass (Calibrator.observe and enqueue) against calib_oracle.forward, and a near-flat frame end to end."""
 import ctypes as C
-import os
 import zlib
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, load_fixture
+from calib_cases import F32, bias, frame, slot_bytes, weights, zero_domain
+from helpers import calib_params, device, pass_equals, same, stream_ptr, to_device
 from oracle import calib_oracle as CO
 
-F32 = np.float32
-PS = {3: 1, 5: 4, 6: 2}
 NETS = ("nrdm_3", "sesr_x4", "sesr_x2_rand")
 SHAPES = [(1, 1), (1, 33), (8, 32), (9, 33), (37, 70), (80, 960)]
 OFFSETS = (100, 127, 129, 1e3, 1e5)               # min / span at b = 8; at b = 3 the same zero points: x 255 / 7
 
 
-def _dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
-
-
-def _st():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(_dev()).cuda_stream)
-
-
-def _t(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
-
-
-def _eq(what, got, want):
-    got = got.cpu().numpy() if hasattr(got, "cpu") else np.asarray(got)
-    want = np.asarray(want, F32)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = got != want
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} differ, first at {np.argwhere(bad)[0]}: " \
-                          f"{got[bad][0]!r} vs {want[bad][0]!r}"
-
-
 # ---------------------------------------------------------------------------------------------------------------------- inputs
-def zero_domain(kind, b, span=1.5):
-    """(mn, mx) whose zero point is of the kind: 'low' = -2^(b-1), 'below' far below it, 'far' (min / span = 200) further still,
-    'positive', or a float min / span."""
-    if kind == "low":
-        return 0.0, span
-    if kind == "below":
-        return 2.0 * span, 3.0 * span
-    if kind == "far":
-        return 200.0 * span, 201.0 * span
-    if kind == "positive":
-        return -0.9 * span, 0.1 * span
-    r = float(kind) * (1.0 if b == 8 else 255.0 / 7.0)
-    mn = F32(0.7)
-    return float(mn), float(F32(mn * (1.0 + 1.0 / r)))
-
-
-def frame(rng, shape, d: CO.Domain, b):
-    """fp32 values of the domain: uniform inside it, on the quantiser's ties and one ulp either side, beyond both clamps."""
-    n = int(np.prod(shape))
-    span = d.mx - d.mn
-    x = (d.mn + rng.random(n) * span).astype(F32)
-    k = np.arange(-(1 << (b - 1)) - 1, (1 << (b - 1)) + 1, dtype=np.float64)
-    ties = ((k + 0.5 - float(d.zero32)) * float(d.scale32)).astype(F32)
-    row = np.concatenate([ties, np.nextafter(ties, F32(np.inf)), np.nextafter(ties, F32(-np.inf)),
-                          np.array([d.mn - span, d.mx + span, d.mn, d.mx], F32)])
-    pos = rng.permutation(n)[:min(n, row.size)]
-    x[pos] = row[rng.permutation(row.size)[:pos.size]]
-    return x.reshape(shape)
-
-
-def weights(rng, oc, ic, K, b, sat=False):
-    lo, hi = -(1 << (b - 1)), (1 << (b - 1)) - 1
-    if sat:                        # one sign per output channel: the PE sums run to the accumulator's bounds
-        s = np.where(np.arange(oc) % 2 == 0, hi, lo)[:, None, None, None]
-        return np.broadcast_to(s, (oc, ic, K, K)).astype(np.int32).copy()
-    return rng.integers(lo, hi + 1, size=(oc, ic, K, K)).astype(np.int32)
-
-
-def bias(rng, oc, ss, big=False):
-    b = (rng.standard_normal(oc) * 200.0 * float(ss)).astype(F32)
-    if big:                        # beyond the 16-bit bias code on both sides
-        b[::2] = F32(50000.0 * float(ss))
-        b[1::2] = F32(-50000.0 * float(ss))
-    return b
-
-
 # ---------------------------------------------------------------------------------------------------------------------- launchers
-def _slot_bytes(d: CO.Domain, batches=1):
-    from sesrq import _lib
-    s = _lib.CalibSlot()
-    s.ord[0], s.ord[1] = 0xffffffff, 0
-    s.min = s.run_min = d.mn
-    s.max = s.run_max = d.mx
-    s.scale, s.zero, s.degenerate, s.batches = d.scale, d.zero, int(d.degenerate), batches
-    s.scale32, s.zero32, s.ss = float(d.scale32), float(d.zero32), float(d.ss)
-    s.acc_lo, s.acc_hi, s.add_lo, s.add_hi = float(d.acc_lo), float(d.acc_hi), float(d.add_lo), float(d.add_hi)
-    for i, v in enumerate(d.qbias):
-        s.qbias[i] = float(v)
-    import torch
-    return torch.frombuffer(bytearray(bytes(s)), dtype=torch.uint8).to(_dev())
 
 
 def run_conv(entry, x, wq, d: CO.Domain, b, relu, skip):
@@ -117,19 +31,19 @@ def run_conv(entry, x, wq, d: CO.Domain, b, relu, skip):
     lib = _lib.lib()
     N, ic, H, W = x.shape
     oc, _, K, _ = wq.shape
-    xt, wt, qb = _t(x), _t(wq), _t(d.qbias.astype(F32))
-    st = _t(skip) if skip is not None else None
-    out = torch.full((N, oc, H, W), float("nan"), dtype=torch.float32, device=_dev())
+    xt, wt, qb = to_device(x), to_device(wq), to_device(d.qbias.astype(F32))
+    st = to_device(skip) if skip is not None else None
+    out = torch.full((N, oc, H, W), float("nan"), dtype=torch.float32, device=device())
     desc = _lib.CalibConvDesc(k=K, ic=ic, oc=oc, w=wt.data_ptr(), qbias=qb.data_ptr(), in_scale=float(d.scale32), in_zero=d.zero,
                               ss=float(d.ss), acc_lo=float(d.acc_lo), acc_hi=float(d.acc_hi), add_lo=float(d.add_lo),
                               add_hi=float(d.add_hi), relu=int(relu))
     sp = st.data_ptr() if st is not None else None
     if entry == "q":
-        _lib.check(lib.sesrq_calib_conv_q(C.byref(desc), xt.data_ptr(), sp, out.data_ptr(), N, H, W, b, _st()))
+        _lib.check(lib.sesrq_calib_conv_q(C.byref(desc), xt.data_ptr(), sp, out.data_ptr(), N, H, W, b, stream_ptr()))
     else:
         desc.qbias, desc.in_scale, desc.in_zero = None, 0.0, 0          # the slot's are used
-        slot = _slot_bytes(d)
-        _lib.check(lib.sesrq_calib_conv_slot(C.byref(desc), slot.data_ptr(), xt.data_ptr(), sp, out.data_ptr(), N, H, W, b, _st()))
+        slot = slot_bytes(d)
+        _lib.check(lib.sesrq_calib_conv_slot(C.byref(desc), slot.data_ptr(), xt.data_ptr(), sp, out.data_ptr(), N, H, W, b, stream_ptr()))
     torch.cuda.synchronize()
     return out
 
@@ -191,17 +105,17 @@ def test_calib_conv_bit_exact_with_the_oracle(entry):
         if not isinstance(kind, str):                              # offset domains: from min / span 129 on, codes beyond 16 bits
             q = CO.codes(x, d, b) - d.zero
             assert (np.abs(q).max() > 32767) == (kind >= 129), (_cid(c), np.abs(q).max())
-        _eq(f"{entry} {_cid(c)}", run_conv(entry, x, wq, d, b, relu, sk), want)
+        same(f"{entry} {_cid(c)}", run_conv(entry, x, wq, d, b, relu, sk), want, values=True, cast=F32)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- minmax
 def _minmax(x):
     import torch
     from sesrq import _lib
-    xt = _t(x)
-    mm = torch.empty(2, dtype=torch.float32, device=_dev())
-    scratch = torch.empty(2, dtype=torch.int32, device=_dev())
-    _lib.check(_lib.lib().sesrq_calib_minmax(xt.data_ptr(), xt.numel(), mm.data_ptr(), scratch.data_ptr(), _st()))
+    xt = to_device(x)
+    mm = torch.empty(2, dtype=torch.float32, device=device())
+    scratch = torch.empty(2, dtype=torch.int32, device=device())
+    _lib.check(_lib.lib().sesrq_calib_minmax(xt.data_ptr(), xt.numel(), mm.data_ptr(), scratch.data_ptr(), stream_ptr()))
     return mm.cpu().numpy()
 
 
@@ -260,11 +174,11 @@ def test_observe_slot_equals_the_domain(b):
     oc, sw = 16, 0.0071
     bt = (rng.standard_normal(oc) * 2.0).astype(F32)
     bt[0] = F32(1e4)                                             # beyond the 16-bit code at every domain here
-    btd = _t(bt)
+    btd = to_device(bt)
     desc = _lib.CalibDomainDesc(quan_bits=b, oc=oc, bias=btd.data_ptr(), sw=sw, acc_bits=18, add_bits=20, bias_bits=16)
     init = _lib.CalibSlot()
     _lib.check(lib.sesrq_calib_slots_init(C.byref(init), 1))
-    slot = torch.frombuffer(bytearray(bytes(init)), dtype=torch.uint8).to(_dev())
+    slot = torch.frombuffer(bytearray(bytes(init)), dtype=torch.uint8).to(device())
     run_mn, run_mx = None, None
     batches = [("low", 1.0), ("positive", 2.0), ("below", 0.5), (129, 1.0), (1e5, 1.0), ("huge", 1.0), ("low", 7.0)]
     for i, (kind, span) in enumerate(batches):
@@ -274,7 +188,7 @@ def test_observe_slot_equals_the_domain(b):
             mn, mx = zero_domain(kind, b, span)
         x = (mn + rng.random(3 * 256 + 11) * (mx - mn)).astype(F32)
         x[:2] = (F32(mn), F32(mx))
-        _lib.check(lib.sesrq_calib_observe_slot(_t(x).data_ptr(), x.size, slot.data_ptr(), C.byref(desc), _st()))
+        _lib.check(lib.sesrq_calib_observe_slot(to_device(x).data_ptr(), x.size, slot.data_ptr(), C.byref(desc), stream_ptr()))
         s = _read_slot(slot)
         bmn, bmx = CO.minmax(x)
         assert (s.min, s.max) == (bmn, bmx), (i, s.min, s.max)
@@ -289,28 +203,17 @@ def test_observe_slot_equals_the_domain(b):
         _slot_equals_domain((b, i, kind), s, d, oc)
         assert not s.degenerate
     x = np.full(300, 0.25, F32)                                 # constant: degenerate, and it stays raised
-    _lib.check(lib.sesrq_calib_observe_slot(_t(x).data_ptr(), x.size, slot.data_ptr(), C.byref(desc), _st()))
+    _lib.check(lib.sesrq_calib_observe_slot(to_device(x).data_ptr(), x.size, slot.data_ptr(), C.byref(desc), stream_ptr()))
     s = _read_slot(slot)
     assert s.degenerate and s.scale == 0.0 and s.zero == 0 and s.batches == len(batches) + 1
     x = (rng.random(300)).astype(F32)
-    _lib.check(lib.sesrq_calib_observe_slot(_t(x).data_ptr(), x.size, slot.data_ptr(), C.byref(desc), _st()))
+    _lib.check(lib.sesrq_calib_observe_slot(to_device(x).data_ptr(), x.size, slot.data_ptr(), C.byref(desc), stream_ptr()))
     s = _read_slot(slot)
     assert s.degenerate
     _slot_equals_domain((b, "after"), s, CO.domain(*CO.minmax(x), b, sw, bt), oc)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- whole pass
-def _params(case):
-    p, pm = load_fixture(os.path.join(GOLDEN, f"{case}.params.npz"))
-    return [p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], PS[pm["mflag"]]
-
-
-def _pass_equals(what, cal, want: CO.Pass):
-    assert cal.run_min == want.run_min, (what, cal.run_min, want.run_min)
-    assert cal.run_max == want.run_max, (what, cal.run_max, want.run_max)
-    assert cal.last_scale == want.last_scale and cal.last_zero == want.last_zero, (what, cal.last_zero, want.last_zero)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("b", [8, 3])
 @pytest.mark.parametrize("case", NETS)
@@ -319,21 +222,21 @@ def test_whole_pass_equals_the_oracle(case, b):
     (scale, zero) and each batch's returned output equal calib_oracle.forward."""
     import torch
     from sesrq.calibrate import Calibrator
-    Wf, bf, ps = _params(case)
+    Wf, bf, ps = calib_params(case)
     cin = Wf[0].shape[1]
     rng = np.random.default_rng(zlib.crc32(f"{case}.{b}".encode()))
     frames = [rng.random((2, cin, 37, 70)).astype(F32), (rng.random((2, cin, 37, 70)) * 1.3 - 0.1).astype(F32)]
     want = CO.forward(Wf, bf, ps, frames, b)
-    host = Calibrator(Wf, bf, ps, _dev(), quan_bits=b)
-    dev = Calibrator(Wf, bf, ps, _dev(), quan_bits=b)
+    host = Calibrator(Wf, bf, ps, device(), quan_bits=b)
+    dev = Calibrator(Wf, bf, ps, device(), quan_bits=b)
     for i, x in enumerate(frames):
-        _eq(f"{case} b={b} observe {i}", host.observe(_t(x)), want.outputs[i])
-        y = dev.enqueue(_t(x))
+        same(f"{case} b={b} observe {i}", host.observe(to_device(x)), want.outputs[i], values=True, cast=F32)
+        y = dev.enqueue(to_device(x))
         torch.cuda.synchronize()
-        _eq(f"{case} b={b} enqueue {i}", y, want.outputs[i])
+        same(f"{case} b={b} enqueue {i}", y, want.outputs[i], values=True, cast=F32)
     dev.sync()
-    _pass_equals(f"{case} b={b} observe", host, want)
-    _pass_equals(f"{case} b={b} enqueue", dev, want)
+    pass_equals(f"{case} b={b} observe", host, want)
+    pass_equals(f"{case} b={b} enqueue", dev, want)
 
 
 @pytest.mark.gpu
@@ -344,7 +247,7 @@ def test_near_flat_frame_end_to_end(case):
     import torch
     from sesrq.bundle import calib_scale_zero, derive_bundle_from_quantized
     from sesrq.calibrate import Calibrator
-    Wf, bf, ps = _params(case)
+    Wf, bf, ps = calib_params(case)
     cin = Wf[0].shape[1]
     rng = np.random.default_rng(5)
     x = (F32(0.700) + rng.random((1, cin, 40, 96)) * F32(0.005)).astype(F32)
@@ -352,12 +255,12 @@ def test_near_flat_frame_end_to_end(case):
     want = CO.forward(Wf, bf, ps, [x], 8)
     assert want.last_zero[0] < -35000
     for form in ("observe", "enqueue"):
-        cal = Calibrator(Wf, bf, ps, _dev(), quan_bits=8)
-        y = cal.observe(_t(x)) if form == "observe" else cal.enqueue(_t(x))
+        cal = Calibrator(Wf, bf, ps, device(), quan_bits=8)
+        y = cal.observe(to_device(x)) if form == "observe" else cal.enqueue(to_device(x))
         torch.cuda.synchronize()
-        _eq(f"{case} {form}", y, want.outputs[0])
+        same(f"{case} {form}", y, want.outputs[0], values=True, cast=F32)
         got = cal.bundle()
-        _pass_equals(f"{case} {form}", cal, want)
+        pass_equals(f"{case} {form}", cal, want)
         sz = [calib_scale_zero(0.0 if k == 5 else want.run_min[k], want.run_max[k], 8) for k in range(6)]
         qw = CO.quantize(Wf, 8)
         ref = derive_bundle_from_quantized([w for w, _ in qw], [s for _, s in qw], bf, [s for s, _ in sz], [z for _, z in sz], ps)
@@ -373,15 +276,15 @@ def test_zero_clamp_agrees_on_host_and_device():
     enqueue (device-derived) clamp alike and equal calib_oracle.forward."""
     import torch
     from sesrq.calibrate import Calibrator
-    Wf, bf, ps = _params("nrdm_3")
+    Wf, bf, ps = calib_params("nrdm_3")
     rng = np.random.default_rng(11)
     x = np.where(rng.random((1, 3, 9, 40)) < 0.5, F32(1.0e6), np.nextafter(F32(1.0e6), F32(np.inf))).astype(F32)
     want = CO.forward(Wf, bf, ps, [x], 8)
     assert want.last_zero[0] == -CO.ZERO_CLAMP
     for form in ("observe", "enqueue"):
-        cal = Calibrator(Wf, bf, ps, _dev(), quan_bits=8)
-        y = cal.observe(_t(x)) if form == "observe" else cal.enqueue(_t(x))
+        cal = Calibrator(Wf, bf, ps, device(), quan_bits=8)
+        y = cal.observe(to_device(x)) if form == "observe" else cal.enqueue(to_device(x))
         torch.cuda.synchronize()
         cal.sync()
-        _eq(f"clamp {form}", y, want.outputs[0])
-        _pass_equals(f"clamp {form}", cal, want)
+        same(f"clamp {form}", y, want.outputs[0], values=True, cast=F32)
+        pass_equals(f"clamp {form}", cal, want)

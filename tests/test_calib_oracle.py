@@ -5,19 +5,16 @@ The reference ran its mode-0 graph in fp32 in oneDNN's order; the oracle forms t
 arithmetic in float64 (exact=True).  Bars as for the device pass (test_gpu_parity.py, test_calib_reference.py): running min / max
 within 1e-4 of the span, zero points equal, scales within rtol 2e-4; the two forms within 1e-4 of the span of each other."""
 import glob
-import json
 import os
-import sys
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_fixture
+from calib_cases import dataset_frames, finalize, frame_of
+from helpers import PIXEL_SHUFFLE
 from oracle import calib_oracle as CO
 
-PS = {3: 1, 5: 4, 6: 2}
-NAT_SEED = {"sesr_x4_nat": 2024, "nrdm_3_nat": 2025, "sesr_x2_rand_nat": 2026, "sesr_x4_qat_nat": 2027,
-            "nrdm_3_qat_nat": 2028}                                              # tests/golden/make_golden.py CASES
 QAT = ("nrdm_3_qat", "sesr_x4_qat", "nrdm_3_qat_nat", "sesr_x4_qat_nat")
 QB = os.path.join(GOLDEN, "quan_bits")
 
@@ -34,28 +31,12 @@ RECORDS = sorted(p for p in glob.glob(os.path.join(GOLDEN, "*.params.npz")) if _
 EXACT_SLACK = {("sesr_x2_rand.params.npz", 5): 3e-4, ("nrdm_3.q6.params.npz", 5): 5e-4, ("sesr_x2_rand.q4.params.npz", 5): 2e-3}
 
 
-def frame_of(meta):
-    """The frame the reference calibrated on: its random 80 x 960 input, or the natural frame of the case."""
-    if meta["case"] in NAT_SEED:
-        sys.path.insert(0, GOLDEN)
-        from natural import natural_frame
-        return natural_frame(1 if meta["mflag"] == 5 else 3, 80, 960, NAT_SEED[meta["case"]])
-    return np.load(os.path.join(GOLDEN, "rand_SR_Input_80x960.npy" if meta["mflag"] == 5 else "rand_DM_Input_80x960.npy"))
-
-
 def run(path, exact=False, frames=None):
     p, pm = load_fixture(path)
     b = pm.get("quan_bits", 8)
     frames = [frame_of(pm)] if frames is None else frames
-    return CO.forward([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], PS[pm["mflag"]], frames, b, exact=exact,
+    return CO.forward([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], PIXEL_SHUFFLE[pm["mflag"]], frames, b, exact=exact,
                       keep_outputs=False), pm, b
-
-
-def finalize(r, b):
-    """test.py:185-217: the output domain's min := 0."""
-    from oracle.sesrq_oracle import calib_scale_zero
-    sz = [calib_scale_zero(0.0 if k == len(r.run_min) - 1 else r.run_min[k], r.run_max[k], b) for k in range(len(r.run_min))]
-    return [s for s, _ in sz], [z for _, z in sz]
 
 
 def assert_ranges(what, r, mins, maxs, check_last_min=False, bar=1e-4):
@@ -108,17 +89,6 @@ def test_qat_records_hold_the_graph_of_their_training(case):
 
 
 # ------------------------------------------------------------------------------------------------------------- dataset loops
-def dataset_frames(case, mflag):
-    """fp32 frames a, b, c of the reference's dataset loop (tests/golden/make_calib_golden.py), decoded on the CPU."""
-    sys.path.insert(0, os.path.dirname(__file__))
-    if case == "nrdm_3":
-        import test_raw
-        return [test_raw.ref_inp(f) for f in ("a", "b", "c")]
-    import image_oracle
-    from test_calib_dataset import image_frames
-    return [image_oracle.decode(lr, "y" if mflag == 5 else "rgb") for lr, _ in image_frames(mflag)]
-
-
 @pytest.mark.parametrize("case", ["nrdm_3", "sesr_x4", "sesr_x2_rand"])
 def test_oracle_reproduces_the_dataset_loops(case):
     """tests/golden/calib/<case>.npz: running ranges over frames a, b, c (every domain's min included), zero points, scales; both

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_fixture
-from test_calib_dataset import _calibrators, image_frames, raw_frames
+from calib_cases import calibrators, image_frames, raw_dataset_frames
 
 CASES = ["nrdm_3", "sesr_x4", "sesr_x2_rand"]
 # Output deviation in steps of the output domain (scale[5]).  Where an upstream fake-quantiser input lies at a rounding tie the two
@@ -31,7 +31,7 @@ def fixture(case):
 
 
 def pairs(case, mflag):
-    return raw_frames() if case == "nrdm_3" else image_frames(mflag)
+    return raw_dataset_frames() if case == "nrdm_3" else image_frames(mflag)
 
 
 def test_fixtures_hold_the_dataset_frames():
@@ -63,7 +63,7 @@ def test_enqueue_matches_the_reference_loop(case):
     ranges and the final domains against the reference's."""
     import torch
     fx, meta = fixture(case)
-    cal, _, mflag = _calibrators(case)
+    cal, _, mflag = calibrators(case)
     assert mflag == meta["mflag"]
     step = meta["scale"][5]
     h, w = meta["crop"]
@@ -84,7 +84,7 @@ def test_evaluate_calibration_matches_the_reference_scores(case):
     """evaluate_calibration over frames a, b, c: per-frame PSNR / SSIM of the mode-0 output (MFLAG 6 anchored) against the reference's
     outputs scored by the metric restatement, the mean line's values, and the domains it accumulated."""
     fx, meta = fixture(case)
-    cal, _, mflag = _calibrators(case)
+    cal, _, mflag = calibrators(case)
     ps = pairs(case, mflag)
     res = quality_eval(cal, ps, mflag, meta["kind"])
     want = np.array([[meta["per_frame"][f][k] for k in ("mse", "psnr", "ssim")] for f in meta["frames"]])

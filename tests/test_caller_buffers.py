@@ -26,14 +26,14 @@ step; (2, 17, 70): the second image of a batch, ragged in both directions, acros
 import ctypes as C
 import functools
 import itertools
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, load_fixture
-from helpers import Arena, bundle_from_oracle, rand_frame
+from helpers import (Arena, bundle_from_oracle, calib_params, device, pass_equals, rand_frame, reference_levels, same, spread_like,
+                     stream_ptr)
+from planner import expected_plan_and_engines
 from oracle import calib_oracle as CO
 from oracle import sesrq_oracle as O
 import image_oracle as IO
@@ -53,15 +53,6 @@ F32_OFFS = (0, 4, 8, 12)
 SHAPES = ((1, 1, 1), (1, 9, 61), (2, 17, 70))
 TORCH = {np.dtype(np.int8): torch.int8, np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8,
          np.dtype(np.uint16): torch.uint16, np.dtype(np.int32): torch.int32, np.dtype(np.float64): torch.float64}
-
-
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(_dev()).cuda_stream)
 
 
 class Offsets:
@@ -92,21 +83,6 @@ def _clean(what, *arenas):
         assert not stray, f"{what}: bytes outside the caller's buffers changed: {stray[:6]}"
 
 
-def _same(what, got, want):
-    """Bit for bit (fp32 compared as words: a canary, a NaN or a signed zero cannot pass for the value)."""
-    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
-    want = np.ascontiguousarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, got.dtype, want.shape, want.dtype)
-    if got.dtype.kind == "f":
-        w = {4: np.uint32, 8: np.uint64}[got.dtype.itemsize]
-        bad = np.argwhere(np.ascontiguousarray(got).view(w) != want.view(w))
-    else:
-        bad = np.argwhere(got != want)
-    if len(bad):
-        i = tuple(bad[0])
-        raise AssertionError(f"{what}: {len(bad)} of {got.size} differ, first at {i}: got {got[i]!r} want {want[i]!r}")
-
-
 def _put(arena, a, off, name):
     a = np.array(a, order="C", copy=True)          # the shared cases are read-only
     return arena.place(a.shape, TORCH[a.dtype], off, fill=a, name=name)
@@ -135,7 +111,7 @@ def _case(kind, hard, shape, seed=0):
 
 @functools.lru_cache(maxsize=None)
 def _engine(kind, hard=False, **kw):
-    return sesrq.Engine(bundle_from_oracle(_net(kind, hard)), _dev(), **kw)
+    return sesrq.Engine(bundle_from_oracle(_net(kind, hard)), device(), **kw)
 
 
 CONFIGS = {
@@ -168,21 +144,21 @@ def _forward_in_arenas(e, want, shape, in_kind, want_q, want_f, offs, rnd, what)
     N, H, W = shape
     lib = _lib.lib()
     src = want["x"] if in_kind == "f32" else want["q0"]
-    ain = Arena(_dev(), Arena.room(src.nbytes), around_f32 if in_kind == "f32" else around_i8)
+    ain = Arena(device(), Arena.room(src.nbytes), around_f32 if in_kind == "f32" else around_i8)
     xin = _put(ain, src, offs.next("in_" + in_kind, F32_OFFS if in_kind == "f32" else I8_OFFS), "in")
     ws_bytes = lib.sesrq_workspace_bytes(e._h, N, H, W)
     assert ws_bytes > 0
     oshape = e.out_shape(N, H, W)
     n_out = int(np.prod(oshape))
-    aout = Arena(_dev(), Arena.room(n_out, 4 * n_out, ws_bytes), canary)
+    aout = Arena(device(), Arena.room(n_out, 4 * n_out, ws_bytes), canary)
     q = aout.place(oshape, torch.int8, offs.next("out_q", I8_OFFS, 2), name="out_q") if want_q else None
     y = aout.place(oshape, torch.float32, offs.next("out_f", F32_OFFS, 3), name="out_f") if want_f else None
     ws = aout.place(ws_bytes, torch.uint8, 16, fill=ws_fill, name="workspace")      # exactly sesrq_workspace_bytes, 16-byte aligned
     rc = lib.sesrq_forward(e._h, xin.data_ptr(), _lib.F32 if in_kind == "f32" else _lib.I8, q.data_ptr() if want_q else None,
-                           y.data_ptr() if want_f else None, N, H, W, ws.data_ptr(), ws_bytes, _stream())
+                           y.data_ptr() if want_f else None, N, H, W, ws.data_ptr(), ws_bytes, stream_ptr())
     assert rc == 0, (what, _lib.last_error())
     _clean(what, ain, aout)
-    _same(what + " input untouched", xin, src)
+    same(what + " input untouched", xin, src)
     return q, y
 
 
@@ -193,6 +169,8 @@ def test_forward_in_hostile_surroundings(cfg):
     kind, hard, kw = CONFIGS[cfg]
     e = _engine(kind, hard, **kw)
     _expect_kernels(cfg, e.layer_engines())
+    plan, names = expected_plan_and_engines(_net(kind, hard), fast_division=e.fast_division_proven(), **kw)
+    assert e.launch_plan() == plan and e.layer_engines() == names, (cfg, e.launch_plan(), plan, e.layer_engines(), names)
     anchored = bool(kw.get("anchor_add"))
     offs = Offsets()
     for shape in SHAPES:
@@ -203,9 +181,9 @@ def test_forward_in_hostile_surroundings(cfg):
                     what = f"{cfg} {shape} in={in_kind} q={want_q} f={want_f} run {r + 1}"
                     q, y = _forward_in_arenas(e, want, shape, in_kind, want_q, want_f, offs, rnd, what)
                     if want_q:
-                        _same(what + " out_q", q, want["q_out"])
+                        same(what + " out_q", q, want["q_out"])
                     if want_f:
-                        _same(what + " out_f", y, want["y_anchor"] if anchored else want["y"])
+                        same(what + " out_f", y, want["y_anchor"] if anchored else want["y"])
     offs.assert_all_seen()
 
 
@@ -232,9 +210,9 @@ def test_forward_many_frames_packed_in_one_pool(cfg, group):
         for r, (canary, around_f32, around_i8, ws_fill) in enumerate(ROUNDS):
             what = f"forward_many {cfg} group {group} in={in_kind} run {r + 1}"
             srcs = [w["x"] if in_kind == "f32" else w["q0"] for w in wants]
-            ain = Arena(_dev(), Arena.room(*[s.nbytes for s in srcs]), around_f32 if in_kind == "f32" else around_i8)
+            ain = Arena(device(), Arena.room(*[s.nbytes for s in srcs]), around_f32 if in_kind == "f32" else around_i8)
             xs = [_put(ain, s, offs.next("in_" + in_kind, F32_OFFS if in_kind == "f32" else I8_OFFS), f"in{k}") for k, s in enumerate(srcs)]
-            aout = Arena(_dev(), Arena.room(*([n_out, 4 * n_out] * F + [ws_bytes])), canary)
+            aout = Arena(device(), Arena.room(*([n_out, 4 * n_out] * F + [ws_bytes])), canary)
             qs, ys = [], []
             for k in range(F):
                 qs.append(aout.place(oshape, torch.int8, offs.next("out_q", I8_OFFS, 2), name=f"out_q{k}"))
@@ -242,12 +220,12 @@ def test_forward_many_frames_packed_in_one_pool(cfg, group):
             ws = aout.place(ws_bytes, torch.uint8, 16, fill=ws_fill, name="workspace")
             io = (_lib.FrameIO * F)(*[_lib.FrameIO(xs[k].data_ptr(), qs[k].data_ptr(), ys[k].data_ptr()) for k in range(F)])
             rc = lib.sesrq_forward_many(e._h, io, F, _lib.F32 if in_kind == "f32" else _lib.I8, N, H, W,
-                                        (C.c_void_p * 1)(ws.data_ptr()), ws_bytes, (C.c_void_p * 1)(_stream().value), 1, group)
+                                        (C.c_void_p * 1)(ws.data_ptr()), ws_bytes, (C.c_void_p * 1)(stream_ptr().value), 1, group)
             assert rc == 0, (what, _lib.last_error())
             _clean(what, ain, aout)
             for k in range(F):
-                _same(f"{what} frame {k} out_q", qs[k], wants[k]["q_out"])
-                _same(f"{what} frame {k} out_f", ys[k], wants[k]["y_anchor"] if kw else wants[k]["y"])
+                same(f"{what} frame {k} out_q", qs[k], wants[k]["q_out"])
+                same(f"{what} frame {k} out_f", ys[k], wants[k]["y_anchor"] if kw else wants[k]["y"])
     offs.assert_all_seen()
 
 
@@ -275,9 +253,9 @@ def test_forward_debug_taps_in_hostile_surroundings():
     offs = Offsets()
     for r, (canary, around_f32, around_i8, ws_fill) in enumerate(ROUNDS):
         what = f"forward_debug run {r + 1}"
-        ain = Arena(_dev(), Arena.room(x.nbytes), around_f32)
+        ain = Arena(device(), Arena.room(x.nbytes), around_f32)
         xin = _put(ain, x, (4, 12)[r], "in")
-        aout = Arena(_dev(), Arena.room(*([v.nbytes for v in want.values()] + [ws_bytes])), canary)
+        aout = Arena(device(), Arena.room(*([v.nbytes for v in want.values()] + [ws_bytes])), canary)
         bufs = {}
         for name, v in want.items():
             classes, step = (I8_OFFS, 2) if v.dtype == np.int8 else (F32_OFFS, 3)
@@ -288,22 +266,16 @@ def test_forward_debug_taps_in_hostile_surroundings():
             taps.act[k], taps.pe_out[k], taps.pe_add[k] = (bufs[f"{n}{k}"].data_ptr() for n in ("input", "pe_out", "pe_add"))
         taps.shortcut, taps.ic, taps.overflow = bufs["shortcut"].data_ptr(), bufs["input4_special"].data_ptr(), bufs["overflow"].data_ptr()
         rc = lib.sesrq_forward_debug(e._h, xin.data_ptr(), _lib.F32, bufs["q_out"].data_ptr(), bufs["y"].data_ptr(), N, H, W,
-                                     ws.data_ptr(), ws_bytes, _stream(), C.byref(taps))
+                                     ws.data_ptr(), ws_bytes, stream_ptr(), C.byref(taps))
         assert rc == 0, _lib.last_error()
         _clean(what, ain, aout)
         for name, v in want.items():
-            _same(f"{what} {name}", bufs[name], v)
+            same(f"{what} {name}", bufs[name], v)
     offs.assert_all_seen()
 
 
 # =============================================================================================================== libsesrq_raw
-def _levels():
-    from test_raw import reference_levels
-    return reference_levels()
-
-
 def _spread(raw, per_code, fill):
-    from test_raw import spread_like
     return np.stack([spread_like(f, per_code, fill) for f in raw])
 
 
@@ -319,30 +291,30 @@ def test_raw_unpack_in_hostile_surroundings(hw):
     from sesrq import raw as R
     H, W = hw
     s0, z0 = 0.0038037779284458536, -128
-    lv = _levels()
+    lv = reference_levels()
     tq = O.quantize_input(lv, s0, z0)
     rng = np.random.default_rng(H * W)
     raw = rng.integers(0, 4096, (2, H, W)).astype(np.uint16)
     raw[0, 1, 3], raw[1, 0, 0], raw[1, H - 1, W - 1], raw[0, 2, 2] = 4095, 4096, 65535, 0
     want_q, want_sp = _spread(raw, tq, tq[0]), _spread(raw, lv, F32(0))
-    ctx = R._so.context(_dev(), s0, z0, 0)
+    ctx = R._so.context(device(), s0, z0, 0)
     for i, (ro, qo, so) in enumerate(RAW_PLACES):
         for outs in ((True, True), (True, False), (False, True)) if i in (0, 6) else ((True, True),):
             for r, (canary, _, around_i8, _) in enumerate(ROUNDS):
                 what = f"raw {H}x{W} at ({ro}, {qo}, {so}) q0={outs[0]} spread={outs[1]} run {r + 1}"
-                ain = Arena(_dev(), Arena.room(raw.nbytes), around_i8)
+                ain = Arena(device(), Arena.room(raw.nbytes), around_i8)
                 rin = _put(ain, raw, ro, "raw")
-                aout = Arena(_dev(), Arena.room(want_q.nbytes, want_sp.nbytes), canary)
+                aout = Arena(device(), Arena.room(want_q.nbytes, want_sp.nbytes), canary)
                 q = aout.place(want_q.shape, torch.int8, qo, name="q0") if outs[0] else None
                 sp = aout.place(want_sp.shape, torch.float32, so, name="spread") if outs[1] else None
                 rc = R.lib().sesrq_raw_unpack(ctx, rin.data_ptr(), q.data_ptr() if q is not None else None,
-                                              sp.data_ptr() if sp is not None else None, 2, H, W, _stream())
+                                              sp.data_ptr() if sp is not None else None, 2, H, W, stream_ptr())
                 assert rc == 0, (what, R.last_error())
                 _clean(what, ain, aout)
                 if outs[0]:
-                    _same(what + " q0", q, want_q)
+                    same(what + " q0", q, want_q)
                 if outs[1]:
-                    _same(what + " spread", sp, want_sp)
+                    same(what + " spread", sp, want_sp)
 
 
 # =============================================================================================================== libsesrq_image
@@ -361,7 +333,7 @@ def test_image_decode_in_hostile_surroundings(hw, form):
     rng = np.random.default_rng(H * W + len(form))
     img = rng.integers(0, 256, (2, H, W, 3)).astype(np.uint8)
     img[0, 0, 0], img[1, H - 1, W - 1] = 255, 0
-    ctx = I._so.context(_dev(), s0, z0, 0)
+    ctx = I._so.context(device(), s0, z0, 0)
     for i, (so, qo, xo) in enumerate(IMG_PLACES):
         order = ("rgb", "bgr")[i % 2]
         want_x = np.ascontiguousarray(IO.decode(img, form, order))
@@ -369,19 +341,19 @@ def test_image_decode_in_hostile_surroundings(hw, form):
         for outs in ((True, True), (True, False), (False, True)) if i in (0, 5) else ((True, True),):
             for r, (canary, _, around_i8, _) in enumerate(ROUNDS):
                 what = f"decode {form} {order} {H}x{W} at ({so}, {qo}, {xo}) q0={outs[0]} x={outs[1]} run {r + 1}"
-                ain = Arena(_dev(), Arena.room(img.nbytes), around_i8)
+                ain = Arena(device(), Arena.room(img.nbytes), around_i8)
                 src = _put(ain, img, so, "img")
-                aout = Arena(_dev(), Arena.room(want_q.nbytes, want_x.nbytes), canary)
+                aout = Arena(device(), Arena.room(want_q.nbytes, want_x.nbytes), canary)
                 q = aout.place(want_q.shape, torch.int8, qo, name="q0") if outs[0] else None
                 x = aout.place(want_x.shape, torch.float32, xo, name="x") if outs[1] else None
                 rc = I.lib().sesrq_image_decode(ctx, src.data_ptr(), I._form(form), I._order(order), q.data_ptr() if q is not None else None,
-                                                x.data_ptr() if x is not None else None, 2, H, W, _stream())
+                                                x.data_ptr() if x is not None else None, 2, H, W, stream_ptr())
                 assert rc == 0, (what, I.last_error())
                 _clean(what, ain, aout)
                 if outs[0]:
-                    _same(what + " q0", q, want_q)
+                    same(what + " q0", q, want_q)
                 if outs[1]:
-                    _same(what + " x", x, want_x)
+                    same(what + " x", x, want_x)
 
 
 @pytest.mark.parametrize("dtype", ["f32", "i8"])
@@ -406,15 +378,15 @@ def test_image_export_in_hostile_surroundings(hw, Ch, dtype):
         want = IO.export(deq, order)
         for r, (canary, around_f32, around_i8, _) in enumerate(ROUNDS):
             what = f"export {dtype} C={Ch} {order} {H}x{W} at ({po}, {do}) run {r + 1}"
-            ain = Arena(_dev(), Arena.room(pred.nbytes), around_f32 if dtype == "f32" else around_i8)
+            ain = Arena(device(), Arena.room(pred.nbytes), around_f32 if dtype == "f32" else around_i8)
             src = _put(ain, pred, po, "pred")
-            aout = Arena(_dev(), Arena.room(want.nbytes), canary)
+            aout = Arena(device(), Arena.room(want.nbytes), canary)
             out = aout.place(want.shape, torch.uint8, do, name="out")
             rc = I.lib().sesrq_image_export(src.data_ptr(), I.PRED_F32 if dtype == "f32" else I.PRED_I8, scale, zero, Ch, I._order(order),
-                                            out.data_ptr(), 2, H, W, _stream())
+                                            out.data_ptr(), 2, H, W, stream_ptr())
             assert rc == 0, (what, I.last_error())
             _clean(what, ain, aout)
-            _same(what, out, want)
+            same(what, out, want)
 
 
 # =============================================================================================================== libsesrq_eval
@@ -464,44 +436,33 @@ def test_quality_score_in_hostile_surroundings(wide, form):
         po = EVAL_I8[i] if dt == "i8" else po
         for r, (canary, around_f32, around_i8, ws_fill) in enumerate(ROUNDS):
             what = f"eval {form} {H}x{W} at ({po}, {go}, {ao}) run {r + 1}"
-            af = Arena(_dev(), Arena.room(gt.nbytes, gt.nbytes, gt.nbytes), around_f32)
+            af = Arena(device(), Arena.room(gt.nbytes, gt.nbytes, gt.nbytes), around_f32)
             g = _put(af, gt, go, "gt")
-            a8 = Arena(_dev(), Arena.room(gt.nbytes), around_i8)
+            a8 = Arena(device(), Arena.room(gt.nbytes), around_i8)
             p = _put(a8 if dt == "i8" else af, pred, po, "pred")
             a = _put(af, lr, ao, "lr") if anchored else None
-            aout = Arena(_dev(), Arena.room(48, ws_bytes), canary)
+            aout = Arena(device(), Arena.room(48, ws_bytes), canary)
             out = aout.place((2, 3), torch.float64, 8 + 16 * (i % 2), name="out")
             ws = aout.place(ws_bytes, torch.uint8, 16, fill=ws_fill, name="workspace")
             if anchored:
                 rc = QL.anchored_lib().sesrq_eval_anchored(C.byref(desc), p.data_ptr(), a.data_ptr(), g.data_ptr(), 2, Ch, H, W,
-                                                           out.data_ptr(), ws.data_ptr(), ws_bytes, _stream())
+                                                           out.data_ptr(), ws.data_ptr(), ws_bytes, stream_ptr())
             else:
                 rc = QL.lib().sesrq_eval(C.byref(desc), p.data_ptr(), g.data_ptr(), 2, Ch, H, W, out.data_ptr(), ws.data_ptr(), ws_bytes,
-                                         _stream())
+                                         stream_ptr())
             assert rc == 0, (what, QL.last_error())
             _clean(what, af, a8, aout)
             _scores_ok(what, out.cpu().numpy(), want)
 
 
 # =============================================================================================================== calibration front end
-def _params(case):
-    p, pm = load_fixture(os.path.join(GOLDEN, f"{case}.params.npz"))
-    return [p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], {3: 1, 5: 4, 6: 2}[pm["mflag"]]
-
-
-def _pass_equals(what, cal, want):
-    assert cal.run_min == want.run_min, (what, cal.run_min, want.run_min)
-    assert cal.run_max == want.run_max, (what, cal.run_max, want.run_max)
-    assert cal.last_scale == want.last_scale and cal.last_zero == want.last_zero, (what, cal.last_zero, want.last_zero)
-
-
 @pytest.mark.parametrize("entry,case", [("enqueue", "nrdm_3"), ("enqueue", "sesr_x4"), ("enqueue_raw", "nrdm_3"),
                                         ("enqueue_image", "sesr_x4"), ("enqueue_image", "sesr_x2_rand")])
 def test_calibrator_frames_at_odd_offsets(entry, case):
     """Calibrator.enqueue / enqueue_raw / enqueue_image on one tiny frame at an odd element offset, its output at another: ranges and
     output equal calib_oracle.forward, as tests/test_calib_kernels.py requires of the aligned frame."""
     from sesrq.calibrate import Calibrator
-    Wf, bf, ps = _params(case)
+    Wf, bf, ps = calib_params(case)
     cin = Wf[0].shape[1]
     H, W = 9, 33
     rng = np.random.default_rng(len(entry) + cin)
@@ -510,32 +471,32 @@ def test_calibrator_frames_at_odd_offsets(entry, case):
         x, off = src, 4
     elif entry == "enqueue_raw":
         src = rng.integers(0, 4200, (1, H, W)).astype(np.uint16)
-        x, off = _spread(src, _levels(), F32(0)), 6
+        x, off = _spread(src, reference_levels(), F32(0)), 6
     else:
         src = rng.integers(0, 256, (1, H, W, 3)).astype(np.uint8)
         x, off = np.ascontiguousarray(IO.decode(src, "y" if cin == 1 else "rgb", "bgr")), 3
     want = CO.forward(Wf, bf, ps, [x], 8)
     for r, (canary, around_f32, around_i8, _) in enumerate(ROUNDS):
         what = f"{entry} {case} run {r + 1}"
-        cal = Calibrator(Wf, bf, ps, _dev(), quan_bits=8)
-        ain = Arena(_dev(), Arena.room(src.nbytes), around_f32 if entry == "enqueue" else around_i8)
+        cal = Calibrator(Wf, bf, ps, device(), quan_bits=8)
+        ain = Arena(device(), Arena.room(src.nbytes), around_f32 if entry == "enqueue" else around_i8)
         xin = _put(ain, src, off, "frame")
-        aout = Arena(_dev(), Arena.room(want.outputs[0].nbytes), canary)
+        aout = Arena(device(), Arena.room(want.outputs[0].nbytes), canary)
         out = aout.place(want.outputs[0].shape, torch.float32, 12, name="out")
         got = cal.enqueue(xin, out=out) if entry == "enqueue" else cal.enqueue_raw(xin, out=out) if entry == "enqueue_raw" \
             else cal.enqueue_image(xin, order="bgr", out=out)
         assert got.data_ptr() == out.data_ptr()
         _clean(what, ain, aout)
         cal.sync()
-        _same(what + " output", out, np.asarray(want.outputs[0], F32))
-        _pass_equals(what, cal, want)
+        same(what + " output", out, np.asarray(want.outputs[0], F32))
+        pass_equals(what, cal, want)
 
 
 # =============================================================================================================== Engine: caller outputs
 def test_engine_refuses_unusable_caller_outputs():
     """Engine.forward / forward_raw / forward_image write caller outputs through data_ptr(): a short buffer, a wrong dtype, a strided
     view or another device's tensor is a ValueError before any launch, never a device-memory overrun."""
-    dev = _dev()
+    dev = device()
     e2 = _engine("sesr_x2")
     e4 = _engine("sesr_x4")
     en = _engine("nrdm")
@@ -582,5 +543,5 @@ def test_engine_refuses_unusable_caller_outputs():
     rq, ry = e2.forward(x, out_q=q, out_f=y)
     torch.cuda.synchronize()
     assert rq is q and ry is y
-    _same("caller out_q", q, want["q_out"])
-    _same("caller out_f", y, want["y"])
+    same("caller out_q", q, want["q_out"])
+    same("caller out_f", y, want["y"])

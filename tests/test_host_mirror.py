@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, load_fixture
+from qat_calib_oracle import qat_state_dict
 import define
 import sim
 from myQL import quan_func as qf
@@ -261,26 +262,13 @@ def _plain_state_dict(mflag):
     return sim.MODELS[mflag]().state_dict()
 
 
-def _qat_state_dict(mflag):
-    """A state_dict shaped like the reference's *_qat_G.pth: conv weights + the buffers of both quantisers of every conv
-    + the QuantAdd state of the long-skip adds."""
-    from models import quantize_utils_pt as quantize
-    torch.manual_seed(4)
-    m = quantize.prepare(sim.MODELS[mflag](), a_bits=8, w_bits=8, q_type=0, q_level="C")
-    sd = dict(m.state_dict())
-    for add in ("add_residual", "add_upsampled_input"):
-        sd[f"{add}.activation_quantizer.scale"] = torch.ones(1)
-        sd[f"{add}.observer_res.min_val"] = torch.zeros(1)
-    return sd
-
-
 def test_qat_checkpoint_is_folded_through_the_fake_quantisers(tmp_path):
     """A *_qat_G.pth carries weight_quantizer / activation_quantizer state; the reference consumes it through
     quantize.prepare() (reference sim.py:64-66) and its collapse() then folds THROUGH the fake-quantisers.  The loader
     recognises such a checkpoint by its keys, prepares the net and folds it the same way: the result is NOT the fold of
     the raw conv weights (45..1129 differing INT8 weights when folded silently)."""
     from models import quantize_utils_pt as quantize
-    sd = _qat_state_dict(5)
+    sd = qat_state_dict(5)
     assert sum("_quantizer." in k for k in sd) == 10 * 14 + 2 and "conv_first.conv_expand.weight_quantizer.observer.max_val" in sd
     p = tmp_path / "fake_qat_G.pth"
     torch.save(sd, p)

@@ -6,7 +6,6 @@ CPU: the C ABI, the argument checks, the fixtures' SHA-256 values, the restateme
 export bytes, load_image.  GPU: decode against the reference and, exhaustively, against the restatement; load_gt; forward_image against
 the reference's outputs and against forward() on the fp32 frame; evaluate_image; export; sim.py; a side stream; the refusals; and
 that every kernel instantiation ran."""
-import hashlib
 import json
 import os
 import re
@@ -17,6 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
+from helpers import device, sha256
 
 import image_oracle as IO
 
@@ -25,10 +25,6 @@ HEADER = os.path.join(ROOT, "include", "sesrq_image.h")
 NETS = {"sesr_x4": 5, "sesr_x4_qat": 5, "sesr_x2_rand": 6}
 FRAMES = ("a", "b", "c")
 FORM = {5: "y", 6: "rgb"}
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 def frames():
@@ -55,20 +51,20 @@ def frame(f, mflag):
         from make_image_golden import natural_image
         lr, hr = natural_image(f, mflag)
     s = frames_sha()
-    assert sha(lr) == s[f"lr_{f}"] and sha(hr) == s[f"hr{mflag}_{f}"], f"frame {f} differs from the one the reference ran on"
+    assert sha256(lr) == s[f"lr_{f}"] and sha256(hr) == s[f"hr{mflag}_{f}"], f"frame {f} differs from the one the reference ran on"
     return lr, hr
 
 
 def ref_inp(f, mflag):
     """The reference's fp32 input frame (1, C, H, W), restated and checked against its SHA-256."""
     x = IO.decode(frame(f, mflag)[0], FORM[mflag])
-    assert sha(x) == frames_sha()[f"inp{mflag}_{f}"], (f, mflag)
+    assert sha256(x) == frames_sha()[f"inp{mflag}_{f}"], (f, mflag)
     return x
 
 
 def ref_gt(f, mflag):
     g = IO.decode(frame(f, mflag)[1], FORM[mflag])
-    assert sha(g) == frames_sha()[f"gt{mflag}_{f}"], (f, mflag)
+    assert sha256(g) == frames_sha()[f"gt{mflag}_{f}"], (f, mflag)
     return g
 
 
@@ -107,7 +103,7 @@ def test_restatement_equals_reference_inp_gt_and_input0(mflag):
             continue
         _, meta = net_fixture(net)
         for f in FRAMES:
-            assert sha(IO.q0(ref_inp(f, m), meta["scale"][0], meta["zero"][0])) == meta["sha"][f"input0_{f}"], (net, f)
+            assert sha256(IO.q0(ref_inp(f, m), meta["scale"][0], meta["zero"][0])) == meta["sha"][f"input0_{f}"], (net, f)
 
 
 @pytest.mark.parametrize("net", ["sesr_x4", "sesr_x2_rand"])
@@ -122,14 +118,14 @@ def test_export_restatement_equals_reference_bytes(net):
         x = ref_inp(f, m)
         st = O.forward(onet, x)
         y = st["y"].astype(np.float32)
-        assert sha(y) == meta["sha"][f"out_{f}"] and sha(st["q_out"]) == meta["sha"][f"out_q_{f}"], (net, f)
+        assert sha256(y) == meta["sha"][f"out_{f}"] and sha256(st["q_out"]) == meta["sha"][f"out_q_{f}"], (net, f)
         if m == 6:
             y = (y + IO.upsample2(x)).astype(np.float32)
-            assert sha(y) == meta["sha"][f"anchored_{f}"]
+            assert sha256(y) == meta["sha"][f"anchored_{f}"]
         else:
             assert np.array_equal(IO.dequant(st["q_out"], np.float32(meta["scale"][5]), meta["zero"][5]), y)
         for bo in ("rgb", "bgr"):
-            assert sha(IO.export(y, bo)) == meta["sha"][f"png_{bo}_{f}"], (net, f, bo)
+            assert sha256(IO.export(y, bo)) == meta["sha"][f"png_{bo}_{f}"], (net, f, bo)
 
 
 def test_rgb_table_equals_the_restatement():
@@ -218,11 +214,6 @@ def test_decode_and_export_argument_checks_without_a_device():
 
 
 # ------------------------------------------------------------------------------------------------------------------------ GPU
-def _dev():
-    import torch
-    return torch.device("cuda:0")
-
-
 def _bundle(net):
     from sesrq.bundle import Bundle
     return Bundle.load(os.path.join(IMG, net + ".npz"))
@@ -230,12 +221,12 @@ def _bundle(net):
 
 def _engine(net, **kw):
     import sesrq
-    return sesrq.Engine(_bundle(net), _dev(), **kw)
+    return sesrq.Engine(_bundle(net), device(), **kw)
 
 
 def _u8(a):
     import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(_dev())
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(device())
 
 
 def _batch(lr, n):
@@ -264,12 +255,12 @@ def test_decode_equals_reference_inp_and_input0(net, N, order):
         torch.cuda.synchronize()
         for q in (q_both, q_only):
             q = q.cpu().numpy()
-            assert sha(q[:1]) == meta["sha"][f"input0_{f}"], (net, f)
+            assert sha256(q[:1]) == meta["sha"][f"input0_{f}"], (net, f)
             for n in range(1, N):
                 assert np.array_equal(q[n], IO.q0(IO.decode(imgs[n], FORM[m]), b.scale[0], b.zero[0])[0]), (f, n)
         for x in (x_both, x_only):
             x = x.cpu().numpy()
-            assert sha(x[:1]) == frames_sha()[f"inp{m}_{f}"], (net, f)
+            assert sha256(x[:1]) == frames_sha()[f"inp{m}_{f}"], (net, f)
             for n in range(1, N):
                 assert x[n].tobytes() == IO.decode(imgs[n], FORM[m])[0].tobytes(), (f, n)
 
@@ -289,13 +280,13 @@ def test_decode_y_exhaustive_every_triple():
     x_ref = IO.decode_y(img[None])
     d = _u8(img[None])
     db = _u8(bgr(img)[None])
-    q = torch.empty((1, 1, 4096, 4096), dtype=torch.int8, device=_dev())
-    x = torch.empty((1, 1, 4096, 4096), dtype=torch.float32, device=_dev())
-    st = torch.cuda.current_stream(_dev())
+    q = torch.empty((1, 1, 4096, 4096), dtype=torch.int8, device=device())
+    x = torch.empty((1, 1, 4096, 4096), dtype=torch.float32, device=device())
+    st = torch.cuda.current_stream(device())
     for s0, z0 in ((0.0022352789546929153, -214), (0.0037, -145)):
         for ed in (0, 1, 2):
             for src, order in ((d, "rgb"), (db, "bgr")):
-                I.launch(_dev(), s0, z0, ed, src, "y", order, q, x, st)
+                I.launch(device(), s0, z0, ed, src, "y", order, q, x, st)
                 torch.cuda.synchronize()
                 assert x.cpu().numpy().tobytes() == x_ref.tobytes(), (s0, ed, order)
                 assert np.array_equal(q.cpu().numpy(), IO.q0(x_ref, s0, z0, ed)), (s0, z0, ed, order)
@@ -312,9 +303,9 @@ def test_decode_rgb_exhaustive_every_code():
         for ed in (0, 1, 2):
             for order in ("rgb", "bgr"):
                 d = _u8((bgr(img) if order == "bgr" else img)[None])
-                q = torch.empty((1, 3, 16, 16), dtype=torch.int8, device=_dev())
-                x = torch.empty((1, 3, 16, 16), dtype=torch.float32, device=_dev())
-                I.launch(_dev(), s0, z0, ed, d, "rgb", order, q, x, torch.cuda.current_stream(_dev()))
+                q = torch.empty((1, 3, 16, 16), dtype=torch.int8, device=device())
+                x = torch.empty((1, 3, 16, 16), dtype=torch.float32, device=device())
+                I.launch(device(), s0, z0, ed, d, "rgb", order, q, x, torch.cuda.current_stream(device()))
                 torch.cuda.synchronize()
                 assert x.cpu().numpy().tobytes() == x_ref.tobytes(), (s0, ed, order)
                 assert np.array_equal(q.cpu().numpy(), IO.q0(x_ref, s0, z0, ed)), (s0, z0, ed, order)
@@ -326,9 +317,9 @@ def test_load_gt_equals_reference_gt():
     for m in (5, 6):
         for f in FRAMES:
             hr = frame(f, m)[1]
-            g = I.load_gt(hr, m, _dev()).cpu().numpy()
-            assert g.dtype == np.float32 and sha(g) == frames_sha()[f"gt{m}_{f}"], (m, f)
-            assert sha(I.load_gt(bgr(hr), m, _dev(), order="bgr").cpu().numpy()) == frames_sha()[f"gt{m}_{f}"]
+            g = I.load_gt(hr, m, device()).cpu().numpy()
+            assert g.dtype == np.float32 and sha256(g) == frames_sha()[f"gt{m}_{f}"], (m, f)
+            assert sha256(I.load_gt(bgr(hr), m, device(), order="bgr").cpu().numpy()) == frames_sha()[f"gt{m}_{f}"]
 
 
 @pytest.mark.gpu
@@ -343,8 +334,8 @@ def test_forward_image_equals_reference_outputs(net):
             lr = frame(f, m)[0]
             q, y = e.forward_image(_u8(bgr(lr) if order == "bgr" else lr), order=order)
             torch.cuda.synchronize()
-            assert sha(q.cpu().numpy()) == meta["sha"][f"out_q_{f}"], (net, f)
-            assert sha(y.cpu().numpy()) == meta["sha"][f"anchored_{f}" if m == 6 else f"out_{f}"], (net, f)
+            assert sha256(q.cpu().numpy()) == meta["sha"][f"out_q_{f}"], (net, f)
+            assert sha256(y.cpu().numpy()) == meta["sha"][f"anchored_{f}" if m == 6 else f"out_{f}"], (net, f)
 
 
 @pytest.mark.gpu
@@ -397,10 +388,10 @@ def test_export_equals_restatement_and_reference_bytes():
         p.reshape(-1)[:6] = [0.0, 1.0, -0.0, 1.0000001, np.float32(254.5 / 255), np.float32(1 / 255)]
         qi = rng.integers(-128, 128, shape).astype(np.int8)
         for order in ("rgb", "bgr"):
-            got = I.export(torch.from_numpy(p).to(_dev()), order=order).cpu().numpy()
+            got = I.export(torch.from_numpy(p).to(device()), order=order).cpu().numpy()
             assert np.array_equal(got, IO.export(p, order)), (shape, order)
             for s, z in ((0.0049, -128), (0.0031, -77)):
-                got = I.export(torch.from_numpy(qi).to(_dev()), order=order, scale=s, zero=z).cpu().numpy()
+                got = I.export(torch.from_numpy(qi).to(device()), order=order, scale=s, zero=z).cpu().numpy()
                 assert np.array_equal(got, IO.export(IO.dequant(qi, np.float32(s), z), order)), (shape, order, s)
     # the nets' outputs: int8 (MFLAG 5) and the anchored fp32 x2 output against the reference's export bytes
     for net, m in NETS.items():
@@ -410,14 +401,14 @@ def test_export_equals_restatement_and_reference_bytes():
         for f in FRAMES:
             q, y = e.forward_image(_u8(frame(f, m)[0]))
             for order in ("rgb", "bgr"):
-                assert sha(I.export(y, order=order).cpu().numpy()) == meta["sha"][f"png_{order}_{f}"], (net, f, order)
+                assert sha256(I.export(y, order=order).cpu().numpy()) == meta["sha"][f"png_{order}_{f}"], (net, f, order)
                 if m == 5:
                     u = I.export(q, order=order, scale=e.bundle.scale[L], zero=e.bundle.zero[L]).cpu().numpy()
-                    assert sha(u) == meta["sha"][f"png_{order}_{f}"], (net, f, order)
+                    assert sha256(u) == meta["sha"][f"png_{order}_{f}"], (net, f, order)
     with pytest.raises(ValueError, match="scale and zero"):
         I.export(q)
     with pytest.raises(ValueError, match="channels"):
-        I.export(torch.zeros((1, 2, 4, 4), device=_dev()))
+        I.export(torch.zeros((1, 2, 4, 4), device=device()))
 
 
 @pytest.mark.gpu
@@ -464,7 +455,7 @@ def test_forward_image_refusals():
     with pytest.raises(ValueError, match="1 channel"):
         e6.forward_image(lr, form="y")
     nrdm = Bundle.load(os.path.join(GOLDEN, "raw", "nrdm_3.npz"))
-    chained = sesrq.Engine(_bundle("sesr_x2_rand"), _dev(), upstream=nrdm)
+    chained = sesrq.Engine(_bundle("sesr_x2_rand"), device(), upstream=nrdm)
     with pytest.raises(ValueError, match="upstream"):
         chained.forward_image(lr)
     with pytest.raises(ValueError, match="uint8"):
@@ -484,14 +475,14 @@ def test_forward_image_on_a_side_stream(net):
     m = NETS[net]
     e = _engine(net, anchor_add=m == 6)
     want = net_fixture(net)[1]["sha"]["out_q_b"]
-    dev = _dev()
+    dev = device()
     side = torch.cuda.Stream(device=dev)
     src = torch.from_numpy(frame("b", m)[0].astype(np.int32)).to(dev)
     for _ in range(3):
         x = (src * 1).to(torch.uint8)                 # produced on the current stream just before the call
         q, y = e.forward_image(x, stream=side)
         side.synchronize()
-        assert sha(q.cpu().numpy()) == want
+        assert sha256(q.cpu().numpy()) == want
         del x
 
 

@@ -20,10 +20,10 @@ import pytest
 import torch
 
 from conftest import GOLDEN
-from helpers import bundle_from_oracle, fixture_case
+from helpers import bundle_from_oracle, device, fixture_case, same
 import sesrq
 from sesrq import _lib
-from test_instances import CROPS, OUT_KINDS, Track, dev, eq, plan_variants, shuffle
+from instances import CROPS, OUT_KINDS, Track, plan_variants, shuffle
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +41,7 @@ def trace_crop(path):
     """{case label: {"engines": [per layer], "launches": {instance name: launches of ONE forward}}} of one golden crop."""
     fx, meta, net, x = fixture_case(path)
     want_q, want_f = shuffle(fx["input5"], net.pixel_shuffle), fx["out"]
-    inputs = {"f32": torch.from_numpy(x).to(dev()), "i8": torch.from_numpy(fx["input0"]).to(dev())}
+    inputs = {"f32": torch.from_numpy(x).to(device()), "i8": torch.from_numpy(fx["input0"]).to(device())}
     b = bundle_from_oracle(net)
     out = {}
 
@@ -51,15 +51,15 @@ def trace_crop(path):
             torch.cuda.synchronize()
             after = _lib.instances()
             if q is not None:
-                eq(f"{case} q_out", q, want_q)
+                same(f"{case} q_out", q, want_q)
             if y is not None:
-                eq(f"{case} y", y, want_f)
+                same(f"{case} y", y, want_f)
         assert case not in out
         out[case] = {"engines": e.layer_engines(), "launches": {k: v - t.before.get(k, 0) for k, v in after.items() if v > t.before.get(k, 0)}}
 
-    stream = torch.cuda.Stream(device=dev())
+    stream = torch.cuda.Stream(device=device())
     for kw in plan_variants():
-        e = sesrq.Engine(b, dev(), **kw)
+        e = sesrq.Engine(b, device(), **kw)
         for src, xt in inputs.items():
             for wq, wf in OUT_KINDS:
                 record(f"{label(kw)}|{src}|q{int(wq)}f{int(wf)}", e, lambda: e.forward(xt, want_q=wq, want_f=wf))
@@ -67,21 +67,21 @@ def trace_crop(path):
                     continue
                 # two frames of one stream as the images of ONE launch sequence (sesrq_forward_many, group = 2)
                 frames = [xt.clone() for _ in range(2)]
-                oq = [torch.zeros(want_q.shape, dtype=torch.int8, device=dev()) for _ in range(2)] if wq else None
-                of = [torch.zeros(want_f.shape, dtype=torch.float32, device=dev()) for _ in range(2)] if wf else None
+                oq = [torch.zeros(want_q.shape, dtype=torch.int8, device=device()) for _ in range(2)] if wq else None
+                of = [torch.zeros(want_f.shape, dtype=torch.float32, device=device()) for _ in range(2)] if wf else None
                 torch.cuda.synchronize()
 
                 def grouped():
                     e.submission(frames, oq, [stream], outs_f=of, group=2).enqueue(2)
                     torch.cuda.synchronize()
                     if oq:
-                        eq("grouped frame 0 q_out", oq[0], want_q)
+                        same("grouped frame 0 q_out", oq[0], want_q)
                     if of:
-                        eq("grouped frame 0 y", of[0], want_f)
+                        same("grouped frame 0 y", of[0], want_f)
                     return (oq[1] if oq else None), (of[1] if of else None)
                 record(f"{label(kw)}|{src}|q{int(wq)}f{int(wf)}|group2", e, grouped)
     for kw in (dict(), dict(engine=_lib.ENGINE_DOT4), dict(force_general=True), dict(reduced_forms=0)):
-        e = sesrq.Engine(b, dev(), **kw)
+        e = sesrq.Engine(b, device(), **kw)
         for src, xt in inputs.items():
             for name, taps in DEBUG_TAPS.items():
                 def debug():

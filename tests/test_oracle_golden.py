@@ -1,20 +1,16 @@
 """Pins the numpy oracle (oracle/sesrq_oracle.py) to the reference: every stage of every
 golden fixture (produced by running the reference itself, tests/golden/make_golden.py) must
 be reproduced bit-for-bit."""
-import hashlib
 import os
 
 import numpy as np
 import pytest
 
 from conftest import golden_files, load_fixture, fixture_input, big_cases, big_input, GOLDEN
+from helpers import sha256
 from oracle import sesrq_oracle as O
 
 STAGE_FILES = [f for f in golden_files() if not f.endswith((".params.npz", "tables.npz", ".stimtxt.npz", ".anchor.npz"))]
-
-
-def _sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 @pytest.mark.parametrize("path", STAGE_FILES, ids=[os.path.basename(p)[:-4] for p in STAGE_FILES])
@@ -28,7 +24,7 @@ def test_forward_matches_reference_stage_by_stage(path):
         got = st[inv.get(name, name)]
         if name.startswith("input") and name != "input4_special":
             got = got.astype(np.int8)
-        assert _sha(got) == want_sha, f"{name} differs from the reference"
+        assert sha256(got) == want_sha, f"{name} differs from the reference"
     # stored arrays (crops keep everything) compared element-wise too, for readable failures
     for name in fx.files:
         if name in ("meta", "x") or name.startswith(("Wq", "add_const")):
@@ -49,10 +45,10 @@ def test_c_oracle_matches_the_reference_at_config2_size():
     fx, meta = load_fixture(os.path.join(GOLDEN, "sesr_x2_rand.crop.npz"))
     net = O.net_from_fixture(fx)
     x = torch.rand((1, 3, 1080, 1920), generator=torch.Generator().manual_seed(1), dtype=torch.float32).numpy()
-    assert _sha(x) == ref["x_sha256"]
+    assert sha256(x) == ref["x_sha256"]
     r = CO.forward(net, x, threads=min(os.cpu_count() or 1, 8), want_f=True)
     assert list(r["q_out"].shape) == ref["out_shape"]
-    assert _sha(r["q_out"]) == ref["out_q_sha256"] and _sha(r["y"]) == ref["out_f_sha256"]
+    assert sha256(r["q_out"]) == ref["out_q_sha256"] and sha256(r["y"]) == ref["out_f_sha256"]
 
 
 BIG = big_cases()
@@ -69,7 +65,7 @@ def test_c_oracle_matches_the_reference_on_baseline_size_natural_frames(rec):
     net = O.net_from_fixture(fx)
     r = CO.forward(net, big_input(rec), threads=min(os.cpu_count() or 1, 8), want_f=True)
     assert list(r["q_out"].shape) == rec["out_shape"]
-    assert _sha(r["q_out"]) == rec["out_q_sha256"] and _sha(r["y"]) == rec["out_f_sha256"]
+    assert sha256(r["q_out"]) == rec["out_q_sha256"] and sha256(r["y"]) == rec["out_f_sha256"]
 
 
 def test_qconst_table():
@@ -115,9 +111,9 @@ def test_c_oracle_matches_reference(path):
     r = CO.forward(net, fixture_input(fx, meta), keep=True)
     for k in range(5):
         for nm in (f"input{k}", f"pe_out{k}", f"pe_add{k}"):
-            assert _sha(r[nm]) == meta["sha"][nm], nm
-    assert _sha(r["y"]) == meta["sha"]["out"]
-    assert _sha(O.forward(net, fixture_input(fx, meta))["q_out"]) == _sha(r["q_out"])
+            assert sha256(r[nm]) == meta["sha"][nm], nm
+    assert sha256(r["y"]) == meta["sha"]["out"]
+    assert sha256(O.forward(net, fixture_input(fx, meta))["q_out"]) == sha256(r["q_out"])
 
 
 def test_c_oracle_vs_numpy_oracle_batches_and_depth():

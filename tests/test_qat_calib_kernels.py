@@ -13,10 +13,9 @@ import numpy as np
 import pytest
 
 import qat_calib_oracle as QO
-import test_calib_kernels as K
-import test_calib_oracle as T
-import test_qat_calib_oracle as TQ
+import calib_cases as K
 from conftest import GOLDEN, load_fixture
+from helpers import PIXEL_SHUFFLE, calib_params, device, pass_equals, same, stream_ptr, to_device
 from oracle import calib_oracle as CO
 
 F32 = np.float32
@@ -37,19 +36,19 @@ def run_qadd(entry, x, wq, d, b, relu, skip, s):
     lib = _lib.lib()
     N, ic, H, W = x.shape
     oc, _, k, _ = wq.shape
-    xt, wt, qb, st = K._t(x), K._t(wq), K._t(d.qbias.astype(F32)), K._t(skip)
-    out = torch.full((N, oc, H, W), float("nan"), dtype=torch.float32, device=K._dev())
+    xt, wt, qb, st = to_device(x), to_device(wq), to_device(d.qbias.astype(F32)), to_device(skip)
+    out = torch.full((N, oc, H, W), float("nan"), dtype=torch.float32, device=device())
     desc = _lib.CalibConvDesc(k=k, ic=ic, oc=oc, w=wt.data_ptr(), qbias=qb.data_ptr(), in_scale=float(d.scale32), in_zero=d.zero,
                               ss=float(d.ss), acc_lo=float(d.acc_lo), acc_hi=float(d.acc_hi), add_lo=float(d.add_lo),
                               add_hi=float(d.add_hi), relu=int(relu))
     before = _lib.qadd_instances()
     if entry == "q":
-        _lib.check(lib.sesrq_calib_conv_qadd(C.byref(desc), xt.data_ptr(), st.data_ptr(), out.data_ptr(), N, H, W, b, float(s), K._st()))
+        _lib.check(lib.sesrq_calib_conv_qadd(C.byref(desc), xt.data_ptr(), st.data_ptr(), out.data_ptr(), N, H, W, b, float(s), stream_ptr()))
     else:
         desc.qbias, desc.in_scale, desc.in_zero = None, 0.0, 0
-        slot = K._slot_bytes(d)
+        slot = K.slot_bytes(d)
         _lib.check(lib.sesrq_calib_conv_slot_qadd(C.byref(desc), slot.data_ptr(), xt.data_ptr(), st.data_ptr(), out.data_ptr(), N, H, W,
-                                                  b, float(s), K._st()))
+                                                  b, float(s), stream_ptr()))
     torch.cuda.synchronize()
     _track(before)
     return out
@@ -97,7 +96,7 @@ def test_qadd_conv_bit_exact_with_the_oracle(entry):
             assert np.any(np.abs(u) - np.floor(np.abs(u)) == F32(0.5)), "ties must occur"
         want = QO.merge(v, skip, s)
         what = f"{entry} k{k}-ic{ic}-oc{oc}-n{N}-{H}x{W}-b{b}-z{kind}-s{float(s)!r}"
-        K._eq(what, run_qadd(entry, x, wq, d, b, relu, skip, s), want)
+        same(what, run_qadd(entry, x, wq, d, b, relu, skip, s), want, values=True, cast=np.float32)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- whole pass
@@ -105,7 +104,7 @@ def _frames(rng, cin, dataset=False):
     """A 1 x C x 9 x 35 and a 2 x C x 17 x 33 batch of noise.  dataset: crops of the raw dataset frames a, b, c instead -- noise leaves
     the 2-bit nrdm_3's last output constant (with the float add as well), which the pass refuses as the reference does."""
     if dataset:
-        a, b, c = T.dataset_frames("nrdm_3", 3)
+        a, b, c = K.dataset_frames("nrdm_3", 3)
         return [np.ascontiguousarray(a[:, :, :9, :35]), np.ascontiguousarray(np.concatenate([b[:, :, :17, :33], c[:, :, :17, :33]]))]
     return [rng.random((1, cin, 9, 35)).astype(F32), (rng.random((2, cin, 17, 33)) * 1.3 - 0.1).astype(F32)]
 
@@ -138,7 +137,7 @@ def test_whole_pass_with_the_quantised_merge_equals_the_oracle(case, b):
     give the same bundle."""
     import torch
     from sesrq.calibrate import Calibrator
-    Wf, bf, ps = K._params(case)
+    Wf, bf, ps = calib_params(case)
     cin = Wf[0].shape[1]
     rng = np.random.default_rng(zlib.crc32(f"qat.{case}.{b}".encode()))
     frames = _frames(rng, cin, dataset=(case, b) == ("nrdm_3", 2))
@@ -148,20 +147,20 @@ def test_whole_pass_with_the_quantised_merge_equals_the_oracle(case, b):
     for bi in want.inputs:          # the merge's upper clamp fires on the shortcut (behind ReLUs the lower one cannot: the conv test has it)
         assert float(bi[1].max()) > 128.5 * float(s)
     assert float(F32(127.0) * s) <= want.run_max[4] <= float(F32(F32(127.0) * s) + F32(F32(127.0) * s))
-    host = Calibrator(Wf, bf, ps, K._dev(), quan_bits=b, skip_quant_scale=float(s))
-    dev = Calibrator(Wf, bf, ps, K._dev(), quan_bits=b, skip_quant_scale=float(s))
+    host = Calibrator(Wf, bf, ps, device(), quan_bits=b, skip_quant_scale=float(s))
+    dev = Calibrator(Wf, bf, ps, device(), quan_bits=b, skip_quant_scale=float(s))
     from sesrq import _lib
     before = _lib.qadd_instances()
     for i, x in enumerate(frames):
-        K._eq(f"{case} b={b} observe {i}", host.observe(K._t(x)), want.outputs[i])
+        same(f"{case} b={b} observe {i}", host.observe(to_device(x)), want.outputs[i], values=True, cast=np.float32)
         _domains_equal(f"{case} b={b} observe {i}", host, want.domains[i])
-        y = dev.enqueue(K._t(x))
+        y = dev.enqueue(to_device(x))
         dev.sync()
-        K._eq(f"{case} b={b} enqueue {i}", y, want.outputs[i])
+        same(f"{case} b={b} enqueue {i}", y, want.outputs[i], values=True, cast=np.float32)
         _domains_equal(f"{case} b={b} enqueue {i}", dev, want.domains[i])
     _track(before)
-    K._pass_equals(f"{case} b={b} observe", host, want)
-    K._pass_equals(f"{case} b={b} enqueue", dev, want)
+    pass_equals(f"{case} b={b} observe", host, want)
+    pass_equals(f"{case} b={b} enqueue", dev, want)
     _same_bundle(f"{case} b={b}", dev.bundle(), host.bundle())
     plain = CO.forward(Wf, bf, ps, frames, b, keep_outputs=False)
     assert plain.run_max[4] != want.run_max[4]                  # and it is not the float add
@@ -175,16 +174,16 @@ def test_four_entry_points_agree(case):
     host pass with it."""
     import torch
     from sesrq.calibrate import Calibrator
-    Wf, bf, ps = K._params(case)
+    Wf, bf, ps = calib_params(case)
     cin = Wf[0].shape[1]
     rng = np.random.default_rng(zlib.crc32(f"four.{case}".encode()))
     s = 0.0031
-    mk = lambda **kw: Calibrator(Wf, bf, ps, K._dev(), quan_bits=8, skip_quant_scale=s, **kw)
+    mk = lambda **kw: Calibrator(Wf, bf, ps, device(), quan_bits=8, skip_quant_scale=s, **kw)
     front = mk()
     if case == "nrdm_3":
-        outs = [front.enqueue_raw(torch.from_numpy(rng.integers(0, 4096, size=(2, 18, 34)).astype(np.uint16)).to(K._dev())).clone()]
+        outs = [front.enqueue_raw(torch.from_numpy(rng.integers(0, 4096, size=(2, 18, 34)).astype(np.uint16)).to(device())).clone()]
     else:
-        outs = [front.enqueue_image(torch.from_numpy(rng.integers(0, 256, size=(2, 17, 33, 3)).astype(np.uint8)).to(K._dev())).clone()]
+        outs = [front.enqueue_image(torch.from_numpy(rng.integers(0, 256, size=(2, 17, 33, 3)).astype(np.uint8)).to(device())).clone()]
     x = front.last_input.clone()
     front.sync()
     assert x.shape[1] == cin
@@ -193,11 +192,11 @@ def test_four_entry_points_agree(case):
     outs += [host.observe(x), dev.enqueue(x)]
     dev.sync()
     for name, y, cal in zip(("front", "observe", "enqueue"), outs, (front, host, dev)):
-        K._eq(f"{case} {name}", y, want.outputs[0])
-        K._pass_equals(f"{case} {name}", cal, want)
+        same(f"{case} {name}", y, want.outputs[0], values=True, cast=np.float32)
+        pass_equals(f"{case} {name}", cal, want)
         _same_bundle(f"{case} {name}", cal.bundle(), host.bundle())
     ent = mk(method="entropy")
-    K._eq(f"{case} entropy pass 1", ent.observe(x), want.outputs[0])
+    same(f"{case} entropy pass 1", ent.observe(x), want.outputs[0], values=True, cast=np.float32)
     ent.begin_histogram_pass()
     ent.observe(x)
     scale, zero = ent.finalize()
@@ -211,23 +210,23 @@ def test_none_is_the_float_add(case):
     on both passes, and no launch of a quantised-merge kernel."""
     from sesrq import _lib
     from sesrq.calibrate import Calibrator
-    Wf, bf, ps = K._params(case)
+    Wf, bf, ps = calib_params(case)
     rng = np.random.default_rng(zlib.crc32(f"none.{case}".encode()))
     frames = _frames(rng, Wf[0].shape[1])
     want = CO.forward(Wf, bf, ps, frames, 8)
     before = _lib.qadd_instances()
-    host = Calibrator(Wf, bf, ps, K._dev(), quan_bits=8, skip_quant_scale=None)
-    dev = Calibrator(Wf, bf, ps, K._dev(), quan_bits=8)
+    host = Calibrator(Wf, bf, ps, device(), quan_bits=8, skip_quant_scale=None)
+    dev = Calibrator(Wf, bf, ps, device(), quan_bits=8)
     assert host.skip_quant_scale is None and dev.skip_quant_scale is None
     for i, x in enumerate(frames):
-        K._eq(f"{case} observe {i}", host.observe(K._t(x)), want.outputs[i])
+        same(f"{case} observe {i}", host.observe(to_device(x)), want.outputs[i], values=True, cast=np.float32)
         _domains_equal(f"{case} observe {i}", host, want.domains[i])
-        y = dev.enqueue(K._t(x))
+        y = dev.enqueue(to_device(x))
         dev.sync()
-        K._eq(f"{case} enqueue {i}", y, want.outputs[i])
+        same(f"{case} enqueue {i}", y, want.outputs[i], values=True, cast=np.float32)
         _domains_equal(f"{case} enqueue {i}", dev, want.domains[i])
-    K._pass_equals(f"{case} observe", host, want)
-    K._pass_equals(f"{case} enqueue", dev, want)
+    pass_equals(f"{case} observe", host, want)
+    pass_equals(f"{case} enqueue", dev, want)
     assert _lib.qadd_instances() == before
 
 
@@ -238,7 +237,7 @@ class _Ranges:
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("record,frames_of", [(r, None) for r in TQ.ONE_FRAME] + sorted(TQ.LOOPS.items()))
+@pytest.mark.parametrize("record,frames_of", [(r, None) for r in K.ONE_FRAME] + sorted(K.LOOPS.items()))
 def test_calibrator_reproduces_the_reference_records(record, frames_of):
     """Calibrator with the checkpoint's scale (qat_add.json) on the committed 80 x 960 frames and on the three-frame loops: the
     reference's running ranges, zero points and scales to the bars of test_qat_calib_oracle.py; the bundle carries the record's zero
@@ -246,13 +245,13 @@ def test_calibrator_reproduces_the_reference_records(record, frames_of):
     from sesrq.calibrate import Calibrator
     p, pm = load_fixture(os.path.join(GOLDEN, f"{record}.params.npz"))
     rec = pm if frames_of is None else load_fixture(os.path.join(GOLDEN, "calib", f"{record}.npz"))[1]
-    frames = [T.frame_of(pm)] if frames_of is None else T.dataset_frames(frames_of, pm["mflag"])
-    cal = Calibrator([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], T.PS[pm["mflag"]], K._dev(), quan_bits=8,
-                     skip_quant_scale=float(TQ.scale_of(record)))
+    frames = [K.frame_of(pm)] if frames_of is None else K.dataset_frames(frames_of, pm["mflag"])
+    cal = Calibrator([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], PIXEL_SHUFFLE[pm["mflag"]], device(), quan_bits=8,
+                     skip_quant_scale=float(K.scale_of(record)))
     for x in frames:
-        cal.enqueue(K._t(x))
+        cal.enqueue(to_device(x))
     b = cal.bundle()
-    TQ.assert_record(record if frames_of is None else "loop " + record, _Ranges(cal), rec)
+    K.assert_record(record if frames_of is None else "loop " + record, _Ranges(cal), rec)
     assert list(b.zero) == rec["zero"]
 
 
@@ -264,11 +263,10 @@ def test_cli_on_a_synthetic_qat_checkpoint(tmp_path, capsys):
     import torch
     import sim
     from sesrq.calibrate import Calibrator
-    from test_calib_dataset import load_test_py
-    add = TQ.ADD["nrdm_3_qat"]
+    add = K.ADD["nrdm_3_qat"]
     ckpt = str(tmp_path / "fake_qat_G.pth")
-    torch.save(TQ._qat_state_dict(3, add), ckpt)
-    s = float(TQ.scale_of("nrdm_3_qat"))
+    torch.save(QO.qat_state_dict(3, add), ckpt)
+    s = float(K.scale_of("nrdm_3_qat"))
     rng = np.random.default_rng(9)
     frames = rng.random((2, 3, 17, 33)).astype(F32)
     fpath = str(tmp_path / "frames.npy")
@@ -276,12 +274,12 @@ def test_cli_on_a_synthetic_qat_checkpoint(tmp_path, capsys):
     m = sim.float_model(3, ckpt=ckpt)
     convs = [m.conv_first.conv_expand] + [blk.conv_expand for blk in m.residual_block] + [m.conv_last.conv_expand]
     Wf, bf = [c.weight.detach().numpy() for c in convs], [c.bias.detach().numpy() for c in convs]
-    mod = load_test_py()
+    mod = K.load_test_py()
 
     def by_hand(skip_s):
-        cal = Calibrator(Wf, bf, 1, K._dev(), quan_bits=8, skip_quant_scale=skip_s)
+        cal = Calibrator(Wf, bf, 1, device(), quan_bits=8, skip_quant_scale=skip_s)
         for i in range(2):
-            cal.observe(K._t(frames[i:i + 1]))
+            cal.observe(to_device(frames[i:i + 1]))
         return cal.finalize()
 
     capsys.readouterr()
@@ -295,7 +293,7 @@ def test_cli_on_a_synthetic_qat_checkpoint(tmp_path, capsys):
     plain = mod.main(["--mflag", "3", "--ckpt", ckpt, "--frames", fpath, "--float-skip"])
     assert "skip_quant_scale: none" in capsys.readouterr().out
     want = CO.forward(Wf, bf, 1, [frames[0:1], frames[1:2]], 8, keep_outputs=False)
-    assert (list(plain[0]), list(plain[1])) == tuple(map(list, T.finalize(want, 8)))
+    assert (list(plain[0]), list(plain[1])) == tuple(map(list, K.finalize(want, 8)))
     assert list(plain[0]) != list(got[0])
     params = str(tmp_path / "net.params.npz")
     np.savez(params, meta=np.array(json.dumps({"case": "synthetic", "mflag": 3})), **{f"Wf{k}": Wf[k] for k in range(5)},
@@ -320,28 +318,28 @@ def test_bad_scale_is_refused_before_any_launch():
     lib = _lib.lib()
     rng = np.random.default_rng(3)
     d = CO.domain(0.0, 1.5, 8, 0.0113, np.zeros(16, F32))
-    x, wq = K._t(rng.random((1, 16, 9, 35)).astype(F32)), K._t(K.weights(rng, 16, 16, 3, 8))
-    qb, skip = K._t(d.qbias), K._t(rng.random((1, 16, 9, 35)).astype(F32))
-    out = torch.zeros((1, 16, 9, 35), dtype=torch.float32, device=K._dev())
+    x, wq = to_device(rng.random((1, 16, 9, 35)).astype(F32)), to_device(K.weights(rng, 16, 16, 3, 8))
+    qb, skip = to_device(d.qbias), to_device(rng.random((1, 16, 9, 35)).astype(F32))
+    out = torch.zeros((1, 16, 9, 35), dtype=torch.float32, device=device())
     desc = _lib.CalibConvDesc(k=3, ic=16, oc=16, w=wq.data_ptr(), qbias=qb.data_ptr(), in_scale=float(d.scale32), in_zero=d.zero,
                               ss=float(d.ss), acc_lo=float(d.acc_lo), acc_hi=float(d.acc_hi), add_lo=float(d.add_lo),
                               add_hi=float(d.add_hi), relu=1)
-    slot = K._slot_bytes(d)
+    slot = K.slot_bytes(d)
     torch.cuda.synchronize()
     launches = sum(_lib.instances().values()) + sum(_lib.qadd_instances().values())
     for s in (0.0, -0.004, float("nan"), float("inf"), -float("inf")):
-        assert lib.sesrq_calib_conv_qadd(C.byref(desc), x.data_ptr(), skip.data_ptr(), out.data_ptr(), 1, 9, 35, 8, s, K._st()) == 1
+        assert lib.sesrq_calib_conv_qadd(C.byref(desc), x.data_ptr(), skip.data_ptr(), out.data_ptr(), 1, 9, 35, 8, s, stream_ptr()) == 1
         assert "skip_scale" in _lib.last_error()
         assert lib.sesrq_calib_conv_slot_qadd(C.byref(desc), slot.data_ptr(), x.data_ptr(), skip.data_ptr(), out.data_ptr(), 1, 9, 35, 8, s,
-                                              K._st()) == 1
+                                              stream_ptr()) == 1
         assert "skip_scale" in _lib.last_error()
         with pytest.raises(ValueError, match="skip_quant_scale"):
-            Calibrator(*K._params("nrdm_3"), K._dev(), skip_quant_scale=s)
-    assert lib.sesrq_calib_conv_qadd(C.byref(desc), x.data_ptr(), None, out.data_ptr(), 1, 9, 35, 8, 0.01, K._st()) == 1
-    assert lib.sesrq_calib_conv_slot_qadd(C.byref(desc), slot.data_ptr(), x.data_ptr(), None, out.data_ptr(), 1, 9, 35, 8, 0.01, K._st()) == 1
-    assert lib.sesrq_calib_conv_qadd(C.byref(desc), x.data_ptr(), skip.data_ptr(), out.data_ptr(), 1, 9, 35, 9, 0.01, K._st()) == 1
+            Calibrator(*calib_params("nrdm_3"), device(), skip_quant_scale=s)
+    assert lib.sesrq_calib_conv_qadd(C.byref(desc), x.data_ptr(), None, out.data_ptr(), 1, 9, 35, 8, 0.01, stream_ptr()) == 1
+    assert lib.sesrq_calib_conv_slot_qadd(C.byref(desc), slot.data_ptr(), x.data_ptr(), None, out.data_ptr(), 1, 9, 35, 8, 0.01, stream_ptr()) == 1
+    assert lib.sesrq_calib_conv_qadd(C.byref(desc), x.data_ptr(), skip.data_ptr(), out.data_ptr(), 1, 9, 35, 9, 0.01, stream_ptr()) == 1
     with pytest.raises(ValueError, match="skip_quant_scale"):
-        Calibrator(*K._params("nrdm_3"), K._dev(), skip_quant_scale="0.1")
+        Calibrator(*calib_params("nrdm_3"), device(), skip_quant_scale="0.1")
     torch.cuda.synchronize()
     assert sum(_lib.instances().values()) + sum(_lib.qadd_instances().values()) == launches, "a refused call launched a kernel"
     assert not out.any()

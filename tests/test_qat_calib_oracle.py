@@ -5,7 +5,6 @@ Records: the four one-frame records tests/golden/<case>.params.npz (random and n
 tests/golden/calib/<case>.npz (make_qat_calib_golden.py).  Bars, the project's own: running min / max within 1e-4 of the span, zero
 points equal, scales within rtol 2e-4 -- over all six domains, the last domain's min included.  The three-frame loops settle that the
 scale is a constant of the traced graph: with live moving-average observers frames b and c would be merged at other scales."""
-import json
 import os
 
 import numpy as np
@@ -13,39 +12,16 @@ import pytest
 import torch
 
 import qat_calib_oracle as QO
-import test_calib_oracle as T
+from calib_cases import (ADD, BAR, LOOPS, MEASURED, ONE_FRAME, assert_record, dataset_frames, frame_of, load_test_py,
+                         scale_of)
 from conftest import GOLDEN, load_fixture
+from helpers import PIXEL_SHUFFLE
 from oracle import calib_oracle as CO
 
-ADD = json.load(open(os.path.join(GOLDEN, "calib", "qat_add.json")))
-ONE_FRAME = ("nrdm_3_qat", "sesr_x4_qat", "nrdm_3_qat_nat", "sesr_x4_qat_nat")
-LOOPS = {"nrdm_3_qat": "nrdm_3", "sesr_x4_qat": "sesr_x4"}           # record -> the plain case whose dataset frames a, b, c it ran on
-BAR, SCALE_RTOL = 1e-4, 2e-4
-
-# (record, domain) -> deviation of the fp32-faithful form from the reference's record, in units of the span, where it misses the
-# bar (measured; the test allows twice that and never more than 1e-3).  One cause, upstream of the QuantAdd -- the plain oracle has
-# it too -- and pinned in test_sesr_x4_qat_deviates_by_one_upstream_tie: 42 pixels of quantiser input 1 hold 0.13814925 (two adjacent floats), which sits
-# exactly on the rounding boundary between codes -86 and -85 with the oracle's scale_1; the reference's fp32 summation order put
-# domain 1's max 3 ulp lower, hence a smaller scale_1, and its copies of that value round the other way.  Domain 2's max moves by
-# five weight codes (1.21e-4 of its span), domain 3's by 6.9e-5 (inside the bar), domain 4 is exact (the QuantAdd's grid), and
-# domain 5 inherits 2.1e-4 (min) / 4.1e-4 (max).  nrdm_3_qat, both natural-frame records and both loops need none (at most 3e-7).
-MEASURED = {("sesr_x4_qat", 2): 1.210e-4, ("sesr_x4_qat", 5): 4.106e-4}
 # (record, domain) -> bar between the float64 and the fp32-faithful forms where float64 resolves a tie of the QuantAdd or of an
 # upstream quantiser the other way (as EXACT_SLACK of test_calib_oracle.py): measured 1.687e-4 and 3.203e-4 of the span, both in the
 # last domain's max; the fp32 form is the one that matches the record there (within 1.2e-7).
 EXACT_SLACK = {("nrdm_3_qat_nat", 5): 3.4e-4, ("loop nrdm_3_qat", 5): 6.5e-4}
-
-
-def bar_of(record, k):
-    m = MEASURED.get((record, k))
-    if m is None:
-        return BAR
-    assert BAR < 2 * m <= 1e-3
-    return 2 * m
-
-
-def scale_of(record):
-    return QO.skip_scale(*[ADD[record.replace("_nat", "")][k] for k in QO.OBSERVERS])
 
 
 _RUNS = {}
@@ -60,26 +36,10 @@ def run(record, frames_of=None, exact=False):
     else:
         _, rec = load_fixture(os.path.join(GOLDEN, "calib", f"{record}.npz"))
     if key not in _RUNS:
-        frames = [T.frame_of(pm)] if frames_of is None else T.dataset_frames(frames_of, pm["mflag"])
-        _RUNS[key] = QO.forward([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], T.PS[pm["mflag"]], frames, 8,
+        frames = [frame_of(pm)] if frames_of is None else dataset_frames(frames_of, pm["mflag"])
+        _RUNS[key] = QO.forward([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], PIXEL_SHUFFLE[pm["mflag"]], frames, 8,
                                 scale_of(record), exact=exact, keep_outputs=False, keep_inputs=frames_of is None and not exact)
     return _RUNS[key], rec
-
-
-def assert_record(record, r, rec):
-    """Running min and max of all six domains, the zero points and the scales of a record."""
-    scale, zero = T.finalize(r, 8)
-    for k in range(6):
-        span, bar = rec["max"][k] - rec["min"][k], bar_of(record, k)
-        dmin, dmax = abs(r.run_min[k] - rec["min"][k]) / span, abs(r.run_max[k] - rec["max"][k]) / span
-        print(f"{record} domain {k}: min off {dmin:.3e}, max off {dmax:.3e} of the span (bar {bar:.1e}); zero {zero[k]} / "
-              f"{rec['zero'][k]}; scale off {abs(scale[k] / rec['scale'][k] - 1):.3e}")
-        assert dmin <= bar and dmax <= bar, (record, k, r.run_min[k], rec["min"][k], r.run_max[k], rec["max"][k])
-        # scale_k = (max_k - min_k) / 255 (min_5 := 0): an excepted domain's scale moves by what its ends may move
-        used = rec["max"][k] - (0.0 if k == 5 else rec["min"][k])
-        rtol = SCALE_RTOL if bar == BAR else max(SCALE_RTOL, (1 if k == 5 else 2) * bar * span / used)
-        assert abs(scale[k] - rec["scale"][k]) <= rtol * abs(rec["scale"][k]), (record, k, scale[k], rec["scale"][k])
-    assert zero == rec["zero"], (record, zero, rec["zero"])       # no zero point differs: no tie to account for
 
 
 @pytest.mark.parametrize("record", ONE_FRAME)
@@ -117,8 +77,8 @@ def test_the_plain_pass_misses_what_the_quantised_merge_reproduces():
     for record, frames_of in LOOPS.items():
         r, rec = run(record, frames_of)
         p, pm = load_fixture(os.path.join(GOLDEN, f"{record}.params.npz"))
-        plain = CO.forward([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], T.PS[pm["mflag"]],
-                           T.dataset_frames(frames_of, pm["mflag"]), 8, keep_outputs=False)
+        plain = CO.forward([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], PIXEL_SHUFFLE[pm["mflag"]],
+                           dataset_frames(frames_of, pm["mflag"]), 8, keep_outputs=False)
         assert plain.run_max[:4] == r.run_max[:4] and plain.run_min[:4] == r.run_min[:4]
         assert any(abs(plain.run_max[k] - rec["max"][k]) > 1e-3 * (rec["max"][k] - rec["min"][k]) for k in (4, 5)), record
 
@@ -135,7 +95,7 @@ def test_sesr_x4_qat_deviates_by_one_upstream_tie():
     ulp = float(np.spacing(np.float32(rec["max"][1])))
     assert r.run_max[0] == rec["max"][0] and 0 < r.run_max[1] - rec["max"][1] <= 3 * ulp
     p, pm = load_fixture(os.path.join(GOLDEN, "sesr_x4_qat.params.npz"))
-    plain = CO.forward([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], 4, [T.frame_of(pm)], 8, keep_outputs=False)
+    plain = CO.forward([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], 4, [frame_of(pm)], 8, keep_outputs=False)
     assert plain.run_max[:4] == r.run_max[:4] and plain.run_min[:4] == r.run_min[:4]
     span = rec["max"][2] - rec["min"][2]
     assert abs(abs(r.run_max[2] - rec["max"][2]) / span - MEASURED[("sesr_x4_qat", 2)]) < 1e-6
@@ -153,22 +113,6 @@ def test_skip_fakequant_rounds_half_away_and_clamps():
 
 
 # ------------------------------------------------------------------------------------------------------------- the loader helper
-def _qat_state_dict(mflag, add):
-    """tests/test_host_mirror.py::_qat_state_dict's layout (conv weights + the buffers of both quantisers of every conv) plus the
-    add_residual.* entries of a reference *_qat_G.pth."""
-    import sim
-    from models import quantize_utils_pt as quantize
-    torch.manual_seed(4)
-    sd = dict(quantize.prepare(sim.MODELS[mflag](), a_bits=8, w_bits=8, q_type=0, q_level="C").state_dict())
-    for k in QO.OBSERVERS:
-        sd["add_residual." + k] = torch.tensor([add[k]], dtype=torch.float32)
-    sd["add_residual.activation_quantizer.scale"] = torch.tensor([add["stored_scale"]], dtype=torch.float32)
-    sd["add_residual.activation_quantizer.observer.max_val"] = torch.tensor([add["observer_res.max_val"]], dtype=torch.float32)
-    sd["add_upsampled_input.activation_quantizer.scale"] = torch.ones(1)
-    sd["add_upsampled_input.observer_res.min_val"] = torch.zeros(1)
-    return sd
-
-
 @pytest.mark.parametrize("record,mflag", [("nrdm_3_qat", 3), ("sesr_x4_qat", 5)])
 def test_loader_helper_gives_the_traced_scale(record, mflag, tmp_path):
     """quantize.skip_quant_scale on a synthetic QAT state_dict with the checkpoint's observer extrema: the scale the reference's traced
@@ -176,7 +120,7 @@ def test_loader_helper_gives_the_traced_scale(record, mflag, tmp_path):
     import sim
     from models import quantize_utils_pt as quantize
     add = ADD[record]
-    sd = _qat_state_dict(mflag, add)
+    sd = QO.qat_state_dict(mflag, add)
     s = quantize.skip_quant_scale(sd)
     assert isinstance(s, float) and np.float32(s) == np.float32(add["traced_scale"]) == scale_of(record)
     assert np.float32(s) != np.float32(add["stored_scale"])
@@ -199,7 +143,7 @@ def quantize_target(mflag):
 def test_loader_helper_refusals_and_edges():
     from models import quantize_utils_pt as quantize
     import sim
-    sd = _qat_state_dict(3, ADD["nrdm_3_qat"])
+    sd = QO.qat_state_dict(3, ADD["nrdm_3_qat"])
     assert quantize.skip_quant_scale(sim.MODELS[3]().state_dict()) is None              # not a QAT checkpoint
     assert quantize.skip_quant_scale({k: v for k, v in sd.items() if not k.startswith("add_residual.")}) is None
     for k in QO.OBSERVERS:                                                               # some of the four, not all
@@ -218,8 +162,7 @@ def test_incomplete_state_stops_calibration_not_the_integer_path(tmp_path):
     """A QAT checkpoint with some of the four observer extrema: sim.float_model (the integer path never evaluates the QuantAdd) loads
     it as before; test.py refuses it, before any device work, unless told how to add the skip."""
     import sim
-    from test_calib_dataset import load_test_py
-    sd = _qat_state_dict(3, ADD["nrdm_3_qat"])
+    sd = QO.qat_state_dict(3, ADD["nrdm_3_qat"])
     del sd["add_residual.observer_shortcut.max_val"]
     p = str(tmp_path / "partial_qat_G.pth")
     torch.save(sd, p)

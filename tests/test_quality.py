@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, load_fixture, fixture_input
+from helpers import device
 import quality_oracle as Q
 
 CSRC = os.path.join(ROOT, "sesr-pytorch-quantize_amd", "csrc")
@@ -151,15 +152,10 @@ def test_score_refuses_bad_arguments_on_the_host():
 
 
 # ------------------------------------------------------------------------------------------------------------------------ GPU
-def _dev():
-    import torch
-    return torch.device("cuda:0")
-
-
 def _score(pred, gt, mflag, **kw):
     import torch
     from sesrq import quality
-    res = quality.score(torch.as_tensor(pred).to(_dev()), torch.as_tensor(gt).to(_dev()), mflag, **kw)
+    res = quality.score(torch.as_tensor(pred).to(device()), torch.as_tensor(gt).to(device()), mflag, **kw)
     torch.cuda.synchronize()
     return res.cpu().numpy()
 
@@ -210,12 +206,12 @@ def test_int8_prediction_scores_as_its_float_output():
         path = os.path.join(GOLDEN, case + ".npz")
         fx, meta = load_fixture(path)
         b = Bundle.load(path)
-        e = sesrq.Engine(b, _dev())
-        x = torch.from_numpy(fixture_input(fx, meta)).to(_dev())
+        e = sesrq.Engine(b, device())
+        x = torch.from_numpy(fixture_input(fx, meta)).to(device())
         q, y = e.forward(x)
         np.testing.assert_array_equal(y.cpu().numpy(), fx["out"])          # the reference's output, for the record
         rng = np.random.default_rng(7)
-        gt = torch.from_numpy((fx["out"] + rng.normal(0, 0.03, fx["out"].shape)).astype(np.float32)).to(_dev())
+        gt = torch.from_numpy((fx["out"] + rng.normal(0, 0.03, fx["out"].shape)).astype(np.float32)).to(device())
         L = b.L
         sq = quality.score(q, gt, mflag, scale=b.scale[L], zero=b.zero[L])
         sf = quality.score(y, gt, mflag)
@@ -231,8 +227,8 @@ def test_bitwise_reproducible():
     from sesrq import quality
     z, _ = quality_fixture()
     for name, mflag in (("x2_67x101", 6), ("y255_67x101", 5), ("rgb_7x7", 3)):
-        p3 = torch.from_numpy(np.concatenate([z[name + ".pred"]] * 2)[:3]).to(_dev())
-        g3 = torch.from_numpy(np.concatenate([z[name + ".gt"]] * 2)[:3]).to(_dev())
+        p3 = torch.from_numpy(np.concatenate([z[name + ".pred"]] * 2)[:3]).to(device())
+        g3 = torch.from_numpy(np.concatenate([z[name + ".gt"]] * 2)[:3]).to(device())
         runs = [quality.score(p3, g3, mflag) for _ in range(3)]
         side = torch.cuda.Stream()
         runs.append(quality.score(p3, g3, mflag, stream=side))
@@ -262,7 +258,7 @@ def test_4k_frames_against_the_oracle(mflag, C):
 def _engine(case, **kw):
     import sesrq
     from sesrq.bundle import Bundle
-    return sesrq.Engine(Bundle.load(os.path.join(GOLDEN, case + ".npz")), _dev(), **kw)
+    return sesrq.Engine(Bundle.load(os.path.join(GOLDEN, case + ".npz")), device(), **kw)
 
 
 @pytest.mark.gpu
@@ -276,8 +272,8 @@ def test_evaluate_matches_score_of_a_separate_forward():
     gts = [torch.from_numpy(rng.uniform(0, 1, (1, 1, 96, 160)).astype(np.float32)) for _ in range(3)]
     got = quality.evaluate(e, xs, gts, 5)
     for k in range(3):
-        _, y = e.forward(xs[k].to(_dev()), want_q=False)
-        want = quality.score(y, gts[k].to(_dev()), 5)
+        _, y = e.forward(xs[k].to(device()), want_q=False)
+        want = quality.score(y, gts[k].to(device()), 5)
         torch.cuda.synchronize()
         assert np.array_equal(got[k], want[0].cpu().numpy()), k
     # MFLAG 6: the anchored float output, and only on an anchored engine
@@ -287,10 +283,10 @@ def test_evaluate_matches_score_of_a_separate_forward():
     got = quality.evaluate(ea, xs, gts, 6)
     plain = _engine("sesr_x2_rand.crop")
     for k in range(2):
-        x = xs[k].to(_dev())
+        x = xs[k].to(device())
         _, y = plain.forward(x, want_q=False)
         y = y + x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)         # reference test.py:149-155
-        want = quality.score(y, gts[k].to(_dev()), 6)
+        want = quality.score(y, gts[k].to(device()), 6)
         torch.cuda.synchronize()
         assert np.array_equal(got[k], want[0].cpu().numpy()), k
     with pytest.raises(ValueError, match="anchor"):

@@ -13,23 +13,15 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, load_fixture
+from helpers import PIXEL_SHUFFLE, calib_params, device, full_input, same, sha256
 
 QB = os.path.join(GOLDEN, "quan_bits")
 CROPS = sorted(glob.glob(os.path.join(QB, "*.crop.npz")))
 STAGE_FILES = CROPS + sorted(glob.glob(os.path.join(QB, "*.zeros.npz")))
-PS = {5: 4, 6: 2, 3: 1}
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 def _id(p):
     return os.path.basename(p)[:-4]
-
-
-def full_input(meta):
-    return np.load(os.path.join(GOLDEN, "rand_SR_Input_80x960.npy" if meta["mflag"] == 5 else "rand_DM_Input_80x960.npy"))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- CPU
@@ -84,7 +76,7 @@ def test_derive_bundle_reproduces_the_reference(path):
     b = meta["quan_bits"]
     p, pm = load_fixture(path.replace(".crop.npz", ".params.npz"))
     assert pm["quan_bits"] == b and pm["zero"] == meta["zero"]
-    bun = derive_bundle([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], pm["scale"], pm["zero"], PS[meta["mflag"]],
+    bun = derive_bundle([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], pm["scale"], pm["zero"], PIXEL_SHUFFLE[meta["mflag"]],
                         quan_bit=b)
     assert bun.quan_bits == b and bun.zero == meta["zero"]
     assert (bun.M_res, bun.n_res) == (meta["M_res"], meta["n_res"])
@@ -94,7 +86,7 @@ def test_derive_bundle_reproduces_the_reference(path):
         assert (l.M, l.n) == (meta["M"][k], meta["n"][k]), k
         np.testing.assert_array_equal(l.add_const, fx[f"add_const{k}"])
     # an 8-bit derivation of the same convs is a different net: the width is live
-    b8 = derive_bundle([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], pm["scale"], pm["zero"], PS[meta["mflag"]])
+    b8 = derive_bundle([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], pm["scale"], pm["zero"], PIXEL_SHUFFLE[meta["mflag"]])
     assert b8.quan_bits == 8 and not np.array_equal(b8.layers[0].wq, bun.layers[0].wq)
 
 
@@ -158,10 +150,10 @@ def test_c_oracle_reproduces_the_crop_and_the_full_frame_at_the_width(path):
     np.testing.assert_array_equal(r["y"], fx["out"])
     if meta["tag"] == "crop":
         x = full_input(meta)
-        assert sha(x) == meta["full"]["x_sha256"]
+        assert sha256(x) == meta["full"]["x_sha256"]
         f = CO.forward(net, x, threads=8)
         assert list(f["y"].shape) == meta["full"]["shape"]
-        assert sha(f["q_out"]) == meta["full"]["q_out"] and sha(f["y"]) == meta["full"]["y"]
+        assert sha256(f["q_out"]) == meta["full"]["q_out"] and sha256(f["y"]) == meta["full"]["y"]
 
 
 @pytest.mark.parametrize("path", CROPS, ids=_id)
@@ -174,7 +166,7 @@ def test_oracle_derivation_at_the_width(path):
     p, pm = load_fixture(path.replace(".crop.npz", ".params.npz"))
     sz = [O.calib_scale_zero(0.0 if i == 5 else pm["min"][i], pm["max"][i], b) for i in range(6)]
     assert [s_ for s_, _ in sz] == pm["scale"] == meta["scale"] and [z for _, z in sz] == pm["zero"] == meta["zero"]
-    net = O.derive_net([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], pm["scale"], pm["zero"], PS[meta["mflag"]],
+    net = O.derive_net([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], pm["scale"], pm["zero"], PIXEL_SHUFFLE[meta["mflag"]],
                        quan_bit=b)
     assert net.quan_bits == b
     for k in range(5):
@@ -230,25 +222,10 @@ def test_c_oracle_equals_numpy_oracle_at_every_width():
 
 # ---------------------------------------------------------------------------------------------------------------------------- GPU
 
-def _dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
-
-
 def _engine(path, **kw):
     import sesrq
     from sesrq.bundle import Bundle
-    return sesrq.Engine(Bundle.load(path), _dev(), **kw)
-
-
-def _eq(name, got, want):
-    got = got.cpu().numpy() if hasattr(got, "cpu") else np.asarray(got)
-    want = np.asarray(want)
-    assert got.size == want.size, (name, got.shape, want.shape)
-    got = got.reshape(want.shape)
-    bad = np.flatnonzero(got.astype(np.float64).ravel() != want.astype(np.float64).ravel())
-    assert bad.size == 0, f"{name}: {bad.size} mismatches, first at {bad[0]}: got {got.ravel()[bad[0]]} want {want.ravel()[bad[0]]}"
+    return sesrq.Engine(Bundle.load(path), device(), **kw)
 
 
 @pytest.mark.gpu
@@ -260,22 +237,22 @@ def test_every_stage_matches_the_reference(path, force_general):
     e = _engine(path, force_general=force_general)
     b = meta["quan_bits"]
     assert e.quan_bits == b
-    r = e.forward_debug(torch.from_numpy(fx["x"]).to(_dev()), pe=True, acts=True, special=True)
+    r = e.forward_debug(torch.from_numpy(fx["x"]).to(device()), pe=True, acts=True, special=True)
     torch.cuda.synchronize()
     for k in range(5):
-        _eq(f"input{k}", r[f"input{k}"], fx[f"input{k}"])
-        _eq(f"pe_out{k}", r[f"pe_out{k}"], fx[f"pe_out{k}"])
-        _eq(f"pe_add{k}", r[f"pe_add{k}"], fx[f"pe_add{k}"])
-    _eq("shortcut", r["shortcut"], fx["shortcut"])
-    _eq("input4_special", r["input4_special"], fx["input4_special"])
-    _eq("q_out", r["q_out"], fx["q_out"])
-    _eq("y", r["y"], fx["out"])
+        same(f"input{k}", r[f"input{k}"], fx[f"input{k}"])
+        same(f"pe_out{k}", r[f"pe_out{k}"], fx[f"pe_out{k}"], reshape=True)      # stored without the batch axis
+        same(f"pe_add{k}", r[f"pe_add{k}"], fx[f"pe_add{k}"])
+    same("shortcut", r["shortcut"], fx["shortcut"])
+    same("input4_special", r["input4_special"], fx["input4_special"])
+    same("q_out", r["q_out"], fx["q_out"])
+    same("y", r["y"], fx["out"])
     q = r["q_out"].cpu().numpy()
     assert q.min() >= -(1 << (b - 1)) and q.max() <= (1 << (b - 1)) - 1
     # the production forward (no taps) gives the same bits
-    q2, y2 = e.forward(torch.from_numpy(fx["x"]).to(_dev()))
-    _eq("q_out (forward)", q2, fx["q_out"])
-    _eq("y (forward)", y2, fx["out"])
+    q2, y2 = e.forward(torch.from_numpy(fx["x"]).to(device()))
+    same("q_out (forward)", q2, fx["q_out"])
+    same("y (forward)", y2, fx["out"])
 
 
 @pytest.mark.gpu
@@ -295,13 +272,13 @@ def test_both_residual_layouts_are_covered():
 def test_full_frame_hashes_to_the_reference(path):
     import torch
     fx, meta = load_fixture(path)
-    x = torch.from_numpy(full_input(meta)).to(_dev())
-    assert sha(full_input(meta)) == meta["full"]["x_sha256"]
+    x = torch.from_numpy(full_input(meta)).to(device())
+    assert sha256(full_input(meta)) == meta["full"]["x_sha256"]
     q, y = _engine(path)(x)
     torch.cuda.synchronize()
     assert list(y.shape) == meta["full"]["shape"]
-    assert sha(q.cpu().numpy()) == meta["full"]["q_out"]
-    assert sha(y.cpu().numpy()) == meta["full"]["y"]
+    assert sha256(q.cpu().numpy()) == meta["full"]["q_out"]
+    assert sha256(y.cpu().numpy()) == meta["full"]["y"]
 
 
 @pytest.mark.gpu
@@ -313,17 +290,17 @@ def test_frame_shapes_and_batches_agree_with_single_frames(path):
     x = fx["x"]
     for fg in (False, True):
         e = _engine(path, force_general=fg)
-        q, y = e(torch.from_numpy(np.ascontiguousarray(x[:, :, 5:6, 7:8])).to(_dev()))      # a 1 x 1 frame
-        r = PS[meta["mflag"]]
+        q, y = e(torch.from_numpy(np.ascontiguousarray(x[:, :, 5:6, 7:8])).to(device()))      # a 1 x 1 frame
+        r = PIXEL_SHUFFLE[meta["mflag"]]
         assert tuple(q.shape) == tuple(e.out_shape(1, 1, 1)) and tuple(q.shape[2:]) == (r, r)
         b = meta["quan_bits"]
         assert int(q.min()) >= -(1 << (b - 1)) and int(q.max()) <= (1 << (b - 1)) - 1
         crops = [np.ascontiguousarray(x[:, :, 2:11, 3:36]), np.ascontiguousarray(x[:, :, 13:22, 6:39])]
-        qb, yb = e(torch.from_numpy(np.concatenate(crops)).to(_dev()))
+        qb, yb = e(torch.from_numpy(np.concatenate(crops)).to(device()))
         for i, c in enumerate(crops):
-            q1, y1 = e(torch.from_numpy(c).to(_dev()))
-            _eq(f"q frame {i}", qb[i:i + 1], q1.cpu().numpy())
-            _eq(f"y frame {i}", yb[i:i + 1], y1.cpu().numpy())
+            q1, y1 = e(torch.from_numpy(c).to(device()))
+            same(f"q frame {i}", qb[i:i + 1], q1.cpu().numpy())
+            same(f"y frame {i}", yb[i:i + 1], y1.cpu().numpy())
         torch.cuda.synchronize()
 
 
@@ -336,17 +313,17 @@ def test_int8_q0_input_equals_the_fp32_route(path):
     fx, meta = load_fixture(path)
     b = meta["quan_bits"]
     e = _engine(path)
-    q0 = torch.from_numpy(fx["input0"]).to(_dev())
+    q0 = torch.from_numpy(fx["input0"]).to(device())
     q, y = e(q0)
-    _eq("q from q0", q, fx["q_out"])
-    _eq("y from q0", y, fx["out"])
+    same("q from q0", q, fx["q_out"])
+    same("y from q0", y, fx["out"])
     # out-of-range codes: the same bits as the clipped q0
     rng = np.random.default_rng(b)
     wild = rng.integers(-128, 128, size=fx["input0"].shape).astype(np.int8)
-    qa, ya = e(torch.from_numpy(wild).to(_dev()))
-    qc, yc = e(torch.from_numpy(np.clip(wild, -(1 << (b - 1)), (1 << (b - 1)) - 1).astype(np.int8)).to(_dev()))
-    _eq("wild q", qa, qc.cpu().numpy())
-    _eq("wild y", ya, yc.cpu().numpy())
+    qa, ya = e(torch.from_numpy(wild).to(device()))
+    qc, yc = e(torch.from_numpy(np.clip(wild, -(1 << (b - 1)), (1 << (b - 1)) - 1).astype(np.int8)).to(device()))
+    same("wild q", qa, qc.cpu().numpy())
+    same("wild y", ya, yc.cpu().numpy())
 
 
 @pytest.mark.gpu
@@ -364,8 +341,8 @@ def test_engine_names_carry_the_width_and_every_engine_option_lands_on_dot4():
             assert _lib.lib().sesrq_net_quan_bits(e._h) == b
     # grouping (several frames as one launch sequence) needs the MFMA kernels: refused
     e = _engine(os.path.join(QB, "sesr_x4.q4.crop.npz"))
-    fr = [torch.zeros((1, 1, 8, 8), device=_dev()) for _ in range(2)]
-    outs = [torch.empty(e.out_shape(1, 8, 8), dtype=torch.int8, device=_dev()) for _ in range(2)]
+    fr = [torch.zeros((1, 1, 8, 8), device=device()) for _ in range(2)]
+    outs = [torch.empty(e.out_shape(1, 8, 8), dtype=torch.int8, device=device()) for _ in range(2)]
     with pytest.raises(RuntimeError, match="MFMA first- and last-layer"):
         e.submission(fr, outs, [torch.cuda.current_stream()], group=2).enqueue(2)
         torch.cuda.synchronize()
@@ -378,14 +355,14 @@ def test_create_refuses_what_the_width_cannot_hold():
     b = Bundle.load(os.path.join(QB, "sesr_x4.q4.crop.npz"))
     for qb in (1, 9):
         with pytest.raises(ValueError, match="quan_bits"):
-            sesrq.Engine(dataclasses.replace(b, quan_bits=qb), _dev())
+            sesrq.Engine(dataclasses.replace(b, quan_bits=qb), device())
     wide = dataclasses.replace(b, quan_bits=4, layers=[dataclasses.replace(b.layers[0], wq=b.layers[0].wq * 2)] + b.layers[1:])
     with pytest.raises(ValueError, match="4-bit range"):
-        sesrq.Engine(wide, _dev())
+        sesrq.Engine(wide, device())
     with pytest.raises(ValueError, match="zero point"):
-        sesrq.Engine(dataclasses.replace(b, zero=b.zero[:3] + [8] + b.zero[4:]), _dev())
+        sesrq.Engine(dataclasses.replace(b, zero=b.zero[:3] + [8] + b.zero[4:]), device())
     with pytest.raises(ValueError, match="upstream"):
-        sesrq.Engine(b, _dev(), upstream=Bundle.load(os.path.join(GOLDEN, "sesr_x4.crop.npz")))
+        sesrq.Engine(b, device(), upstream=Bundle.load(os.path.join(GOLDEN, "sesr_x4.crop.npz")))
 
 
 @pytest.mark.gpu
@@ -396,13 +373,13 @@ def test_an_8bit_engine_of_the_same_weights_differs():
     path = os.path.join(QB, "sesr_x4.q4.crop.npz")
     fx, _ = load_fixture(path)
     b = Bundle.load(path)
-    x = torch.from_numpy(fx["x"]).to(_dev())
-    q4, _ = sesrq.Engine(b, _dev())(x)
-    e8 = sesrq.Engine(dataclasses.replace(b, quan_bits=8), _dev())
+    x = torch.from_numpy(fx["x"]).to(device())
+    q4, _ = sesrq.Engine(b, device())(x)
+    e8 = sesrq.Engine(dataclasses.replace(b, quan_bits=8), device())
     q8, _ = e8(x)
     assert not any(n.endswith("-q8") for n in e8.layer_engines())
     assert not torch.equal(q4, q8)
-    _eq("q4", q4, fx["q_out"])
+    same("q4", q4, fx["q_out"])
 
 
 @pytest.mark.gpu
@@ -418,13 +395,13 @@ def test_calibrator_matches_the_reference_ranges_at_the_width(path):
     fx, meta = load_fixture(path)
     b = meta["quan_bits"]
     p, pm = load_fixture(path.replace(".crop.npz", ".params.npz"))
-    Wf, bf = [p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)]
-    cal = Calibrator(Wf, bf, PS[pm["mflag"]], _dev(), quan_bits=b)
-    cal.observe(torch.from_numpy(full_input(meta)).to(_dev()))
+    Wf, bf, ps = calib_params(path.replace(".crop.npz", ".params.npz"))
+    cal = Calibrator(Wf, bf, ps, device(), quan_bits=b)
+    cal.observe(torch.from_numpy(full_input(meta)).to(device()))
     want_min, want_max = list(pm["min"]), list(pm["max"])
     tie = os.path.basename(path) == "sesr_x4.q3.crop.npz"
     if tie:
-        orc = CO.forward(Wf, bf, PS[pm["mflag"]], [full_input(meta)], b, keep_outputs=False)
+        orc = CO.forward(Wf, bf, ps, [full_input(meta)], b, keep_outputs=False)
         for k in (4, 5):
             assert cal.run_min[k] == orc.run_min[k] and cal.run_max[k] == orc.run_max[k], k
             want_min[k], want_max[k] = orc.run_min[k], orc.run_max[k]
@@ -449,9 +426,8 @@ def test_calibrator_matches_the_reference_ranges_at_the_width(path):
     for k in range(5):
         np.testing.assert_array_equal(bun.layers[k].wq, fx[f"Wq{k}"])
     # the entropy variant runs at the width (2^b levels; parity unpinned)
-    cal2 = Calibrator([p[f"Wf{k}"] for k in range(5)], [p[f"bf{k}"] for k in range(5)], PS[pm["mflag"]], _dev(), quan_bits=b,
-                      method="entropy")
-    xt = torch.from_numpy(full_input(meta)).to(_dev())
+    cal2 = Calibrator(Wf, bf, ps, device(), quan_bits=b, method="entropy")
+    xt = torch.from_numpy(full_input(meta)).to(device())
     cal2.observe(xt)
     cal2.begin_histogram_pass()
     cal2.observe(xt)
@@ -491,15 +467,15 @@ def test_sim_py_at_the_width_hashes_to_the_reference(case, monkeypatch, capsys):
     torch.cuda.synchronize()
     out = capsys.readouterr().out
     assert f"QUAN_BIT: {b}" in out and f"-q{b}" in out
-    assert sha(y.cpu().numpy()) == meta["full"]["y"]
+    assert sha256(y.cpu().numpy()) == meta["full"]["y"]
     # the int8 frame behind it: the spliced model's engine, same input
     model = sim.splice(sim.float_model(meta["mflag"], None, os.path.join(QB, f"{case}.params.npz")))
     x = torch.from_numpy(np.load(inp)).cuda()
-    assert sha(model(x).cpu().numpy()) == meta["full"]["y"]
+    assert sha256(model(x).cpu().numpy()) == meta["full"]["y"]
     eng = model._sesrq_engine(x.device)
     assert eng.quan_bits == b
     q, _ = eng(x)
-    assert sha(q.cpu().numpy()) == meta["full"]["q_out"]
+    assert sha256(q.cpu().numpy()) == meta["full"]["q_out"]
 
 
 @pytest.mark.gpu
@@ -508,13 +484,13 @@ def test_forward_image_equals_forward_on_the_decoded_frame(case, form):
     import torch
     from sesrq import image
     e = _engine(os.path.join(QB, f"{case}.crop.npz"))
-    img = torch.from_numpy(np.random.default_rng(5).integers(0, 256, size=(2, 17, 29, 3), dtype=np.uint8)).to(_dev())
+    img = torch.from_numpy(np.random.default_rng(5).integers(0, 256, size=(2, 17, 29, 3), dtype=np.uint8)).to(device())
     q, y = e.forward_image(img, form=form)
     _, x = image.decode(None, img, form, want_q=False, want_f=True)
     q2, y2 = e(x)
     torch.cuda.synchronize()
-    _eq("q", q, q2.cpu().numpy())
-    _eq("y", y, y2.cpu().numpy())
+    same("q", q, q2.cpu().numpy())
+    same("y", y, y2.cpu().numpy())
 
 
 @pytest.mark.gpu
@@ -522,13 +498,13 @@ def test_forward_raw_equals_forward_on_the_unpacked_frame():
     import torch
     from sesrq import raw
     e = _engine(os.path.join(QB, "nrdm_3.q4.crop.npz"))
-    fr = torch.from_numpy(np.random.default_rng(6).integers(0, 4096, size=(2, 18, 30)).astype(np.uint16)).to(_dev())
+    fr = torch.from_numpy(np.random.default_rng(6).integers(0, 4096, size=(2, 18, 30)).astype(np.uint16)).to(device())
     q, y = e.forward_raw(fr)
     _, x = raw.unpack(None, fr, want_q=False, want_spread=True)
     q2, y2 = e(x)
     torch.cuda.synchronize()
-    _eq("q", q, q2.cpu().numpy())
-    _eq("y", y, y2.cpu().numpy())
+    same("q", q, q2.cpu().numpy())
+    same("y", y, y2.cpu().numpy())
 
 
 @pytest.mark.gpu
@@ -538,9 +514,9 @@ def test_quality_score_of_the_int8_output_equals_scoring_y():
     path = os.path.join(QB, "sesr_x4.q4.crop.npz")
     fx, meta = load_fixture(path)
     e = _engine(path)
-    q, y = e(torch.from_numpy(fx["x"]).to(_dev()))
-    gt = torch.from_numpy(np.random.default_rng(7).random(tuple(y.shape), dtype=np.float32)).to(_dev())
+    q, y = e(torch.from_numpy(fx["x"]).to(device()))
+    gt = torch.from_numpy(np.random.default_rng(7).random(tuple(y.shape), dtype=np.float32)).to(device())
     a = quality.score(q, gt, 5, scale=float(np.float32(meta["scale"][5])), zero=meta["zero"][5])
     b = quality.score(y, gt, 5)
     torch.cuda.synchronize()
-    _eq("scores", a, b.cpu().numpy())
+    same("scores", a, b, values=True)

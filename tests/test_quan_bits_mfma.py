@@ -10,13 +10,13 @@ not max(zero, -2^(b-1)): the hard synthetic nets (zero points down to -170) pin 
 """
 import dataclasses
 import glob
-import hashlib
 import os
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_fixture
+from helpers import device, full_input, same, sha256, to_device
 
 QB = os.path.join(GOLDEN, "quan_bits")
 CROPS = sorted(glob.glob(os.path.join(QB, "*.crop.npz")))
@@ -26,25 +26,6 @@ HIT = set()          # narrow instantiations launched inside a checked case
 
 def _id(p):
     return os.path.basename(p)[:-4]
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
-
-
-def full_input(meta):
-    return np.load(os.path.join(GOLDEN, "rand_SR_Input_80x960.npy" if meta["mflag"] == 5 else "rand_DM_Input_80x960.npy"))
-
-
-def _dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
-
-
-def _t(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
 
 
 class Checked:
@@ -64,20 +45,11 @@ class Checked:
         return False
 
 
-def _eq(name, got, want):
-    got = got.cpu().numpy() if hasattr(got, "cpu") else np.asarray(got)
-    want = want.cpu().numpy() if hasattr(want, "cpu") else np.asarray(want)
-    assert got.size == want.size, (name, got.shape, want.shape)
-    got = got.reshape(want.shape)
-    bad = np.flatnonzero(got.astype(np.float64).ravel() != want.astype(np.float64).ravel())
-    assert bad.size == 0, f"{name}: {bad.size} mismatches, first at {bad[0]}: got {got.ravel()[bad[0]]} want {want.ravel()[bad[0]]}"
-
-
 def _engine(bundle, **kw):
     import sesrq
     from sesrq import _lib
     kw.setdefault("engine", _lib.ENGINE_MFMA_Q)
-    return sesrq.Engine(bundle, _dev(), **kw)
+    return sesrq.Engine(bundle, device(), **kw)
 
 
 def _bundle(path):
@@ -121,15 +93,15 @@ def test_reference_fixtures_on_the_narrow_engine(path, fuse):
     if fuse:
         assert e.layer_engines()[1:4] == [f"mfma-trio-merged-q{b}"] * 3
     with Checked():
-        q, y = e.forward(_t(fx["x"]))
-        _eq("q_out", q, fx["q_out"])
-        _eq("y", y, fx["out"])
+        q, y = e.forward(to_device(fx["x"]))
+        same("q_out", q, fx["q_out"])
+        same("y", y, fx["out"])
         if meta["tag"] == "crop":          # the reference's 80 x 960 frame
             x = full_input(meta)
-            assert sha(x) == meta["full"]["x_sha256"]
-            q, y = e.forward(_t(x))
+            assert sha256(x) == meta["full"]["x_sha256"]
+            q, y = e.forward(to_device(x))
             assert list(y.shape) == meta["full"]["shape"]
-            assert sha(q.cpu().numpy()) == meta["full"]["q_out"] and sha(y.cpu().numpy()) == meta["full"]["y"]
+            assert sha256(q.cpu().numpy()) == meta["full"]["q_out"] and sha256(y.cpu().numpy()) == meta["full"]["y"]
 
 
 # ------------------------------------------------------------------------------------------------------------- 2. against the dot4 engine
@@ -155,19 +127,19 @@ def test_every_accepted_option_gives_the_dot4_bits(case):
         kw = dict(kw)
         pe = kw.pop("pe", None)
         bb = dataclasses.replace(bun, pe_acc_bits=pe[0], pe_add_bits=pe[1]) if pe else bun
-        d4 = sesrq.Engine(bb, _dev(), engine=_lib.ENGINE_DOT4, **kw)
+        d4 = sesrq.Engine(bb, device(), engine=_lib.ENGINE_DOT4, **kw)
         mq = _engine(bb, **kw)
         assert all(n.endswith(f"-q{b}") for n in mq.layer_engines()) and any(n.startswith("mfma-") for n in mq.layer_engines())
-        inputs = [("f32", _t(x))] + ([] if kw.get("anchor_add") else [("i8 beyond the width", _t(wild))])
+        inputs = [("f32", to_device(x))] + ([] if kw.get("anchor_add") else [("i8 beyond the width", to_device(wild))])
         with Checked():
             for lbl, xt in inputs:
                 for wq, wf in ((True, False), (False, True), (True, True)):
                     q0, y0 = d4.forward(xt, want_q=wq, want_f=wf)
                     q1, y1 = mq.forward(xt, want_q=wq, want_f=wf)
                     if wq:
-                        _eq(f"{case} {kw} pe={pe} [{lbl}] q", q1, q0)
+                        same(f"{case} {kw} pe={pe} [{lbl}] q", q1, q0)
                     if wf:
-                        _eq(f"{case} {kw} pe={pe} [{lbl}] y", y1, y0)
+                        same(f"{case} {kw} pe={pe} [{lbl}] y", y1, y0)
 
 
 # ------------------------------------------------------------------------------------------------------------- 3. the walk, against the oracles
@@ -196,13 +168,13 @@ def test_strip_and_step_borders_against_the_oracle(kind, b, hard):
         want = CO.forward(net, x, threads=4)
         if H * W < 500:          # the C oracle itself against the numpy oracle, where that is cheap
             ref = O.forward(net, x)
-            _eq("c_oracle q", want["q_out"], ref["q_out"])
-            _eq("c_oracle y", want["y"], ref["y"])
+            same("c_oracle q", want["q_out"], ref["q_out"])
+            same("c_oracle y", want["y"], ref["y"])
         with Checked():
             for w, e in zip((0, 1), engines):
-                q, y = e.forward(_t(x))
-                _eq(f"{kind} b={b} hard={hard} {N}x{H}x{W} budget {w} q", q, want["q_out"])
-                _eq(f"{kind} b={b} hard={hard} {N}x{H}x{W} budget {w} y", y, want["y"])
+                q, y = e.forward(to_device(x))
+                same(f"{kind} b={b} hard={hard} {N}x{H}x{W} budget {w} q", q, want["q_out"])
+                same(f"{kind} b={b} hard={hard} {N}x{H}x{W} budget {w} y", y, want["y"])
                 assert int(q.min()) >= net.qlo and int(q.max()) <= net.qhi
 
 
@@ -251,21 +223,21 @@ def test_first_hidden_and_last_layer_flavours_against_the_oracle():
             e = _engine(bun, **kw)
             assert all(n.startswith("mfma-") for n in e.layer_engines()), (tag, e.layer_engines())
             with Checked():
-                for lbl, xt in (("f32", _t(x)), ("i8", _t(q0))):
+                for lbl, xt in (("f32", to_device(x)), ("i8", to_device(q0))):
                     for wq, wf in ((True, False), (False, True), (True, True)):
                         q, y = e.forward(xt, want_q=wq, want_f=wf)
                         if wq:
-                            _eq(f"{tag} {kw} [{lbl}] q", q, want["q_out"])
+                            same(f"{tag} {kw} [{lbl}] q", q, want["q_out"])
                         if wf:
-                            _eq(f"{tag} {kw} [{lbl}] y", y, want["y"])
+                            same(f"{tag} {kw} [{lbl}] y", y, want["y"])
     # the x2 anchor add (fp32 frame out): the oracle's frame + the nearest-upsampled input, one fp32 add
     net = O.synth_net("sesr_x2", 60, quan_bits=b)
     x = rand_frame((1, 3, 21, 70), 12)
     ya = (O.forward(net, x)["y"] + np.repeat(np.repeat(x, 2, axis=2), 2, axis=3)).astype(np.float32)
     for kw in (dict(), dict(force_general=True)):
         with Checked():
-            _, y = _engine(bundle_from_oracle(net), anchor_add=True, **kw).forward(_t(x), want_q=False, want_f=True)
-            _eq(f"anchor {kw}", y, ya)
+            _, y = _engine(bundle_from_oracle(net), anchor_add=True, **kw).forward(to_device(x), want_q=False, want_f=True)
+            same(f"anchor {kw}", y, ya)
 
 
 # ------------------------------------------------------------------------------------------------------------- 4. grouped launches
@@ -276,19 +248,19 @@ def test_grouped_launches_equal_single_frames():
     path = os.path.join(QB, "sesr_x4.q4.crop.npz")
     fx, _ = load_fixture(path)
     e = _engine(_bundle(path))
-    frames = [_t(fx["x"] * np.float32(0.5 + 0.1 * k)) for k in range(6)]
+    frames = [to_device(fx["x"] * np.float32(0.5 + 0.1 * k)) for k in range(6)]
     N, _, H, W = frames[0].shape
     want = [tuple(t.clone() for t in e.forward(f)) for f in frames]
     torch.cuda.synchronize()
     for group in (1, 2, 4):
-        oq = [torch.zeros(e.out_shape(N, H, W), dtype=torch.int8, device=_dev()) for _ in frames]
-        of = [torch.zeros(e.out_shape(N, H, W), dtype=torch.float32, device=_dev()) for _ in frames]
+        oq = [torch.zeros(e.out_shape(N, H, W), dtype=torch.int8, device=device()) for _ in frames]
+        of = [torch.zeros(e.out_shape(N, H, W), dtype=torch.float32, device=device()) for _ in frames]
         with Checked():
-            e.submission(frames, oq, [torch.cuda.Stream(device=_dev())], outs_f=of, group=group).enqueue(len(frames))
+            e.submission(frames, oq, [torch.cuda.Stream(device=device())], outs_f=of, group=group).enqueue(len(frames))
             torch.cuda.synchronize()
             for k in range(len(frames)):
-                _eq(f"group {group} frame {k} q", oq[k], want[k][0])
-                _eq(f"group {group} frame {k} y", of[k], want[k][1])
+                same(f"group {group} frame {k} q", oq[k], want[k][0])
+                same(f"group {group} frame {k} y", of[k], want[k][1])
 
 
 # ------------------------------------------------------------------------------------------------------------- 5. caller buffers
@@ -301,18 +273,18 @@ def test_odd_output_addresses_inside_a_canary_arena(q_off):
     path = os.path.join(QB, "sesr_x2_rand.q4.crop.npz")
     fx, _ = load_fixture(path)
     e = _engine(_bundle(path))
-    x = _t(fx["x"])
+    x = to_device(fx["x"])
     N, _, H, W = x.shape
     oshape = e.out_shape(N, H, W)
     n_out = int(np.prod(oshape))
-    arena = Arena(_dev(), Arena.room(n_out, 4 * n_out), canary=0xA5)
+    arena = Arena(device(), Arena.room(n_out, 4 * n_out), canary=0xA5)
     q = arena.place(oshape, torch.int8, q_off, name="out_q")
     y = arena.place(oshape, torch.float32, 4, name="out_f")
     with Checked():
         e.forward(x, out_q=q, out_f=y)
         torch.cuda.synchronize()
-        _eq("q", q, fx["q_out"])
-        _eq("y", y, fx["out"])
+        same("q", q, fx["q_out"])
+        same("y", y, fx["out"])
         assert arena.check() == []
 
 
@@ -326,14 +298,14 @@ def test_at_8_bits_the_narrow_engine_is_the_mfma_engine():
     fx, _ = load_fixture(path)
     bun = _bundle(path)
     before = _lib.narrow_instances()
-    a, m = sesrq.Engine(bun, _dev(), engine=_lib.ENGINE_MFMA), _engine(bun)
+    a, m = sesrq.Engine(bun, device(), engine=_lib.ENGINE_MFMA), _engine(bun)
     assert m.layer_engines() == a.layer_engines() and m.launch_plan() == a.launch_plan() and m.one_fma_layers() == a.one_fma_layers()
     assert not any("-q8" in n for n in m.layer_engines())
-    qa, ya = a.forward(_t(fx["x"]))
-    qm, ym = m.forward(_t(fx["x"]))
-    _eq("q", qm, qa)
-    _eq("y", ym, ya)
-    _eq("y (reference)", ym, fx["out"])
+    qa, ya = a.forward(to_device(fx["x"]))
+    qm, ym = m.forward(to_device(fx["x"]))
+    same("q", qm, qa)
+    same("y", ym, ya)
+    same("y (reference)", ym, fx["out"])
     assert _lib.narrow_instances() == before          # no narrow instantiation launched
 
 
@@ -345,10 +317,10 @@ def test_other_engine_values_and_the_debug_forward_stay_on_dot4():
     path = os.path.join(QB, "nrdm_3.q4.crop.npz")
     fx, _ = load_fixture(path)
     before = _lib.narrow_instances()
-    r = _engine(_bundle(path)).forward_debug(_t(fx["x"]), pe=True, acts=True, special=True)
+    r = _engine(_bundle(path)).forward_debug(to_device(fx["x"]), pe=True, acts=True, special=True)
     for k in range(5):
-        _eq(f"pe_out{k}", r[f"pe_out{k}"], fx[f"pe_out{k}"])
-    _eq("q_out", r["q_out"], fx["q_out"])
+        same(f"pe_out{k}", r[f"pe_out{k}"], fx[f"pe_out{k}"], reshape=True)      # stored without the batch axis
+    same("q_out", r["q_out"], fx["q_out"])
     assert _lib.narrow_instances() == before
     with pytest.raises(ValueError, match="bad engine option"):
         _engine(_bundle(path), engine=4)

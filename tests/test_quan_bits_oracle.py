@@ -13,11 +13,12 @@ import pytest
 import torch
 
 from conftest import GOLDEN, load_fixture
-from helpers import bundle_from_oracle, rand_frame
+from helpers import bundle_from_oracle, device, rand_frame, same
+from planner import expected_plan_and_engines
+from topologies import RAGGED_FRAMES as SIZES
 from oracle import sesrq_oracle as O
 import sesrq
 from sesrq import _lib
-from test_gpu_parity import SIZES, _cmp
 
 pytestmark = pytest.mark.gpu
 
@@ -25,19 +26,16 @@ WIDTHS = list(range(2, 8))
 QB = os.path.join(GOLDEN, "quan_bits")
 
 
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
-
-
 def _engine(net, **kw):
-    e = sesrq.Engine(bundle_from_oracle(net), _dev(), **kw)
+    e = sesrq.Engine(bundle_from_oracle(net), device(), **kw)
     assert e.quan_bits == net.quan_bits and all(n.endswith(f"-q{net.quan_bits}") for n in e.layer_engines()), e.layer_engines()
+    plan, names = expected_plan_and_engines(net, fast_division=e.fast_division_proven(), **kw)
+    assert e.launch_plan() == plan and e.layer_engines() == names, (net.name, kw, e.launch_plan(), plan, e.layer_engines(), names)
     return e
 
 
 def _run(e, x, **kw):
-    q, y = e.forward(torch.from_numpy(np.ascontiguousarray(x)).to(_dev()), **kw)
+    q, y = e.forward(torch.from_numpy(np.ascontiguousarray(x)).to(device()), **kw)
     return q.cpu().numpy(), y.cpu().numpy()
 
 
@@ -65,8 +63,8 @@ def test_synthetic_nets_at_the_width_vs_oracle(kind, b):
                 for fg, e in zip((False, True), engines):
                     q, y = _run(e, x)
                     tag = f"{net.name} general={fg} {N}x{H}x{W}"
-                    _cmp(f"{tag} q_out", q, want["q_out"])
-                    _cmp(f"{tag} y", y, want["y"])
+                    same(f"{tag} q_out", q, want["q_out"])
+                    same(f"{tag} y", y, want["y"])
             assert lo and hi, (net.name, lo, hi)
             if hard and b >= 6:
                 assert sat, f"{net.name}: no PE sum beyond 18 bits"
@@ -92,8 +90,8 @@ def test_zero_point_sweep_at_the_width(b):
             e = _engine(net, engine=_lib.ENGINE_DOT4)
             want = O.forward(net, x)
             q, y = _run(e, x)
-            _cmp(f"b={b} zero[{k}]={z} q_out", q, want["q_out"])
-            _cmp(f"b={b} zero[{k}]={z} y", y, want["y"])
+            same(f"b={b} zero[{k}]={z} q_out", q, want["q_out"])
+            same(f"b={b} zero[{k}]={z} y", y, want["y"])
             if k == 1:
                 seps.add(e.workspace(1, 8, 8).numel())
     assert len(seps) == 2          # zero[1] == qlo: layer 0's output is the residual operand; otherwise a separate one
@@ -128,7 +126,7 @@ def test_input_quantiser_edges_in_every_division_mode(b):
         if z0 is not None:
             net.zero[0] = z0
         x = _edge_frame(net, rng)
-        xt = torch.from_numpy(x).to(_dev())
+        xt = torch.from_numpy(x).to(device())
         q0 = O.quantize_input(x, net.scale[0], net.zero[0], quan_bits=b)
         q0r = O.quantize_input(x, net.scale[0], net.zero[0], reciprocal=True, quan_bits=b)
         assert (q0 == net.qlo).any() and (q0 == net.qhi).any()
@@ -136,15 +134,15 @@ def test_input_quantiser_edges_in_every_division_mode(b):
         for mode, kw in ((0, {}), (1, dict(exact_division=True)), (2, dict(reciprocal_division=True))):
             e = _engine(net, **kw)
             assert e.exact_div == mode
-            _cmp(f"b={b} s0={s0} exact_div={mode} input0", e.forward_debug(xt, pe=False)["input0"], q0r if mode == 2 else q0)
+            same(f"b={b} s0={s0} exact_div={mode} input0", e.forward_debug(xt, pe=False)["input0"], q0r if mode == 2 else q0)
             q, y = e.forward(xt)
             if mode == 2:
                 q_want, y_want = _run(_engine(net), q0r)      # an int8 frame is q0
-                _cmp(f"b={b} exact_div=2 q_out vs oracle", q, O.forward(net, q0r)["q_out"])
+                same(f"b={b} exact_div=2 q_out vs oracle", q, O.forward(net, q0r)["q_out"])
             else:
                 q_want, y_want = want["q_out"], want["y"]
-            _cmp(f"b={b} s0={s0} exact_div={mode} q_out", q, q_want)
-            _cmp(f"b={b} s0={s0} exact_div={mode} y", y, y_want)
+            same(f"b={b} s0={s0} exact_div={mode} q_out", q, q_want)
+            same(f"b={b} s0={s0} exact_div={mode} y", y, y_want)
     # the (scale, zero) pairs test_fast_division_is_proven_and_equals_exact_division finds proven at b = 8
     pairs = [(O.synth_net("sesr_x2", 1).scale[0], O.synth_net("sesr_x2", 1).zero[0])]
     for tag in ("sesr_x4", "nrdm_3", "sesr_x2_rand"):
@@ -169,8 +167,8 @@ def test_int8_q0_beyond_the_width_is_clamped(b):
         want = O.forward(net, np.clip(q0, net.qlo, net.qhi).astype(np.int8))
         for fg in (False, True):
             q, y = _run(_engine(net, force_general=fg), q0)
-            _cmp(f"{net.name} general={fg} q_out", q, want["q_out"])
-            _cmp(f"{net.name} general={fg} y", y, want["y"])
+            same(f"{net.name} general={fg} q_out", q, want["q_out"])
+            same(f"{net.name} general={fg} y", y, want["y"])
 
 
 @pytest.mark.parametrize("b", WIDTHS)
@@ -180,10 +178,10 @@ def test_x2_anchor_add_at_the_width(b):
     x = rand_frame((2, 3, 37, 70), 12 + b)
     q, y = _run(e, x)
     want = O.forward(net, x)
-    _cmp("int8 output unaffected", q, want["q_out"])
-    _cmp("y + upsampled input", y, want["y"] + np.repeat(np.repeat(x, 2, axis=2), 2, axis=3))
+    same("int8 output unaffected", q, want["q_out"])
+    same("y + upsampled input", y, want["y"] + np.repeat(np.repeat(x, 2, axis=2), 2, axis=3))
     with pytest.raises(RuntimeError, match="anchor"):
-        e.forward(torch.from_numpy(O.quantize_input(x, net.scale[0], net.zero[0], quan_bits=b)).to(_dev()))
+        e.forward(torch.from_numpy(O.quantize_input(x, net.scale[0], net.zero[0], quan_bits=b)).to(device()))
 
 
 @pytest.mark.parametrize("case,shape", [("nrdm_3.q3", (1, 3, 540, 960)), ("nrdm_3.q5", (1, 3, 540, 960)),
@@ -195,8 +193,8 @@ def test_full_frame_at_an_odd_width_vs_c_oracle(case, shape):
     x = rand_frame(shape, 5 + net.quan_bits)
     want = CO.forward(net, x, threads=16)
     q, y = _run(_engine(net), x)
-    _cmp(f"{case} q_out", q, want["q_out"])
-    _cmp(f"{case} y", y, want["y"])
+    same(f"{case} q_out", q, want["q_out"])
+    same(f"{case} y", y, want["y"])
 
 
 def _fakequant_ref(x, scale, zero, b):
@@ -223,7 +221,7 @@ def test_calibration_fake_quantiser_at_the_width(b):
     """sesrq_calib_fakequant_q bit for bit with its fp32 definition (ties, negatives, huge values, n not a multiple of 256), and
     sesrq_calib_fakequant_slot's pixel-shuffled store (r = 1, 2, 4) with the slot's f32(scale) and zero."""
     lib = _lib.lib()
-    dev = _dev()
+    dev = device()
     st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     rng = np.random.default_rng(40 + b)
     for scale, zero in ((0.0173, -(1 << (b - 1))), (0.0041, 0), (0.25, -200), (3.0e-3, (1 << (b - 1)) - 1)):
@@ -232,7 +230,7 @@ def test_calibration_fake_quantiser_at_the_width(b):
         xt = torch.from_numpy(x).to(dev)
         out = torch.full_like(xt, float("nan"))
         _lib.check(lib.sesrq_calib_fakequant_q(xt.data_ptr(), out.data_ptr(), n, float(np.float32(scale)), zero, b, st))
-        _cmp(f"fakequant_q b={b} s={scale} z={zero}", out, _fakequant_ref(x, scale, zero, b))
+        same(f"fakequant_q b={b} s={scale} z={zero}", out, _fakequant_ref(x, scale, zero, b), values=True)
         for r, N, Cc, H, W in ((1, 1, 3, 9, 31), (2, 2, 8, 7, 13), (4, 1, 32, 5, 11)):
             a = _fq_input(N * Cc * H * W, scale, zero, b, rng).reshape(N, Cc, H, W)
             slot = (_lib.CalibSlot * 1)()
@@ -243,5 +241,5 @@ def test_calibration_fake_quantiser_at_the_width(b):
             at = torch.from_numpy(a).to(dev)
             o = torch.full((N, Cc // (r * r), H * r, W * r), float("nan"), dtype=torch.float32, device=dev)
             _lib.check(lib.sesrq_calib_fakequant_slot(at.data_ptr(), o.data_ptr(), N, Cc, H, W, r, sl.data_ptr(), b, st))
-            _cmp(f"fakequant_slot b={b} r={r}", o, O.pixel_shuffle(_fakequant_ref(a, scale, zero, b), r))
+            same(f"fakequant_slot b={b} r={r}", o, O.pixel_shuffle(_fakequant_ref(a, scale, zero, b), r), values=True)
     torch.cuda.synchronize()

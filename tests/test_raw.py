@@ -4,7 +4,6 @@
 CPU: the q0 table against the reference's input.0 at every site of a frame that holds every code at every Bayer phase; raw file
 naming; the C ABI.  GPU: the unpacked q0 / fp32 frame against the reference's, the raw forward against the reference's outputs and
 against forward() on the fp32 frame, evaluate_raw, sim.py, the refusals, a side stream, and that every kernel instantiation ran."""
-import hashlib
 import json
 import os
 import re
@@ -14,6 +13,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
+from helpers import (device, raw_frame, raw_frames, raw_frames_sha, ref_gt, ref_inp, reference_levels, sha256, sites,
+                     spread_like)
 
 RAW = os.path.join(GOLDEN, "raw")
 HEADER = os.path.join(ROOT, "include", "sesrq_raw.h")
@@ -21,76 +22,14 @@ NETS = ("nrdm_3", "nrdm_3_qat")
 FRAMES = ("a", "b", "c")
 
 
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
-
-
-def frames():
-    return np.load(os.path.join(RAW, "frames.npz"), allow_pickle=False)
-
-
-def frames_sha():
-    return json.loads(str(frames()["meta"]))["sha"]
-
-
 def net_fixture(net):
     z = np.load(os.path.join(RAW, net + ".npz"), allow_pickle=False)
     return z, json.loads(str(z["meta"]))
 
 
-def sites(H, W):
-    """Site channel of every pixel: (0,0) R, (0,1) / (1,0) G, (1,1) B."""
-    yy, xx = np.meshgrid(np.arange(H) & 1, np.arange(W) & 1, indexing="ij")
-    return yy + xx
-
-
-def spread_like(raw, per_code, fill):
-    """(H, W) codes -> (3, H, W): per_code[min(code, 4095)] at the site channel, `fill` elsewhere."""
-    H, W = raw.shape
-    out = np.full((3, H, W), fill, per_code.dtype)
-    np.put_along_axis(out, sites(H, W)[None], per_code[np.minimum(raw, 4095)][None], 0)
-    return out
-
-
-def frame(f):
-    """(raw (H, W) uint16, ground truth (1, 3, H, W) uint16 RGB) of frame f, the bytes the reference ran on: frame (a) is stored,
-    (b) and (c) are regenerated (make_raw_golden.natural_raw)."""
-    if f == "a":
-        F = frames()
-        raw, gt16 = F["raw_a"], F["gt16_a"]
-    else:
-        import sys
-        sys.path.insert(0, GOLDEN)
-        from make_raw_golden import natural_raw
-        raw, gt16 = natural_raw(f)
-        gt16 = gt16[None]
-    s = frames_sha()
-    assert sha(raw) == s[f"raw_{f}"] and sha(gt16) == s[f"gt16_{f}"], f"frame {f} differs from the one the reference ran on"
-    return raw, gt16
-
-
-def reference_levels():
-    """x(code) for every code 0 .. 4095 as the reference formed it in inp (read off frame (a), which holds every code at every phase)."""
-    return frames()["levels_inp"]
-
-
-def ref_inp(f):
-    """The reference's fp32 input frame (1, 3, H, W) of frame f, rebuilt from its per-code values and checked against its SHA-256."""
-    x = spread_like(frame(f)[0], reference_levels(), np.float32(0))[None]
-    assert sha(x) == frames_sha()[f"inp_{f}"], f
-    return x
-
-
-def ref_gt(f):
-    """The reference's fp32 ground truth (1, 3, H, W) of frame f, rebuilt the same way."""
-    g = frames()["levels_gt"][np.minimum(frame(f)[1], 4095)]
-    assert sha(g) == frames_sha()[f"gt_{f}"], f
-    return g
-
-
 # ------------------------------------------------------------------------------------------------------------------------ CPU
 def test_frame_a_holds_every_code_at_every_phase():
-    raw = frame("a")[0]
+    raw = raw_frame("a")[0]
     assert raw.shape[0] >= 128 and raw.shape[1] >= 128
     for py in (0, 1):
         for px in (0, 1):
@@ -105,10 +44,10 @@ def test_table_equals_reference_input0_at_every_site(net):
     z, meta = net_fixture(net)
     t = R.table(meta["scale"][0], meta["zero"][0])
     for f in FRAMES:
-        assert sha(spread_like(frame(f)[0], t, t[0])[None]) == meta["sha"][f"input0_{f}"], (net, f)
-    assert np.array_equal(spread_like(frame("a")[0], t, t[0]), z["input0_a"][0])
+        assert sha256(spread_like(raw_frame(f)[0], t, t[0])[None]) == meta["sha"][f"input0_{f}"], (net, f)
+    assert np.array_equal(spread_like(raw_frame("a")[0], t, t[0]), z["input0_a"][0])
     # frame (a) pins every entry: each code's q0 sits at some site of it
-    raw = frame("a")[0]
+    raw = raw_frame("a")[0]
     ref = np.take_along_axis(z["input0_a"][0], sites(*raw.shape)[None], 0)[0]
     got = np.full(4096, 999, np.int32)
     got[np.minimum(raw, 4095)] = ref
@@ -119,7 +58,7 @@ def test_table_division_forms_match_the_oracle():
     from sesrq import raw as R
     from oracle import sesrq_oracle as O
     lv = reference_levels()
-    assert np.array_equal(lv, frames()["levels_gt"])        # inp and gt: one quotient per code
+    assert np.array_equal(lv, raw_frames()["levels_gt"])        # inp and gt: one quotient per code
     for f in FRAMES:
         ref_inp(f), ref_gt(f)                                  # the per-code values rebuild the reference's frames exactly
     for s0, z0 in ((0.0038037779284458536, -128), (0.0031, -140), (0.0052, -120), (1.7e-3, -128)):
@@ -183,25 +122,20 @@ def test_unpack_argument_checks_without_a_device():
 
 
 # ------------------------------------------------------------------------------------------------------------------------ GPU
-def _dev():
-    import torch
-    return torch.device("cuda:0")
-
-
 def _engine(net, **kw):
     import sesrq
     from sesrq.bundle import Bundle
-    return sesrq.Engine(Bundle.load(os.path.join(RAW, net + ".npz")), _dev(), **kw)
+    return sesrq.Engine(Bundle.load(os.path.join(RAW, net + ".npz")), device(), **kw)
 
 
 def _u16(a):
     import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint16)).to(_dev())
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint16)).to(device())
 
 
 def _batch(f, n):
     """n frames of frame f's size: frame f itself first, then its codes shuffled (seeded)."""
-    raw = frame(f)[0]
+    raw = raw_frame(f)[0]
     rng = np.random.default_rng(7)
     return np.stack([raw] + [rng.permutation(raw.ravel()).reshape(raw.shape) for _ in range(n - 1)])
 
@@ -226,12 +160,12 @@ def test_unpack_equals_reference_inp_and_input0(f, N):
     for q in (q_both, q_only):
         q = q.cpu().numpy()
         assert q.shape == (N, 3) + raws.shape[1:]
-        assert sha(q[:1]) == meta["sha"][f"input0_{f}"], f
+        assert sha256(q[:1]) == meta["sha"][f"input0_{f}"], f
         for n in range(1, N):
             assert np.array_equal(q[n], spread_like(raws[n], t, t[0])), (f, n)
     for sp in (sp_both, sp_only):
         sp = sp.cpu().numpy()
-        assert sha(sp[:1]) == frames_sha()[f"inp_{f}"], f
+        assert sha256(sp[:1]) == raw_frames_sha()[f"inp_{f}"], f
         for n in range(1, N):
             assert spread_like(raws[n], lv, np.float32(0)).tobytes() == sp[n].tobytes(), (f, n)
 
@@ -240,8 +174,8 @@ def test_unpack_equals_reference_inp_and_input0(f, N):
 def test_load_gt_equals_reference_gt():
     from sesrq import raw as R
     for f in FRAMES:
-        g = R.load_gt(frame(f)[1], _dev()).cpu().numpy()
-        assert g.dtype == np.float32 and sha(g) == frames_sha()[f"gt_{f}"], f
+        g = R.load_gt(raw_frame(f)[1], device()).cpu().numpy()
+        assert g.dtype == np.float32 and sha256(g) == raw_frames_sha()[f"gt_{f}"], f
 
 
 @pytest.mark.gpu
@@ -253,10 +187,10 @@ def test_forward_raw_equals_reference_outputs(net, engine):
     z, meta = net_fixture(net)
     e = _engine(net, engine=_lib.ENGINE_AUTO if engine == "auto" else _lib.ENGINE_DOT4)
     for f in FRAMES:
-        q, y = e.forward_raw(_u16(frame(f)[0])[None, None])
+        q, y = e.forward_raw(_u16(raw_frame(f)[0])[None, None])
         torch.cuda.synchronize()
-        assert sha(q.cpu().numpy()) == meta["sha"][f"out_q_{f}"], (net, engine, f)
-        assert sha(y.cpu().numpy()) == meta["sha"][f"out_{f}"], (net, engine, f)
+        assert sha256(q.cpu().numpy()) == meta["sha"][f"out_q_{f}"], (net, engine, f)
+        assert sha256(y.cpu().numpy()) == meta["sha"][f"out_{f}"], (net, engine, f)
 
 
 @pytest.mark.gpu
@@ -284,7 +218,7 @@ def test_forward_raw_equals_forward_on_the_spread_1080p():
 def test_evaluate_raw_equals_evaluate_on_the_spread():
     import torch
     from sesrq import quality
-    raws = [frame(f) for f in FRAMES]
+    raws = [raw_frame(f) for f in FRAMES]
     for net in NETS:
         e = _engine(net)
         got = quality.evaluate_raw(e, [r for r, _ in raws], [g for _, g in raws], 3)
@@ -299,7 +233,7 @@ def test_sim_raw_input_prints_the_fp32_route_mean_line(capsys, tmp_path):
     import sim
     from sesrq.store import STORE
     params = os.path.join(GOLDEN, "nrdm_3_nat.params.npz")
-    raw, gt16 = frame("b")
+    raw, gt16 = raw_frame("b")
     rawp = str(tmp_path / "frameb_80_960.raw")
     raw.astype("<u2").tofile(rawp)
     np.save(str(tmp_path / "gt16.npy"), gt16)
@@ -320,15 +254,15 @@ def test_sim_raw_input_prints_the_fp32_route_mean_line(capsys, tmp_path):
 def test_forward_raw_refusals():
     import sesrq
     from sesrq.bundle import Bundle
-    x = _u16(frame("c")[0])[None]
-    one = sesrq.Engine(Bundle.load(os.path.join(GOLDEN, "sesr_x4.crop.npz")), _dev())
+    x = _u16(raw_frame("c")[0])[None]
+    one = sesrq.Engine(Bundle.load(os.path.join(GOLDEN, "sesr_x4.crop.npz")), device())
     with pytest.raises(ValueError, match="3-channel"):
         one.forward_raw(x)
     nrdm = Bundle.load(os.path.join(RAW, "nrdm_3.npz"))
-    chained = sesrq.Engine(nrdm, _dev(), upstream=nrdm)
+    chained = sesrq.Engine(nrdm, device(), upstream=nrdm)
     with pytest.raises(ValueError, match="upstream"):
         chained.forward_raw(x)
-    anchored = sesrq.Engine(Bundle.load(os.path.join(GOLDEN, "sesr_x2_rand.crop.npz")), _dev(), anchor_add=True)
+    anchored = sesrq.Engine(Bundle.load(os.path.join(GOLDEN, "sesr_x2_rand.crop.npz")), device(), anchor_add=True)
     with pytest.raises(ValueError, match="anchor_add"):
         anchored.forward_raw(x)
     e = _engine("nrdm_3")
@@ -343,14 +277,14 @@ def test_forward_raw_on_a_side_stream():
     import torch
     e = _engine("nrdm_3")
     want = net_fixture("nrdm_3")[1]["sha"]["out_q_b"]
-    dev = _dev()
+    dev = device()
     side = torch.cuda.Stream(device=dev)
-    src = torch.from_numpy(frame("b")[0].astype(np.int32)).to(dev)
+    src = torch.from_numpy(raw_frame("b")[0].astype(np.int32)).to(dev)
     for _ in range(3):
         x = (src * 1).to(torch.uint16)[None]          # produced on the current stream just before the call
         q, y = e.forward_raw(x, stream=side)
         side.synchronize()
-        assert sha(q.cpu().numpy()) == want
+        assert sha256(q.cpu().numpy()) == want
         del x
 
 

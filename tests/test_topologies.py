@@ -24,15 +24,17 @@ numbers of channels or none, and the refusals of sesrq_create at the edges of th
 """
 import ctypes as C
 import functools
+import os
 
 import numpy as np
 import pytest
 
-from helpers import Arena, bundle_from_oracle, rand_frame
+from conftest import GOLDEN
+from helpers import Arena, bundle_from_oracle, device, fixture_case, rand_frame, same, stream_ptr, to_device
 from oracle import c_oracle as CO
 from oracle import sesrq_oracle as O
-from test_accumulator_limits import SIZES, np_verdict
-from topologies import NARROW, RISKY, TOPOLOGIES, case_net, risky_net, topo_net
+from planner import expected_plan_and_engines, np_verdict, verdicts
+from topologies import NARROW, RISKY, SEAM_FRAMES as SIZES, TOPOLOGIES, case_net, risky_net, topo_net
 import sesrq
 from sesrq import _lib
 
@@ -47,6 +49,9 @@ PLANS = [("default", dict()), ("per-layer", dict(fuse_hidden=0)), ("dot4", dict(
 STATED_PLANS = {"t6": [(0, 1), (1, 1), (2, 3), (5, 1)], "t7": [(0, 1), (1, 1), (2, 1), (3, 3), (6, 1)],
                 "t16": [(0, 1), (1, 1), (2, 1), (3, 3), (6, 3), (9, 3), (12, 3), (15, 1)],
                 "t15": [(k, 1) for k in range(5)], "tmix": [(k, 1) for k in range(5)]}
+# ... and what the reference's three 5-layer nets run by default (tests/golden/<name>.crop.npz): one trio, and the first / last kernels
+GOLDEN_PLANS = {"nrdm_3": ("mfma-f5-merged", "mfma-h5p-merged"), "sesr_x4": ("mfma-f5-merged", "mfma-h5-merged"),
+                "sesr_x2_rand": ("mfma-f5-hybrid", "mfma-h5-general")}
 
 
 def _cin(net):
@@ -76,62 +81,6 @@ def _net(key):
     if key[0] == "risky":
         return risky_net(*key[1:])
     return case_net(*key)
-
-
-# ------------------------------------------------------------------------------------------------ restatement of the planner
-def verdicts(net):
-    return [np_verdict(l.wq, l.add_const, net.zero[k], net.acc_bits, net.add_bits) for k, l in enumerate(net.layers)]
-
-
-def expected_plan_and_engines(net, engine=_lib.ENGINE_AUTO, force_general=False, fuse_hidden=1, fast_division=True, **_):
-    """launch_plan() and layer_engines() from the net alone.  Kernel kind by position and kernel size (first: 5x5 MFMA, 3x3 dot4; hidden:
-    h3 / h5; last: 5x5 h5, h5p for <= 4 channels, 3x3 dot4); mode from the saturation verdict (merged / one risky PE at 18 / 20 bits:
-    hybrid / general / beyond the biased range: unbiased); trios greedy from L-2 backwards over 3x3 16->16 saturation-free layers.
-    A net narrower than 8 bits has MFMA kinds under ENGINE_MFMA_Q only, and no hybrid there."""
-    L, b = net.L, net.quan_bits
-    v = verdicts(net)
-    sfx = f"-q{b}" if b < 8 else ""
-    narrow = b < 8
-    dot4_only = engine == _lib.ENGINE_DOT4 or (narrow and engine != _lib.ENGINE_MFMA_Q)
-    kinds, names = [], []
-    for k, l in enumerate(net.layers):
-        oc, ic, kk = l.wq.shape[:3]
-        if dot4_only or (narrow and not v[k]["biased_ok"]):
-            kind = None
-        elif k == 0:
-            kind = "f5" if kk == 5 else None
-        elif kk == 3:
-            kind = None if k == L - 1 else "h3"
-        else:
-            kind = "h5p" if (k == L - 1 and oc <= 4) else "h5"
-        kinds.append(kind)
-        d4 = ("dot4-merged" if v[k]["saturation_free"] else "dot4-general") + sfx
-        if kind is None or (k == 0 and not fast_division):
-            names.append(d4)
-            continue
-        one = bin(v[k]["risky_mask"]).count("1") == 1 and (net.acc_bits, net.add_bits) == (18, 20) and kind != "h5p" and not narrow
-        mode = "unbiased" if not v[k]["biased_ok"] else "merged" if v[k]["saturation_free"] else "hybrid" if one else "general"
-        names.append(f"mfma-{kind}-{mode}{sfx}")
-
-    def trio_ok(k):
-        oc, ic = net.layers[k].wq.shape[:2]
-        return 1 <= k <= L - 2 and kinds[k] == "h3" and v[k]["saturation_free"] and v[k]["biased_ok"] and ic == 16 and oc == 16
-
-    trio = set()
-    k = L - 4
-    while k >= 1 and trio_ok(k) and trio_ok(k + 1) and trio_ok(k + 2):
-        trio.add(k)
-        k -= 3
-    if not fuse_hidden or force_general or engine == _lib.ENGINE_DOT4:
-        trio = set()
-    plan, k = [], 0
-    while k < L:
-        n = 3 if k in trio else 1
-        if n == 3:
-            names[k:k + 3] = ["mfma-trio-merged" + sfx] * 3
-        plan.append((k, n))
-        k += n
-    return plan, names
 
 
 # ================================================================================================================== CPU part
@@ -273,6 +222,13 @@ def test_planner_restatement_on_the_stated_plans():
         assert expected_plan_and_engines(case_net(tid), fuse_hidden=0)[0] == [(k, 1) for k in range(case_net(tid).L)]
     for tid in ("t3", "t3n", "t4", "t4s", "t16n", "t1"):
         assert all(n == 1 for _, n in expected_plan_and_engines(case_net(tid))[0]), tid
+    for name, (first, last) in GOLDEN_PLANS.items():
+        net = fixture_case(os.path.join(GOLDEN, f"{name}.crop.npz"))[2]
+        assert expected_plan_and_engines(net) == ([(0, 1), (1, 3), (4, 1)], [first] + ["mfma-trio-merged"] * 3 + [last]), name
+        for kw in (dict(fuse_hidden=0), dict(force_general=True), dict(engine=_lib.ENGINE_DOT4)):
+            plan, names = expected_plan_and_engines(net, **kw)
+            assert plan == [(k, 1) for k in range(5)] and not any("trio" in n for n in names), (name, kw)
+        assert expected_plan_and_engines(net, fuse_hidden=0)[1] == [first] + ["mfma-h3-merged"] * 3 + [last], name
 
 
 def test_topo_net_draws_are_seeded_and_shaped():
@@ -289,32 +245,9 @@ def test_topo_net_draws_are_seeded_and_shaped():
 
 
 # ================================================================================================================== GPU part
-def _dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch.device("cuda:0")
-
-
-def _t(a):
-    import torch
-    return torch.from_numpy(np.array(a, order="C", copy=True)).to(_dev())
-
-
-def _cmp(name, got, want):
-    """Bit for bit; fp32 as words."""
-    got = got.cpu().numpy() if hasattr(got, "cpu") else np.asarray(got)
-    want = np.ascontiguousarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{name}: {got.dtype} {got.shape} != {want.dtype} {want.shape}"
-    g, w = (np.ascontiguousarray(got).view(np.uint32), want.view(np.uint32)) if got.dtype == np.float32 else (got, want)
-    bad = np.argwhere(g != w)
-    if len(bad):
-        i = tuple(bad[0])
-        raise AssertionError(f"{name}: {len(bad)} of {got.size} differ, first at {i}: got {got[i]!r} want {want[i]!r}")
-
-
 def _engine(net, **kw):
     """An engine and the proof that it runs the kernels its topology is planned for: launch_plan() and layer_engines() by name."""
-    e = sesrq.Engine(bundle_from_oracle(net), _dev(), **kw)
+    e = sesrq.Engine(bundle_from_oracle(net), device(), **kw)
     plan, names = expected_plan_and_engines(net, fast_division=e.fast_division_proven(), **kw)
     assert e.launch_plan() == plan, (net.name, kw, e.launch_plan(), plan)
     assert e.layer_engines() == names, (net.name, kw, e.layer_engines(), names)
@@ -323,16 +256,16 @@ def _engine(net, **kw):
 
 def _check_forward(tag, e, key, shape, int8_too=True):
     w = _want(key, shape)
-    q, y = e.forward(_t(w["x"]))
-    _cmp(f"{tag} {shape} q_out", q, w["q_out"])
-    _cmp(f"{tag} {shape} y", y, w["y"])
-    q, y = e.forward(_t(w["x"]), want_f=False)
+    q, y = e.forward(to_device(w["x"]))
+    same(f"{tag} {shape} q_out", q, w["q_out"])
+    same(f"{tag} {shape} y", y, w["y"])
+    q, y = e.forward(to_device(w["x"]), want_f=False)
     assert y is None
-    _cmp(f"{tag} {shape} q_out (int8 only)", q, w["q_out"])
+    same(f"{tag} {shape} q_out (int8 only)", q, w["q_out"])
     if int8_too:
-        q, y = e.forward(_t(w["q0"]))
-        _cmp(f"{tag} {shape} q_out (int8 q0 in)", q, w["q_out"])
-        _cmp(f"{tag} {shape} y (int8 q0 in)", y, w["y"])
+        q, y = e.forward(to_device(w["q0"]))
+        same(f"{tag} {shape} q_out (int8 q0 in)", q, w["q_out"])
+        same(f"{tag} {shape} y (int8 q0 in)", y, w["y"])
 
 
 @pytest.mark.gpu
@@ -360,25 +293,25 @@ def test_stage_taps_carry_the_real_channel_counts(tid, hard):
     L = net.L
     x = _frame(net, TAP_FRAME)
     st = O.forward(net, x, keep=True)
-    _cmp("numpy oracle == C oracle", st["q_out"], _want((tid, hard), TAP_FRAME)["q_out"])
+    same("numpy oracle == C oracle", st["q_out"], _want((tid, hard), TAP_FRAME)["q_out"])
     b = bundle_from_oracle(net)
     for tag, kw, acts in (("per-layer", dict(fuse_hidden=0), True), ("per-layer, PE taps only", dict(fuse_hidden=0), False), ("dot4", dict(engine=_lib.ENGINE_DOT4), True)):
-        e = sesrq.Engine(b, _dev(), **kw)
-        res = e.forward_debug(_t(x), pe=True, acts=acts, special=acts)
+        e = sesrq.Engine(b, device(), **kw)
+        res = e.forward_debug(to_device(x), pe=True, acts=acts, special=acts)
         for k, l in enumerate(net.layers):
             oc, ic = l.wq.shape[:2]
             assert tuple(res[f"pe_out{k}"].shape) == (1, 4, oc, *TAP_FRAME[1:]) and tuple(res[f"pe_add{k}"].shape) == (1, oc, *TAP_FRAME[1:])
-            _cmp(f"{net.name} [{tag}] pe_out{k}", res[f"pe_out{k}"][0], st[f"pe_out{k}"])
-            _cmp(f"{net.name} [{tag}] pe_add{k}", res[f"pe_add{k}"], st[f"pe_add{k}"])
+            same(f"{net.name} [{tag}] pe_out{k}", res[f"pe_out{k}"][0], st[f"pe_out{k}"])
+            same(f"{net.name} [{tag}] pe_add{k}", res[f"pe_add{k}"], st[f"pe_add{k}"])
             if acts:
                 assert tuple(res[f"input{k}"].shape) == (1, ic, *TAP_FRAME[1:])
-                _cmp(f"{net.name} [{tag}] input{k}", res[f"input{k}"], st[f"input{k}"])
+                same(f"{net.name} [{tag}] input{k}", res[f"input{k}"], st[f"input{k}"])
         if acts:
-            _cmp(f"{net.name} [{tag}] shortcut", res["shortcut"], st["shortcut"].astype(np.float32))
-            _cmp(f"{net.name} [{tag}] input4_special", res["input4_special"], st["input4_special"].astype(np.int8))
+            same(f"{net.name} [{tag}] shortcut", res["shortcut"], st["shortcut"].astype(np.float32))
+            same(f"{net.name} [{tag}] input4_special", res["input4_special"], st["input4_special"].astype(np.int8))
             assert res["shortcut"].shape[1] == net.layers[0].wq.shape[0] == res["input4_special"].shape[1] == net.layers[L - 2].wq.shape[0]
-        _cmp(f"{net.name} [{tag}] q_out (debug)", res["q_out"], st["q_out"])
-        _cmp(f"{net.name} [{tag}] y (debug)", res["y"], st["y"])
+        same(f"{net.name} [{tag}] q_out (debug)", res["q_out"], st["q_out"])
+        same(f"{net.name} [{tag}] y (debug)", res["y"], st["y"])
         e.close()
 
 
@@ -445,10 +378,10 @@ def _check_hidden_slots(e, net, key, shape, ws, what):
     assert len(where) == min(3, L - 1)
     for k, s_ in sorted(where.items()):
         view = got[s_ * slot:s_ * slot + N * H * W * 16].view(np.int8).reshape(N, H, W, 16)
-        _cmp(f"{what}: 16-lane output of layer {k} ({net.layers[k].wq.shape[0]} channels; byte x = channel (x >> 2) + 4 (x & 3))", view, want[k])
+        same(f"{what}: 16-lane output of layer {k} ({net.layers[k].wq.shape[0]} channels; byte x = channel (x >> 2) + 4 (x & 3))", view, want[k])
     if net.zero[1] != -128:      # layer 0 writes the residual operand apart
         assert len(got) == 4 * slot
-        _cmp(f"{what}: 16-lane residual operand", got[3 * slot:3 * slot + N * H * W * 16].view(np.int8).reshape(N, H, W, 16), want["rc"])
+        same(f"{what}: 16-lane residual operand", got[3 * slot:3 * slot + N * H * W * 16].view(np.int8).reshape(N, H, W, 16), want["rc"])
     else:
         assert len(got) == 3 * slot
 
@@ -463,19 +396,19 @@ def _forward_in_arena(e, net, key, shape, ws_fill, canary, what):
     assert ws_bytes >= 3 * N * H * W * 16
     oshape = e.out_shape(N, H, W)
     n_out = int(np.prod(oshape))
-    arena = Arena(_dev(), Arena.room(n_out, 4 * n_out, ws_bytes), canary)
+    arena = Arena(device(), Arena.room(n_out, 4 * n_out, ws_bytes), canary)
     q = arena.place(oshape, torch.int8, 0, name="out_q")
     y = arena.place(oshape, torch.float32, 0, name="out_f")
     ws = arena.place(ws_bytes, torch.uint8, 16, fill=ws_fill, name="workspace")
-    x = _t(w["x"])
+    x = to_device(w["x"])
     rc = lib.sesrq_forward(e._h, x.data_ptr(), _lib.F32, q.data_ptr(), y.data_ptr(), N, H, W, ws.data_ptr(), ws_bytes,
-                           C.c_void_p(torch.cuda.current_stream(_dev()).cuda_stream))
+                           stream_ptr())
     assert rc == 0, (what, _lib.last_error())
     torch.cuda.synchronize()
     stray = arena.check()
     assert not stray, f"{what}: bytes outside the caller's buffers changed: {stray[:6]}"
-    _cmp(f"{what} q_out", q, w["q_out"])
-    _cmp(f"{what} y", y, w["y"])
+    same(f"{what} q_out", q, w["q_out"])
+    same(f"{what} y", y, w["y"])
     _check_hidden_slots(e, net, key, shape, ws, what)
 
 
@@ -512,26 +445,26 @@ def test_grouped_launches_equal_single_forwards(tid, hard):
     net = case_net(tid, hard)
     wants = [_want((tid, hard), GROUP_FRAME, k) for k in range(GROUP_COUNT)]
     N, H, W = GROUP_FRAME
-    stream = [torch.cuda.Stream(device=_dev())]
+    stream = [torch.cuda.Stream(device=device())]
     for tag, kw in PLANS[:2]:
         e = _engine(net, **kw)
-        frames = [_t(w["x"]) for w in wants]
+        frames = [to_device(w["x"]) for w in wants]
         q1, y1 = e.forward(frames[0])
-        _cmp(f"{net.name} [{tag}] single forward q", q1, wants[0]["q_out"])
-        _cmp(f"{net.name} [{tag}] single forward y", y1, wants[0]["y"])
+        same(f"{net.name} [{tag}] single forward q", q1, wants[0]["q_out"])
+        same(f"{net.name} [{tag}] single forward y", y1, wants[0]["y"])
         for group in (1, 4):
-            oq = [torch.zeros(e.out_shape(N, H, W), dtype=torch.int8, device=_dev()) for _ in frames]
-            of = [torch.zeros(e.out_shape(N, H, W), dtype=torch.float32, device=_dev()) for _ in frames]
+            oq = [torch.zeros(e.out_shape(N, H, W), dtype=torch.int8, device=device()) for _ in frames]
+            of = [torch.zeros(e.out_shape(N, H, W), dtype=torch.float32, device=device()) for _ in frames]
             torch.cuda.synchronize()
             e.submission(frames, oq, stream, outs_f=of, group=group).enqueue(GROUP_COUNT)
             torch.cuda.synchronize()
             for k, w in enumerate(wants):
-                _cmp(f"{net.name} [{tag}] group {group} frame {k} q", oq[k], w["q_out"])
-                _cmp(f"{net.name} [{tag}] group {group} frame {k} y", of[k], w["y"])
+                same(f"{net.name} [{tag}] group {group} frame {k} q", oq[k], w["q_out"])
+                same(f"{net.name} [{tag}] group {group} frame {k} y", of[k], w["y"])
         e.close()
-    e = sesrq.Engine(bundle_from_oracle(net), _dev(), engine=_lib.ENGINE_DOT4)
-    frames = [_t(w["x"]) for w in wants]
-    oq = [torch.zeros(e.out_shape(N, H, W), dtype=torch.int8, device=_dev()) for _ in frames]
+    e = sesrq.Engine(bundle_from_oracle(net), device(), engine=_lib.ENGINE_DOT4)
+    frames = [to_device(w["x"]) for w in wants]
+    oq = [torch.zeros(e.out_shape(N, H, W), dtype=torch.int8, device=device()) for _ in frames]
     with pytest.raises(RuntimeError, match=r"group > 1 needs the MFMA first- and last-layer kernels \(this net / engine option runs them on dot4\)"):
         e.submission(frames, oq, stream, group=4).enqueue(GROUP_COUNT)
     torch.cuda.synchronize()
@@ -567,9 +500,9 @@ def test_anchor_add_on_other_depths_and_widths(tid, hard):
         for shape in SIZES:
             w = _want((tid, hard), shape)
             ya = (w["y"] + np.repeat(np.repeat(w["x"], 2, axis=2), 2, axis=3)).astype(np.float32)
-            q, y = e2.forward(_t(w["x"]))
-            _cmp(f"{net.name} [{tag}] anchor {shape} q_out", q, w["q_out"])
-            _cmp(f"{net.name} [{tag}] anchor {shape} y", y, ya)
-            _, y = e2.forward(_t(w["x"]), want_q=False)
-            _cmp(f"{net.name} [{tag}] anchor {shape} y (fp32 only)", y, ya)
+            q, y = e2.forward(to_device(w["x"]))
+            same(f"{net.name} [{tag}] anchor {shape} q_out", q, w["q_out"])
+            same(f"{net.name} [{tag}] anchor {shape} y", y, ya)
+            _, y = e2.forward(to_device(w["x"]), want_q=False)
+            same(f"{net.name} [{tag}] anchor {shape} y (fp32 only)", y, ya)
         e2.close()

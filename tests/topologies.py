@@ -71,6 +71,11 @@ def topo_net(widths, ks, cin, cout, ps, seed, hard=False, quan_bits=8, risky=Non
     return O.Net(layers=layers, scale=scale, zero=zero, M_res=M_res, n_res=n_res, pixel_shuffle=ps, name=name)
 
 
+# (N, H, W) frames.  SEAM_FRAMES cross a 64-column strip, a row tile and (N = 2) a frame seam; RAGGED_FRAMES walk the tile edges of
+# the dot4 and MFMA kernels from one pixel up, with batches
+SEAM_FRAMES = ((2, 21, 70), (1, 41, 130))
+RAGGED_FRAMES = [(1, 1, 1), (1, 3, 5), (1, 8, 32), (1, 9, 33), (2, 17, 70), (1, 40, 129), (3, 31, 64), (1, 26, 121)]
+
 # id -> (kernel sizes, hidden widths, cin, cout, PixelShuffle): what each row reaches is told in tests/test_topologies.py
 TOPOLOGIES = {
     "t3": ((5, 3, 5), (16, 16), 3, 12, 2),
