@@ -13,7 +13,12 @@
  *                    pred is the anchored fp32 output (sesrq_options.anchor_add = 1).
  * SSIM is skimage's default: 7x7 uniform window, K1 = 0.01, K2 = 0.03, sample covariance (49/48), mean of the SSIM map over the
  * windows that lie wholly inside the frame (the frame cropped by 3 pixels on each side); H and W must be at least 7.
- * gt is never clipped. */
+ * gt is never clipped.
+ *
+ * NaN inside a frame: the clip is np.clip's, which passes a NaN on.  A NaN anywhere in an fp32 pred or in gt (for
+ * sesrq_eval_anchored, also in lr: the prediction is pred + up2(lr)) makes that frame's mse, psnr and ssim NaN, as the reference
+ * prints them; the other frames of the batch keep their bits.  An int8 pred has no NaN.  +-Inf in a frame is unspecified.
+ * (tests/test_quality_seams.py) */
 #ifndef SESRQ_EVAL_H
 #define SESRQ_EVAL_H
 

@@ -67,7 +67,9 @@ __device__ inline void load4(const float *row, int col, int W, bool vec, float v
     }
 }
 
-__device__ inline float clip01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
+// np.clip of the reference: a NaN passes through (fminf / fmaxf alone would return the bound), so a NaN in a frame reaches its scores
+__device__ inline float clip01(float x) { return x != x ? x : fminf(fmaxf(x, 0.f), 1.f); }
+__device__ inline double clip255(double x) { return x != x ? x : fmin(fmax(x, 0.0), 255.0); }
 
 // pred: clip(pred) to [0, 1]; an int8 frame is first dequantised exactly as sesrq_forward forms out_f: (q - zero_L) * scale_out in fp32
 __device__ inline void load_pred(const float *row, int col, int W, bool vec, float, int, float v[KC]) {
@@ -191,7 +193,7 @@ __global__ __launch_bounds__(64 * 3) void eval_tile(TileArgs a) {
             }
 #pragma unroll
             for (int k = 0; k < KC; ++k) {
-                const double yp = fmin(fmax(lp[k] + 16.0, 0.0), 255.0), yg = fmin(fmax(lg[k] + 16.0, 0.0), 255.0);
+                const double yp = clip255(lp[k] + 16.0), yg = clip255(lg[k] + 16.0);
                 const double d = yg - yp;
                 if (col + k >= c0 && col + k < m_c1) sse += d * d;
             }

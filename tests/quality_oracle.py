@@ -22,8 +22,9 @@ def box_mean(a):
     return (c[..., WIN:, :] - c[..., :-WIN, :]) / (WIN * WIN)
 
 
-def ssim_channel(x, y, data_range=1.0):
-    """skimage structural_similarity of two (H, W) images with its default arguments."""
+def window_moments(x, y):
+    """(ux, uy, vx, vy, vxy) of two (H, W) images over every 7x7 window wholly inside them: the window means and skimage's sample
+    (co)variances (49/48), float64, each of shape (H - 6, W - 6)."""
     x = np.asarray(x, np.float64)
     y = np.asarray(y, np.float64)
     if x.shape[-1] < WIN or x.shape[-2] < WIN:
@@ -31,10 +32,19 @@ def ssim_channel(x, y, data_range=1.0):
     ux, uy = box_mean(x), box_mean(y)
     uxx, uyy, uxy = box_mean(x * x), box_mean(y * y), box_mean(x * y)
     cov = WIN * WIN / (WIN * WIN - 1.0)
-    vx, vy, vxy = cov * (uxx - ux * ux), cov * (uyy - uy * uy), cov * (uxy - ux * uy)
+    return ux, uy, cov * (uxx - ux * ux), cov * (uyy - uy * uy), cov * (uxy - ux * uy)
+
+
+def ssim_map(x, y, data_range=1.0):
+    """The SSIM map skimage averages: one value per 7x7 window wholly inside two (H, W) images, (H - 6, W - 6), float64."""
+    ux, uy, vx, vy, vxy = window_moments(x, y)
     C1, C2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
-    S = ((2 * ux * uy + C1) * (2 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2))
-    return float(S.mean(dtype=np.float64))
+    return ((2 * ux * uy + C1) * (2 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2))
+
+
+def ssim_channel(x, y, data_range=1.0):
+    """skimage structural_similarity of two (H, W) images with its default arguments."""
+    return float(ssim_map(x, y, data_range).mean(dtype=np.float64))
 
 
 def luma255(img):
