@@ -26,6 +26,7 @@ and fused-trio kernels alike; the dot4 kernels were right.  +-2^22 +- 1 itself c
 import numpy as np
 import pytest
 
+from constructions import HALF, MARGIN, ONE, _pe_weights, _spread, build_layer, probe, relay, sat
 from helpers import bundle_from_oracle, device, same
 from oracle import sesrq_oracle as O
 from topologies import SEAM_FRAMES as SIZES
@@ -33,102 +34,7 @@ from planner import LIMIT, expected_plan_and_engines, np_verdict, verdicts
 import sesrq
 from sesrq import _lib
 
-ONE = (1 << 15, 15)            # M * 2^-n == 1: the output byte moves with every LSB of the sum
-HALF = (1 << 15, 16)           # residual merge of two equal operands: (2 q + 256) / 2 - 128 == q
 TINY = (65024, 32)             # 63.5 * 2^-22: s = 2^22 lands on the tie 63.5, +-6.45 M on +-97.7
-MARGIN = 8                     # receptive radius of the five layers is 7: pixels further inside see no padding
-
-
-# ------------------------------------------------------------------------------------------------ bound-attaining construction
-def _spread(total, slots):
-    """`total` as `slots` weights of one sign, each within int8's symmetric part."""
-    sign, rest, out = (1 if total >= 0 else -1), abs(int(total)), []
-    for _ in range(slots):
-        out.append(sign * min(127, rest))
-        rest -= min(127, rest)
-    if rest:
-        raise ValueError(f"weight sum {total} does not fit {slots} taps")
-    return out
-
-
-def _pe_weights(T, chans, planes, taps):
-    """Weights [len(chans)][taps] of one PE whose sum over constant planes is exactly T = 127 A - 128 B, A / B = the weight sums on the
-    127 / -128 planes.  The representation with A and B of opposite sign (T >= 0: A >= 0 >= B) makes T the PE's static extreme."""
-    chans = [c for c in chans if planes[c] is not None]      # a varying channel (a relayed byte) carries no probe weight
-    hi = [c for c in chans if planes[c] == 127]
-    lo = [c for c in chans if planes[c] == -128]
-    if not chans:
-        raise ValueError("a probed PE needs input channels with known constant planes")
-    if T == 0:
-        A = B = 0
-    elif not hi or (lo and T % 128 == 0):
-        if T % 128:
-            raise ValueError(f"PE sum {T} is no multiple of 128 and the PE has no 127 plane")
-        A, B = 0, -T // 128
-    elif not lo:
-        if T % 127:
-            raise ValueError(f"PE sum {T} is no multiple of 127 and the PE has no -128 plane")
-        A, B = T // 127, 0
-    else:
-        A = (-T) % 128 if T >= 0 else -(T % 128)
-        B = (127 * A - T) // 128
-    assert 127 * A - 128 * B == T
-    w = {c: [0] * taps for c in chans}
-    for total, group in ((A, hi), (B, lo)):
-        if total:
-            flat = _spread(total, len(group) * taps)
-            for i, c in enumerate(group):
-                w[c] = flat[i * taps:(i + 1) * taps]
-    return w
-
-
-def sat(c):
-    return ("sat", c)
-
-
-def relay(j):
-    return ("relay", j)
-
-
-def probe(T, s):
-    """An output channel whose four raw PE sums are T[0..3] at interior pixels and whose sum + add constant is s there."""
-    return ("probe", tuple(int(t) for t in T), int(s))
-
-
-def build_layer(k, ic, rows, planes, Mn, relu, bits):
-    """rows -> (O.Layer, {row: (T, s)}).  planes[c]: the constant value of input channel c, or None (varying: relays only)."""
-    taps, ctr = k * k, (k * k) // 2
-    acc_lo, acc_hi = -(1 << (bits[0] - 1)), (1 << (bits[0] - 1)) - 1
-    add_lo, add_hi = -(1 << (bits[1] - 1)), (1 << (bits[1] - 1)) - 1
-    w = np.zeros((len(rows), ic, taps), np.int64)
-    ac = np.zeros(len(rows), np.int64)
-    probes = {}
-    for o, row in enumerate(rows):
-        if row[0] == "sat":           # small weights of one sign, a constant that dominates them, a requant that saturates
-            w[o, :, ctr] = 1
-            ac[o] = 32767 if row[1] == 127 else -32768
-            if row[1] == 127 and (32767 - 128 * ic) * Mn[0] * 2.0 ** -Mn[1] < 255:
-                raise ValueError("this requant multiplier cannot saturate a 127 plane")
-        elif row[0] == "relay":       # q -> q: one centre tap, + 128, M 2^-n == 1, ReLU a no-op, zero point -128
-            if Mn != ONE or row[1] >= ic:
-                raise ValueError("a relay needs M * 2^-n == 1 and an existing input channel")
-            w[o, row[1], ctr] = 1
-            ac[o] = 128
-        else:
-            _, T, s = row
-            for p in range(4):
-                chans = list(range(p, ic, 4))
-                if T[p] == 0 and not chans:
-                    continue
-                for c, wc in _pe_weights(T[p], chans, planes, taps).items():
-                    w[o, c] = wc
-            tot = min(max(sum(min(max(t, acc_lo), acc_hi) for t in T), add_lo), add_hi)
-            ac[o] = s - tot
-            if abs(ac[o]) > 1 << 24:
-                raise ValueError("add constant beyond what sesrq_create accepts")
-            probes[o] = (T, s)
-    lay = O.Layer(wq=w.reshape(len(rows), ic, k, k).astype(np.int8), add_const=ac.astype(np.int32), M=Mn[0], n=Mn[1], relu=relu)
-    return lay, probes
 
 
 class Case:
