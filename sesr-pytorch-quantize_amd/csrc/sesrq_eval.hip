@@ -21,30 +21,12 @@
 
 #include "sesrq_eval.h"
 #include "sesrq_eval_anchor.h"
+#include "sesrq_eval_tile.h"
 #include "sesrq_side.h"
 
 namespace sesrq_evalk {
 
-constexpr int KC = 4;              // columns per lane
-constexpr int BAND = 64 * KC;      // input columns of one tile
-constexpr int OW = 248;            // SSIM output columns per tile (BAND - 6, rounded down to a multiple of 4: tiles start 16-B aligned)
-constexpr int RH = 32;             // SSIM output rows per tile
-constexpr int PAD = 3;             // window radius
-constexpr int FIN_THREADS = 256;
-static_assert(OW % 4 == 0 && OW <= BAND - 2 * PAD, "a tile's SSIM columns need their halo inside the band");
-
-struct Geometry {
-    int nbx, nby, ntiles;
-};
-
-// A function of (H, W) only: a frame's partial sums, and so its result, do not depend on N, the stream or the other frames.
-static inline Geometry geometry(int H, int W) {
-    Geometry g;
-    g.nbx = (W - 2 * PAD + OW - 1) / OW;
-    g.nby = (H - 2 * PAD + RH - 1) / RH;
-    g.ntiles = g.nbx * g.nby;
-    return g;
-}
+using namespace sesrq_tile;      // the tile geometry and the row-window core (csrc/sesrq_eval_tile.h)
 
 struct TileArgs {
     const void *pred;
@@ -56,19 +38,7 @@ struct TileArgs {
     int zero;
 };
 
-// four consecutive columns of one row; zeros past the right edge (they reach only SSIM outputs that are never used)
-__device__ inline void load4(const float *row, int col, int W, bool vec, float v[KC]) {
-    if (vec) {
-        float4 t = col < W ? *reinterpret_cast<const float4 *>(row + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < KC; ++k) v[k] = col + k < W ? row[col + k] : 0.f;
-    }
-}
-
-// np.clip of the reference: a NaN passes through (fminf / fmaxf alone would return the bound), so a NaN in a frame reaches its scores
-__device__ inline float clip01(float x) { return x != x ? x : fminf(fmaxf(x, 0.f), 1.f); }
+// np.clip on the float64 luma: a NaN passes through, as clip01
 __device__ inline double clip255(double x) { return x != x ? x : fmin(fmax(x, 0.0), 255.0); }
 
 // pred: clip(pred) to [0, 1]; an int8 frame is first dequantised exactly as sesrq_forward forms out_f: (q - zero_L) * scale_out in fp32
@@ -99,25 +69,9 @@ __device__ inline void load_pred_anchored(const float *row, const float *arow, i
     for (int k = 0; k < KC; ++k) v[k] = clip01(__fadd_rn(v[k], col + k < W ? arow[(col + k) >> 1] : 0.f));
 }
 
-// the 10 columns col-3 .. col+6 of one row: three from the lane on the left, four own, three from the lane on the right
-// (lanes 0 and 63 receive their own values; they reach only SSIM outputs outside the tile)
-__device__ inline void halo(const float own[KC], float out[KC + 2 * PAD]) {
-#pragma unroll
-    for (int k = 0; k < PAD; ++k) out[k] = __shfl_up(own[KC - PAD + k], 1);
-#pragma unroll
-    for (int k = 0; k < KC; ++k) out[PAD + k] = own[k];
-#pragma unroll
-    for (int k = 0; k < PAD; ++k) out[PAD + KC + k] = __shfl_down(own[k], 1);
-}
-
-__device__ inline double moment(int m, double x, double y) {
-    return m == 0 ? x : m == 1 ? y : m == 2 ? x * x : m == 3 ? y * y : x * y;
-}
-
 template <typename T, int FORM>
 __global__ __launch_bounds__(64 * 3) void eval_tile(TileArgs a) {
     constexpr int C = FORM == SESRQ_EVAL_Y255 ? 1 : 3;
-    constexpr int NC = KC + 2 * PAD;
     const int lane = threadIdx.x & 63;
     const int c = threadIdx.x >> 6;                                 // one wave per channel of the tile: they read the same rows at once
     const int tile = blockIdx.x, n = blockIdx.y, H = a.H, W = a.W;
@@ -198,47 +152,16 @@ __global__ __launch_bounds__(64 * 3) void eval_tile(TileArgs a) {
                 if (col + k >= c0 && col + k < m_c1) sse += d * d;
             }
         }
-        float hx[NC], hy[NC], hxo[NC], hyo[NC];
-        halo(x, hx);
-        halo(y, hy);
-        halo(xo, hxo);
-        halo(yo, hyo);
-#pragma unroll
-        for (int m = 0; m < 5; ++m) {
-            double d[NC];
-#pragma unroll
-            for (int i = 0; i < NC; ++i) d[i] = moment(m, hx[i], hy[i]) - moment(m, hxo[i], hyo[i]);
-            double h = d[0] + d[1] + d[2] + d[3] + d[4] + d[5] + d[6];
-            S[0][m] += h;
-#pragma unroll
-            for (int k = 1; k < KC; ++k) {
-                h = h + d[k + 6] - d[k - 1];
-                S[k][m] += h;
-            }
-        }
+        window_step(x, y, xo, yo, S);
         if (emit) {
 #pragma unroll
             for (int k = 0; k < KC; ++k) {
-                const double ux = S[k][0] * (1.0 / 49.0), uy = S[k][1] * (1.0 / 49.0);
-                const double cov = 49.0 / 48.0;
-                const float fux = (float)ux, fuy = (float)uy;
-                const float vx = (float)(cov * (S[k][2] * (1.0 / 49.0) - ux * ux));
-                const float vy = (float)(cov * (S[k][3] * (1.0 / 49.0) - uy * uy));
-                const float vxy = (float)(cov * (S[k][4] * (1.0 / 49.0) - ux * uy));
-                const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-                const float A1 = 2.f * fux * fuy + C1, A2 = 2.f * vxy + C2;
-                const float B1 = fux * fux + fuy * fuy + C1, B2 = vx + vy + C2;
-                const float s = (A1 * A2) / (B1 * B2);
+                const float s = window_ssim(S[k]);
                 if (col + k >= s_c0 && col + k < s_c1) ssim += (double)s;
             }
         }
     }
-    // fixed-order butterfly over the wave: the same bits on every run
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        sse += __shfl_xor(sse, o);
-        ssim += __shfl_xor(ssim, o);
-    }
+    wave_sum2(sse, ssim);
     if (lane == 0) {
         double *p = a.part + (((size_t)n * a.ntiles + tile) * C + c) * 2;
         p[0] = sse;
@@ -251,22 +174,7 @@ __global__ __launch_bounds__(FIN_THREADS) void eval_finish(const double *part, i
     __shared__ double s_sse[FIN_THREADS], s_ssim[FIN_THREADS];
     const int n = blockIdx.x, t = threadIdx.x;
     const int nparts = ntiles * C;                  // (tile, channel) partials of the frame
-    const double *p = part + (size_t)n * nparts * 2;
-    double a = 0.0, b = 0.0;
-    for (int i = t; i < nparts; i += FIN_THREADS) {
-        a += p[2 * i];
-        b += p[2 * i + 1];
-    }
-    s_sse[t] = a;
-    s_ssim[t] = b;
-    __syncthreads();
-    for (int s = FIN_THREADS / 2; s > 0; s >>= 1) {
-        if (t < s) {
-            s_sse[t] += s_sse[t + s];
-            s_ssim[t] += s_ssim[t + s];
-        }
-        __syncthreads();
-    }
+    frame_sum2(part + (size_t)n * nparts * 2, nparts, s_sse, s_ssim);
     if (t == 0) {
         const double px = (double)H * W;
         double mse, psnr;

@@ -1,10 +1,13 @@
 """PSNR / SSIM of output frames on the device: the reference's evaluation loop (test.py:141-183).
 
-ctypes binding of libsesrq_eval.so (C ABI declared in include/sesrq_eval.h), ``score()`` for a batch of frames already on the
-device, and ``evaluate()``: forward + score over a set of frames, one synchronisation at the end.  There is no CPU path: scoring
+ctypes bindings of libsesrq_eval.so (C ABI declared in include/sesrq_eval.h) and libsesrq_mosaic.so (include/sesrq_mosaic.h),
+``score()`` for a batch of frames already on the device, and ``evaluate()``: forward + score over a set of frames, one synchronisation at the end.  There is no CPU path: scoring
 needs the device, as the forward does.
 
 The metric form follows the network (MFLAG, reference sim.py ``MODELS``):
+  1     nr                     MOSAIC skimage PSNR (data_range 1) and single-channel SSIM of three2one(pred), three2one(gt): the
+                               Bayer mosaics, channel (row & 1) + (column & 1) of each pixel (libsesrq_mosaic.so)
+  2     dm                     RGB   as 3, 4
   3, 4  nrdm_small / nrdm_big  RGB   skimage PSNR (data_range 1), SSIM = mean over the three channels
   5     srx4                   Y255  compute_psnr(255 gt, 255 pred) (eps 1e-8), single-channel SSIM
   6     srx2                   X2    compute_psnr(rgb_to_yuv(gt), rgb_to_yuv(pred)) on the anchored output, SSIM as RGB
@@ -19,11 +22,14 @@ from . import _lib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "lib", "libsesrq_eval.so"))
+MOSAIC_LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "lib", "libsesrq_mosaic.so"))
 
 FORM_RGB, FORM_Y255, FORM_X2 = 0, 1, 2
+FORM_MOSAIC = 3                     # scored by libsesrq_mosaic.so: not a form of sesrq_eval
 PRED_F32, PRED_I8 = 0, 1
-FORMS = {3: FORM_RGB, 4: FORM_RGB, 5: FORM_Y255, 6: FORM_X2}
-CHANNELS = {FORM_RGB: 3, FORM_Y255: 1, FORM_X2: 3}
+FORMS = {1: FORM_MOSAIC, 2: FORM_RGB, 3: FORM_RGB, 4: FORM_RGB, 5: FORM_Y255, 6: FORM_X2}
+CHANNELS = {FORM_RGB: 3, FORM_Y255: 1, FORM_X2: 3, FORM_MOSAIC: 3}
+RAW_MFLAGS = (1, 2, 3, 4)           # the denoise / demosaic nets: what 12-bit RGGB raw frames feed
 TASKS = {1: "nr", 2: "dm", 3: "nrdm_small", 4: "nrdm_big", 5: "srx4", 6: "srx2"}     # reference test.py:182
 
 
@@ -52,6 +58,25 @@ _so = _lib.Library(LIB_PATH, SYMBOLS, "sesrq.quality", "sesrq_eval", counters="k
 lib, last_error, kernels = _so.lib, _so.last_error, _so.instances
 
 
+class MosaicDesc(C.Structure):
+    _fields_ = [("pred_dtype", C.c_int32), ("pred_scale", C.c_float), ("pred_zero", C.c_int32)]
+
+
+# every symbol include/sesrq_mosaic.h declares: name -> (restype, argtypes)
+MOSAIC_SYMBOLS = {
+    "sesrq_mosaic_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "sesrq_mosaic_score": (C.c_int, [C.POINTER(MosaicDesc), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_size_t, C.c_void_p]),
+    "sesrq_mosaic_kernel_count": (C.c_int, []),
+    "sesrq_mosaic_kernel_name": (C.c_char_p, [C.c_int]),
+    "sesrq_mosaic_kernel_launches": (C.c_longlong, [C.c_int]),
+    "sesrq_mosaic_last_error": (C.c_char_p, []),
+}
+
+_mosaic_so = _lib.Library(MOSAIC_LIB_PATH, MOSAIC_SYMBOLS, "sesrq.quality", "sesrq_mosaic", counters="kernel")
+mosaic_lib, mosaic_last_error, mosaic_kernels = _mosaic_so.lib, _mosaic_so.last_error, _mosaic_so.instances
+
+
 _anchor_bound = False
 
 
@@ -69,7 +94,7 @@ def anchored_lib():
 
 def form_of(mflag: int) -> int:
     if mflag not in FORMS:
-        raise ValueError(f"MFLAG {mflag}: only 3, 4 (RGB), 5 (srx4) and 6 (srx2) have a metric on the integer path")
+        raise ValueError(f"MFLAG {mflag}: only 1 (nr, mosaic), 2, 3, 4 (RGB), 5 (srx4) and 6 (srx2) have a metric on the integer path")
     return FORMS[mflag]
 
 
@@ -78,7 +103,8 @@ def score(pred, gt, mflag: int, scale=None, zero=None, stream=None):
 
     pred: (N, C, H, W) float32 output frames, or int8 output frames with the net's output domain (scale = f32(input.L.scale),
     zero = zero[L]), dequantised on the device to the bits of the float output; gt: float32 of the same shape and device.
-    For MFLAG 6, pred is the anchored float output (Engine(..., anchor_add=True))."""
+    For MFLAG 6, pred is the anchored float output (Engine(..., anchor_add=True)).  MFLAG 1 scores the Bayer mosaics of the two
+    3-channel frames (libsesrq_mosaic.so); mse is then the mosaic's, over H W."""
     import torch
     form = form_of(mflag)
     if not isinstance(pred, torch.Tensor) or not isinstance(gt, torch.Tensor):
@@ -96,19 +122,28 @@ def score(pred, gt, mflag: int, scale=None, zero=None, stream=None):
         raise ValueError(f"pred ({pred.device}) and gt ({gt.device}) must be on one HIP device")
     if gt.dtype != torch.float32:
         raise ValueError("gt must be float32")
-    d = EvalDesc(form=form, pred_dtype=PRED_F32, pred_scale=0.0, pred_zero=0)
+    dtype, pscale, pzero = PRED_F32, 0.0, 0
     if pred.dtype == torch.int8:
         if scale is None or zero is None:
             raise ValueError("an int8 prediction needs the output domain: scale and zero")
         if form == FORM_X2:
             raise ValueError("MFLAG 6 scores the anchored float output; the anchor does not exist in the int8 output")
-        d.pred_dtype, d.pred_scale, d.pred_zero = PRED_I8, float(scale), int(zero)
+        dtype, pscale, pzero = PRED_I8, float(scale), int(zero)
     elif pred.dtype != torch.float32:
         raise ValueError("pred must be float32 or int8")
     dev = pred.device
     with torch.cuda.device(dev):
         pred, gt = pred.contiguous(), gt.contiguous()
         out = torch.empty((N, 3), dtype=torch.float64, device=dev)
+        if form == FORM_MOSAIC:
+            md = MosaicDesc(pred_dtype=dtype, pred_scale=pscale, pred_zero=pzero)
+            ws = torch.empty(max(1, mosaic_lib().sesrq_mosaic_workspace_bytes(N, H, W)), dtype=torch.uint8, device=dev)
+            st = _lib.enter_stream(dev, stream, pred, gt, out, ws)
+            if mosaic_lib().sesrq_mosaic_score(C.byref(md), pred.data_ptr(), gt.data_ptr(), N, H, W, out.data_ptr(), ws.data_ptr(),
+                                               ws.numel(), st.cuda_stream) != 0:
+                raise ValueError("sesrq_mosaic_score: " + mosaic_last_error())
+            return out
+        d = EvalDesc(form=form, pred_dtype=dtype, pred_scale=pscale, pred_zero=pzero)
         ws = torch.empty(max(1, lib().sesrq_eval_workspace_bytes(N, Ch, H, W)), dtype=torch.uint8, device=dev)
         st = _lib.enter_stream(dev, stream, pred, gt, out, ws)
         rc = lib().sesrq_eval(C.byref(d), pred.data_ptr(), gt.data_ptr(), N, Ch, H, W, out.data_ptr(), ws.data_ptr(), ws.numel(),
@@ -154,16 +189,21 @@ def score_anchored(pred, lr, gt, stream=None):
 KINDS = ("f32", "raw", "image")
 
 
-def check_calibration_input(calibrator, mflag: int, kind: str):
-    """The refusals of evaluate_calibration, before any device work: the input kind must fit the MFLAG (raw frames: 3 / 4, images:
-    5 / 6) and the net's input channels, and the calibrator must be on the min/max rule (the device pass has no entropy variant)."""
+def check_calibration_input(calibrator, mflag: int, kind: str, scored: bool = True):
+    """The refusals of evaluate_calibration, before any device work: the input kind must fit the MFLAG (raw frames: 1 ... 4, images:
+    5 / 6) and the net's input channels, and the calibrator must be on the min/max rule (the device pass has no entropy variant).
+    The scored loop has no MFLAG 1 ("Not covered"); scored=False is the calibration pass alone (test.py without
+    --gt), whose domains do not depend on the metric."""
     form_of(mflag)
+    if scored and FORMS[mflag] == FORM_MOSAIC:
+        raise ValueError(f"MFLAG {mflag}: the scored calibration loop has no mosaic form; calibrate without ground truths and score "
+                         "the integer path's output (evaluate, evaluate_raw, sim.py --gt)")
     if kind not in KINDS:
         raise ValueError(f"kind {kind!r}: one of {KINDS}")
     cin = calibrator.in_channels
     if kind == "raw":
-        if FORMS[mflag] != FORM_RGB:
-            raise ValueError(f"MFLAG {mflag}: raw RGGB frames feed the denoise / demosaic nets (MFLAG 3, 4)")
+        if mflag not in RAW_MFLAGS:
+            raise ValueError(f"MFLAG {mflag}: raw RGGB frames feed the denoise / demosaic nets (MFLAG 1, 2, 3, 4)")
         if cin != 3:
             raise ValueError(f"a raw RGGB frame feeds 3-channel nets; this one takes {cin}")
     if kind == "image":
@@ -224,7 +264,7 @@ def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32",
 def _evaluate(engine, mflag: int, pairs, step):
     """The loop of evaluate, evaluate_raw and evaluate_image: per (input, gt) of `pairs`, step(input, gt, fp32) runs the forward and
     returns (prediction, device fp32 gt).  MFLAG 6 scores the anchored fp32 output (fp32 True), every other MFLAG the int8 output
-    in the net's output domain.  One synchronisation at the end; a host float64 array (frames, 3) of (mse, psnr, ssim)."""
+    in the net's output domain (MFLAG 1: its Bayer mosaic).  One synchronisation at the end; a host float64 array (frames, 3) of (mse, psnr, ssim)."""
     import torch
     form = form_of(mflag)
     if form == FORM_X2 and not getattr(engine, "anchor_add", False):
@@ -246,7 +286,7 @@ def evaluate(engine, frames, gts, mflag: int):
     """The reference's dataset loop on the device: per frame a forward and its metrics; one synchronisation at the end.
 
     frames: iterable of (1, Cin, H, W) float32 input frames (or one (N, Cin, H, W) tensor, taken frame by frame); gts: the matching
-    ground truths of the output shape.  MFLAG 3 / 4 / 5: the forward writes only the int8 output, which is scored in the net's output
+    ground truths of the output shape.  MFLAG 1 ... 5: the forward writes only the int8 output, which is scored in the net's output
     domain (bundle.scale[L], bundle.zero[L]).  MFLAG 6: the forward writes only the anchored float output; the engine must have
     been created with anchor_add=True.  Returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
     import torch
@@ -262,7 +302,7 @@ def evaluate(engine, frames, gts, mflag: int):
 
 
 def evaluate_raw(engine, raws, gts_u16, mflag: int):
-    """The reference's MFLAG 3 / 4 loop from raw frames to scores (test.py:30-55 with self_dataset.py TestDataset): per frame the
+    """The reference's MFLAG 1 ... 4 loop from raw frames to scores (test.py:30-55 with self_dataset.py TestDataset): per frame the
     12-bit RGGB raw frame is unpacked on the device into the net's q0 and run forward (Engine.forward_raw), its 16-bit RGB ground
     truth is mapped to / 4095 and clamped on the device (sesrq.raw.load_gt), and the int8 output is scored as evaluate() scores it.
 
@@ -272,8 +312,9 @@ def evaluate_raw(engine, raws, gts_u16, mflag: int):
     import numpy as np
     import torch
     from . import raw as rawmod
-    if form_of(mflag) != FORM_RGB:
-        raise ValueError(f"MFLAG {mflag}: raw RGGB frames feed the denoise / demosaic nets (MFLAG 3, 4)")
+    form_of(mflag)
+    if mflag not in RAW_MFLAGS:
+        raise ValueError(f"MFLAG {mflag}: raw RGGB frames feed the denoise / demosaic nets (MFLAG 1, 2, 3, 4)")
     dev = engine.device
 
     def step(r, g, fp32):

@@ -1,7 +1,7 @@
 """Integer-inference entry point -- the counterpart of the reference's ``sim.py``.
 
 Behaviour reproduced (reference sim.py:29-114, :197-213): pick the network by ``define.MFLAG``
-(3 = nrdm_3, 5 = SESR x4, 6 = SESR x2), load float weights, ``collapse()``, quantise the weights
+(1 = nr, 2 = dm, 3 = nrdm_3, 5 = SESR x4, 6 = SESR x2), load float weights, ``collapse()``, quantise the weights
 (mode 1), splice the four stage callables around every conv in the reference's order, run ONE
 forward on the frame and print the bit-width banner.  Here the forward is a single fused device
 call; activation domains (input.K.scale / input.K.zero) come from a calibration the reference's
@@ -10,6 +10,7 @@ test.py produced (an ``output_pt`` directory) or from a bundle/fixture file.
     python sim.py --mflag 5 --ckpt x4sesr.pth --calib output_pt --input rand_SR_Input_80x960.pt
     python sim.py --mflag 5 --params tests/golden/sesr_x4.params.npz --input tests/golden/rand_SR_Input_80x960.npy
     python sim.py --mflag 6 --params ... --input LR.png --gt HR.png --save-png SR.png      # 8-bit images (MFLAG 5 / 6)
+    python sim.py --mflag 1 --ckpt nr_G.pth --calib output_pt --input a_132_128.raw --gt gt16.npy     # nr: scored on the Bayer mosaic
 """
 import argparse
 import json
@@ -25,20 +26,21 @@ from myQL.quan_func import (quantize_model_weight, quantize_asymmetrical_by_tens
                             PEs_and_bias_adder, requan_conv2d_output)
 from myQL.quan_classes import NodeInsertMapping, FunctionPackage, NodeInsertMappingElement
 from myQL.graph_modify import insert_before, insert_bias_bypass, insert_after
-from models import sesr_sim, nrdm_3_sim, sesr_arch_sim, nrdm_6
+from models import sesr_sim, nrdm_3_sim, sesr_arch_sim, nrdm_6, nr, dm
 from models import quantize_utils_pt as quantize
 from sesrq.store import STORE
 
 # MFLAG -> net, as the reference's test_float.py:25-48 numbers them.  4 (nrdm_6, 8 convs) has no integer path in the
-# reference: roles generalise by position here, parity unpinned.
-MODELS = {3: nrdm_3_sim.nr, 4: nrdm_6.nr, 5: sesr_sim.sesr, 6: sesr_arch_sim.sesr}
+# reference: roles generalise by position here, parity unpinned.  1 (nr) and 2 (dm) have the class body of nrdm_3: their
+# integer net is the nrdm_3_sim graph with that task's weights and domains.
+MODELS = {1: nr.nr, 2: dm.dm, 3: nrdm_3_sim.nr, 4: nrdm_6.nr, 5: sesr_sim.sesr, 6: sesr_arch_sim.sesr}
 
 
 def float_model(mflag, ckpt=None, params=None):
     """Float net, collapsed.  ckpt: a reference state_dict (.pth, loaded with weights_only=True);
     params: an .npz holding already-collapsed convs Wf{k}/bf{k} (tests/golden/*.params.npz)."""
     if mflag not in MODELS:
-        raise ValueError(f"MFLAG {mflag}: only 3 (nrdm_3), 4 (nrdm_6), 5 (SESR x4) and 6 (SESR x2) have an integer path")
+        raise ValueError(f"MFLAG {mflag}: only 1 (nr), 2 (dm), 3 (nrdm_3), 4 (nrdm_6), 5 (SESR x4) and 6 (SESR x2) have an integer path")
     model = MODELS[mflag]()
     model.train()
     skip_s = load_checkpoint(model, ckpt, mflag) if ckpt is not None else None

@@ -1,10 +1,11 @@
 """Calibration entry point -- the counterpart of the reference's ``test.py`` (:79-113 graph build with
 qmode = 0, :141-183 loop over calibration frames, :185-217 scale/zero derivation).  The reference's
 dataset is private; frames come from ``--frames`` (.npy / .pt, (N,C,H,W) float32, one batch per N), or from ``--input``: what
-sim.py reads -- 12-bit RGGB raw frames (``*.raw``, MFLAG 3 / 4), 8-bit images (``.png``, or uint8 ``.npy`` with ``--image``; MFLAG
+sim.py reads -- 12-bit RGGB raw frames (``*.raw``, MFLAG 1 ... 4), 8-bit images (``.png``, or uint8 ``.npy`` with ``--image``; MFLAG
 5 / 6) or fp32 ``.npy`` / ``.pt`` frames -- decoded on the device and calibrated frame by frame without a host round trip
 (Calibrator.enqueue*).  With ``--gt`` every frame's mode-0 output is scored as the reference's loop scores it (each frame's PSNR, then
-the mean line) before the domains are printed.
+the mean line) before the domains are printed -- not for MFLAG 1 (nr), whose mosaic metric the scored loop does not have: ``--mflag 1``
+calibrates without ``--gt``.
 
     python test.py --mflag 5 --params tests/golden/sesr_x4.params.npz --frames tests/golden/rand_SR_Input_80x960.npy \\
                    --save-bundle x4.bundle.npz
@@ -59,7 +60,7 @@ def main(argv=None):
     ap.add_argument("--params")
     ap.add_argument("--frames", help="(N,C,H,W) float32 frames, .npy / .pt: calibrated on the host-driven pass (without --gt)")
     ap.add_argument("--input", nargs="+", help="dataset frames as sim.py reads them: *.raw 12-bit RGGB frames <name>_<rows>_<cols>.raw "
-                                              "(MFLAG 3 / 4), 8-bit images .png (or uint8 .npy with --image; MFLAG 5 / 6), or fp32 "
+                                              "(MFLAG 1 ... 4), 8-bit images .png (or uint8 .npy with --image; MFLAG 5 / 6), or fp32 "
                                               ".npy / .pt (N,C,H,W); calibrated on the device-resident pass")
     ap.add_argument("--gt", nargs="+", help="ground truths, one per --input file (or one batch .npy / .pt): score every frame's mode-0 "
                                            "output and print its PSNR and the mean line, as the reference's test.py does.  fp32 or "
@@ -198,7 +199,8 @@ def dataset_pass(args, model):
         kind, frames = load_inputs(args.input, args.image)
     cin = next(m for m in model.modules() if isinstance(m, torch.nn.Conv2d)).in_channels
     try:       # the refusals of forward_raw / forward_image, before any device work
-        quality.check_calibration_input(types.SimpleNamespace(in_channels=cin, method=args.method), args.mflag, kind)
+        quality.check_calibration_input(types.SimpleNamespace(in_channels=cin, method=args.method), args.mflag, kind,
+                                        scored=args.gt is not None)
     except ValueError as e:
         raise SystemExit(f"test.py: {e}") from None
     gts = load_gts(args.gt, kind, args.image) if args.gt else None
