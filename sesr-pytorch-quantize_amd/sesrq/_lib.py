@@ -1,5 +1,5 @@
 """ctypes binding of libsesrq.so (C ABI declared in include/sesrq.h), and the host plumbing every binding in the package shares:
-the loader (bind, Library), the stream entry of a launch and the input domain of the front ends.
+the loader (bind, Library), the stream entry of a launch, the host-array conversion and the input domain of the front ends.
 
 The library is the product: if it is missing or a symbol cannot be resolved this module
 raises immediately -- there is no CPU or PyTorch fallback anywhere in the package.
@@ -232,6 +232,13 @@ def enter_stream(device, stream, *tensors):
         if t is not None:
             t.record_stream(stream)
     return stream
+
+
+def host_tensor(a):
+    """A numpy array as a torch tensor over its (contiguous) bytes; anything else as it is."""
+    import numpy as np
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
 
 
 def input_domain(engine_or_bundle, want_q: bool, who: str):

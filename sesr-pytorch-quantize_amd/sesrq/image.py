@@ -174,7 +174,7 @@ def load_gt(img_u8, mflag: int, device=None, order: str = "rgb"):
     (N, C, H, W) frame quality.score takes -- the reference's gt (self_dataset_sr.py: MFLAG 5 the clipped float64 luma, MFLAG 6
     clip(HR / 255.)), uploaded at 3 B/px and formed on the device."""
     import torch
-    g = torch.from_numpy(np.ascontiguousarray(img_u8)) if isinstance(img_u8, np.ndarray) else img_u8
+    g = _lib.host_tensor(img_u8)
     if not isinstance(g, torch.Tensor) or g.dtype != torch.uint8:
         raise ValueError("load_gt: the ground truth must be a uint8 image array or tensor")
     dev = torch.device(device) if device is not None else (g.device if g.device.type == "cuda" else

@@ -98,13 +98,10 @@ def form_of(mflag: int) -> int:
     return FORMS[mflag]
 
 
-def score(pred, gt, mflag: int, scale=None, zero=None, stream=None):
-    """(mse, psnr, ssim) per frame as a device float64 tensor of shape (N, 3), enqueued on `stream` (default: current), not synchronised.
-
-    pred: (N, C, H, W) float32 output frames, or int8 output frames with the net's output domain (scale = f32(input.L.scale),
-    zero = zero[L]), dequantised on the device to the bits of the float output; gt: float32 of the same shape and device.
-    For MFLAG 6, pred is the anchored float output (Engine(..., anchor_add=True)).  MFLAG 1 scores the Bayer mosaics of the two
-    3-channel frames (libsesrq_mosaic.so); mse is then the mosaic's, over H W."""
+def _check_pair(pred, gt, mflag: int, scale=None, zero=None):
+    """The refusals every scorer shares: pred and gt are (N, C, H, W) tensors of one shape on one HIP device, of the MFLAG's channel
+    count, at least one frame of at least 7x7, gt float32.  Returns ((N, C, H, W), (pred_dtype, pred_scale, pred_zero)); an int8
+    prediction takes its domain from `scale` and `zero`."""
     import torch
     form = form_of(mflag)
     if not isinstance(pred, torch.Tensor) or not isinstance(gt, torch.Tensor):
@@ -122,35 +119,47 @@ def score(pred, gt, mflag: int, scale=None, zero=None, stream=None):
         raise ValueError(f"pred ({pred.device}) and gt ({gt.device}) must be on one HIP device")
     if gt.dtype != torch.float32:
         raise ValueError("gt must be float32")
-    dtype, pscale, pzero = PRED_F32, 0.0, 0
+    domain = PRED_F32, 0.0, 0
     if pred.dtype == torch.int8:
         if scale is None or zero is None:
             raise ValueError("an int8 prediction needs the output domain: scale and zero")
         if form == FORM_X2:
             raise ValueError("MFLAG 6 scores the anchored float output; the anchor does not exist in the int8 output")
-        dtype, pscale, pzero = PRED_I8, float(scale), int(zero)
+        domain = PRED_I8, float(scale), int(zero)
     elif pred.dtype != torch.float32:
         raise ValueError("pred must be float32 or int8")
-    dev = pred.device
+    return (N, Ch, H, W), domain
+
+
+def _run(so, fn, desc, tensors, dims, stream):
+    """Enqueue scorer `fn` of library `so` on `stream`: `tensors` (made contiguous) are its frames in the order of its arguments,
+    `dims` its frame counts and sizes, which are also those of the library's workspace.  The (N, 3) float64 device result."""
+    import torch
+    dev = tensors[0].device
     with torch.cuda.device(dev):
-        pred, gt = pred.contiguous(), gt.contiguous()
-        out = torch.empty((N, 3), dtype=torch.float64, device=dev)
-        if form == FORM_MOSAIC:
-            md = MosaicDesc(pred_dtype=dtype, pred_scale=pscale, pred_zero=pzero)
-            ws = torch.empty(max(1, mosaic_lib().sesrq_mosaic_workspace_bytes(N, H, W)), dtype=torch.uint8, device=dev)
-            st = _lib.enter_stream(dev, stream, pred, gt, out, ws)
-            if mosaic_lib().sesrq_mosaic_score(C.byref(md), pred.data_ptr(), gt.data_ptr(), N, H, W, out.data_ptr(), ws.data_ptr(),
-                                               ws.numel(), st.cuda_stream) != 0:
-                raise ValueError("sesrq_mosaic_score: " + mosaic_last_error())
-            return out
-        d = EvalDesc(form=form, pred_dtype=dtype, pred_scale=pscale, pred_zero=pzero)
-        ws = torch.empty(max(1, lib().sesrq_eval_workspace_bytes(N, Ch, H, W)), dtype=torch.uint8, device=dev)
-        st = _lib.enter_stream(dev, stream, pred, gt, out, ws)
-        rc = lib().sesrq_eval(C.byref(d), pred.data_ptr(), gt.data_ptr(), N, Ch, H, W, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                              st.cuda_stream)
+        tensors = [t.contiguous() for t in tensors]
+        out = torch.empty((dims[0], 3), dtype=torch.float64, device=dev)
+        ws = torch.empty(max(1, getattr(so.lib(), so.prefix + "_workspace_bytes")(*dims)), dtype=torch.uint8, device=dev)
+        st = _lib.enter_stream(dev, stream, *tensors, out, ws)
+        rc = fn(C.byref(desc), *(t.data_ptr() for t in tensors), *dims, out.data_ptr(), ws.data_ptr(), ws.numel(), st.cuda_stream)
     if rc != 0:
-        raise ValueError("sesrq_eval: " + last_error())
+        raise ValueError(f"{fn.__name__}: " + so.last_error())
     return out
+
+
+def score(pred, gt, mflag: int, scale=None, zero=None, stream=None):
+    """(mse, psnr, ssim) per frame as a device float64 tensor of shape (N, 3), enqueued on `stream` (default: current), not synchronised.
+
+    pred: (N, C, H, W) float32 output frames, or int8 output frames with the net's output domain (scale = f32(input.L.scale),
+    zero = zero[L]), dequantised on the device to the bits of the float output; gt: float32 of the same shape and device.
+    For MFLAG 6, pred is the anchored float output (Engine(..., anchor_add=True)).  MFLAG 1 scores the Bayer mosaics of the two
+    3-channel frames (libsesrq_mosaic.so); mse is then the mosaic's, over H W."""
+    (N, Ch, H, W), (dtype, pscale, pzero) = _check_pair(pred, gt, mflag, scale, zero)
+    if FORMS[mflag] == FORM_MOSAIC:
+        md = MosaicDesc(pred_dtype=dtype, pred_scale=pscale, pred_zero=pzero)
+        return _run(_mosaic_so, mosaic_lib().sesrq_mosaic_score, md, (pred, gt), (N, H, W), stream)
+    d = EvalDesc(form=FORMS[mflag], pred_dtype=dtype, pred_scale=pscale, pred_zero=pzero)
+    return _run(_so, lib().sesrq_eval, d, (pred, gt), (N, Ch, H, W), stream)
 
 
 def score_anchored(pred, lr, gt, stream=None):
@@ -158,32 +167,16 @@ def score_anchored(pred, lr, gt, stream=None):
     anchor, such as the calibration pass's mode-0 output --, lr (N, 3, H, W) float32, the net's input, gt (N, 3, 2H, 2W) float32, all on
     one device.  The bits of score(pred + up2(lr), gt, 6).  A device float64 (N, 3) tensor of (mse, psnr, ssim), not synchronised."""
     import torch
-    for name, t in (("pred", pred), ("lr", lr), ("gt", gt)):
+    for name, t in (("pred", pred), ("lr", lr)):
         if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.dtype != torch.float32:
             raise ValueError(f"{name} must be a (N, C, H, W) float32 tensor")
-    if tuple(pred.shape) != tuple(gt.shape):
-        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have one shape")
-    N, Ch, H, W = pred.shape
+    (N, Ch, H, W), _ = _check_pair(pred, gt, 6)
     if tuple(lr.shape) != (N, Ch, H // 2, W // 2) or H % 2 or W % 2:
         raise ValueError(f"lr {tuple(lr.shape)} is not the half-size input of a {tuple(pred.shape)} prediction")
-    if Ch != CHANNELS[FORM_X2]:
-        raise ValueError(f"MFLAG 6 scores 3-channel frames, got {Ch}")
-    if H < 7 or W < 7:
-        raise ValueError(f"frame {H}x{W} is smaller than the 7x7 SSIM window")
-    if pred.device.type != "cuda" or gt.device != pred.device or lr.device != pred.device:
+    if lr.device != pred.device:
         raise ValueError("pred, lr and gt must be on one HIP device")
     d = EvalDesc(form=FORM_X2, pred_dtype=PRED_F32, pred_scale=0.0, pred_zero=0)
-    dev = pred.device
-    with torch.cuda.device(dev):
-        pred, lr, gt = pred.contiguous(), lr.contiguous(), gt.contiguous()
-        out = torch.empty((N, 3), dtype=torch.float64, device=dev)
-        ws = torch.empty(max(1, lib().sesrq_eval_workspace_bytes(N, Ch, H, W)), dtype=torch.uint8, device=dev)
-        st = _lib.enter_stream(dev, stream, pred, lr, gt, out, ws)
-        rc = anchored_lib().sesrq_eval_anchored(C.byref(d), pred.data_ptr(), lr.data_ptr(), gt.data_ptr(), N, Ch, H, W, out.data_ptr(),
-                                       ws.data_ptr(), ws.numel(), st.cuda_stream)
-    if rc != 0:
-        raise ValueError("sesrq_eval_anchored: " + last_error())
-    return out
+    return _run(_so, anchored_lib().sesrq_eval_anchored, d, (pred, lr, gt), (N, Ch, H, W), stream)
 
 
 KINDS = ("f32", "raw", "image")
@@ -227,24 +220,20 @@ def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32",
     frames of the output shape, uint16 RGB frames (3, H, W) / (1, 3, H, W) (sesrq.raw.load_gt), or uint8 HR images in `order`
     (sesrq.image.load_gt).
     Returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
-    import numpy as np
     import torch
     check_calibration_input(calibrator, mflag, kind)
     dev = calibrator.device
     form = FORMS[mflag]
-
-    def host(t):
-        return torch.from_numpy(np.ascontiguousarray(t)) if isinstance(t, np.ndarray) else t
     rows = []
     for x, g in zip(frames, gts):
-        x = host(x).to(dev, non_blocking=True)
+        x = _lib.host_tensor(x).to(dev, non_blocking=True)
         if kind == "f32":
             y = calibrator.enqueue(x.float() if x.dim() == 4 else x.float().unsqueeze(0))
         elif kind == "raw":
             y = calibrator.enqueue_raw(x)
         else:
             y = calibrator.enqueue_image(x, order=order)
-        g = host(g)
+        g = _lib.host_tensor(g)
         if g.dtype == torch.uint8:           # an 8-bit HR image: the reference's gt formed on the device
             from . import image as imgmod
             g = imgmod.load_gt(g, mflag, dev, order=order)
@@ -309,8 +298,6 @@ def evaluate_raw(engine, raws, gts_u16, mflag: int):
     raws: iterable of (1, 1, H, W) / (1, H, W) / (H, W) uint16 frames (numpy or torch; uploaded at 2 B/px), or one (N, 1, H, W)
     tensor taken frame by frame; gts_u16: the matching (3, H, W) / (1, 3, H, W) uint16 RGB frames.  One synchronisation at the end;
     returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
-    import numpy as np
-    import torch
     from . import raw as rawmod
     form_of(mflag)
     if mflag not in RAW_MFLAGS:
@@ -318,8 +305,7 @@ def evaluate_raw(engine, raws, gts_u16, mflag: int):
     dev = engine.device
 
     def step(r, g, fp32):
-        r = torch.from_numpy(np.ascontiguousarray(r)) if isinstance(r, np.ndarray) else r
-        q, _ = engine.forward_raw(r.to(dev, non_blocking=True), want_q=True, want_f=False)
+        q, _ = engine.forward_raw(_lib.host_tensor(r).to(dev, non_blocking=True), want_q=True, want_f=False)
         return q, rawmod.load_gt(g, dev)
     return _evaluate(engine, mflag, zip(raws, gts_u16), step)
 
@@ -332,16 +318,13 @@ def evaluate_image(engine, lr_imgs, hr_imgs, mflag: int, order: str = "rgb"):
 
     lr_imgs / hr_imgs: iterables of (H, W, 3) / (1, H, W, 3) uint8 images (numpy or torch), in `order`.  One synchronisation at the
     end; returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
-    import numpy as np
-    import torch
     from . import image as imgmod
     form_of(mflag)
     imgmod.form_of(mflag)
     dev = engine.device
 
     def step(lr, hr, fp32):
-        lr = torch.from_numpy(np.ascontiguousarray(lr)) if isinstance(lr, np.ndarray) else lr
-        lr = lr.to(dev, non_blocking=True)
+        lr = _lib.host_tensor(lr).to(dev, non_blocking=True)
         g = imgmod.load_gt(hr, mflag, dev, order=order)
         q, y = engine.forward_image(lr, order=order, want_q=not fp32, want_f=fp32)
         return (y if fp32 else q), g

@@ -80,7 +80,7 @@ def load_gt(array_u16, device=None):
     = clamp(fl32(v) / 4095, 0, 1), the reference's true fp32 quotient (self_dataset.py:235-243): codes are uploaded at 2 B/px and mapped
     on the device through the 4096 quotients formed on the host (a GPU tensor / scalar division would multiply by fl(1 / 4095))."""
     import torch
-    g = torch.from_numpy(np.ascontiguousarray(array_u16)) if isinstance(array_u16, np.ndarray) else array_u16
+    g = _lib.host_tensor(array_u16)
     if not isinstance(g, torch.Tensor) or g.dtype != torch.uint16:
         raise ValueError("load_gt: the ground truth must be a uint16 array or tensor")
     if g.dim() == 3:

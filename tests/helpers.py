@@ -78,6 +78,35 @@ def pass_equals(what, cal, want):
     assert cal.last_scale == want.last_scale and cal.last_zero == want.last_zero, (what, cal.last_zero, want.last_zero)
 
 
+# ---------------------------------------------------------------------------------------------------- the PSNR / SSIM scorers
+OW, RH, PAD = 248, 32, 3                    # csrc/sesrq_eval_tile.h (SSIM columns / rows of a tile, window radius)
+
+
+def nbx(W):
+    return -(-(W - 2 * PAD) // OW)          # csrc/sesrq_eval_tile.h geometry()
+
+
+def nby(H):
+    return -(-(H - 2 * PAD) // RH)
+
+
+def score(pred, gt, mflag, **kw):
+    """sesrq.quality.score of fresh device copies of the frames (the shared ones are read-only), as a host array."""
+    import torch
+    from sesrq import quality
+    res = quality.score(to_device(pred), to_device(gt), mflag, **kw)
+    torch.cuda.synchronize()
+    return res.cpu().numpy()
+
+
+def score_anchored(pred, lr, gt):
+    import torch
+    from sesrq import quality
+    res = quality.score_anchored(to_device(pred), to_device(lr), to_device(gt))
+    torch.cuda.synchronize()
+    return res.cpu().numpy()
+
+
 # ---------------------------------------------------------------------------------------------------- 12-bit RGGB raw frames
 def raw_frames():
     return np.load(os.path.join(GOLDEN, "raw", "frames.npz"), allow_pickle=False)

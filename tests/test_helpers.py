@@ -1,9 +1,9 @@
 """The shared comparator of the suite (tests/helpers.py::same), pinned on the CPU: a comparator that passes silently hides every
-failure behind it."""
+failure behind it.  And the tile counts the quality tests reason with, against the geometry of csrc/sesrq_eval_tile.h."""
 import numpy as np
 import pytest
 
-from helpers import same, sha256
+from helpers import nbx, nby, same, sha256
 
 
 def _f32(*words):
@@ -103,3 +103,11 @@ def test_sha256_is_of_the_c_ordered_bytes():
     a = np.arange(30, dtype=np.int16).reshape(5, 6)
     assert sha256(a) == sha256(a.copy()) == hashlib.sha256(a.tobytes()).hexdigest()
     assert sha256(a.T) == hashlib.sha256(np.ascontiguousarray(a.T).tobytes()).hexdigest() != sha256(a)
+
+
+def test_tile_counts_on_each_side_of_every_seam():
+    """geometry() of csrc/sesrq_eval_tile.h: a tile gives 248 SSIM columns x 32 SSIM rows, a frame H - 6 rows of W - 6 columns."""
+    for W, want in ((7, 1), (254, 1), (255, 2), (502, 2)):
+        assert nbx(W) == (W - 6 + 247) // 248 == want, W
+    for H, want in ((7, 1), (38, 1), (39, 2), (70, 2)):
+        assert nby(H) == (H - 6 + 31) // 32 == want, H

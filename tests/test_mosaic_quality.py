@@ -11,6 +11,7 @@ Shapes are the smallest at which each mechanism is live: the tile seams of tests
 steps and the last tile owns one SSIM column; H 38 / 39 and 70 / 71 likewise for rows), 7x7 / 7x8 / 8x7 (one window, both parities of
 the last row and column), and W % 4 == 0 beside W % 4 != 0 (the 16-byte and the per-element loads)."""
 import ctypes as C
+import functools
 import json
 import os
 import re
@@ -20,12 +21,12 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
-from helpers import Arena, device, stream_ptr
+from helpers import Arena, OW, PAD, RH, device, nbx, nby, score, stream_ptr, to_device as _dev
 import image_oracle as IO
 import mosaic_oracle as M
 import quality_oracle as Q
 from test_quality import _check
-from test_quality_seams import DY_SCALE, OW, PAD, RH, SCALE, TOL_SSIM, ZERO, _offset_view, frames, nbx, nby
+from test_quality_seams import DY_SCALE, SCALE, TOL_SSIM, ZERO, _offset_view, frames
 
 F32 = np.float32
 HEADER = os.path.join(ROOT, "include", "sesrq_mosaic.h")
@@ -163,17 +164,7 @@ def test_score_mflag_1_refusals_on_the_host():
 
 
 # ------------------------------------------------------------------------------------------------------------------------ GPU
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.array(a, order="C", copy=True)).to(device())
-
-
-def _score(pred, gt, mflag=1, **kw):
-    import torch
-    from sesrq import quality
-    res = quality.score(_dev(pred), _dev(gt), mflag, **kw)
-    torch.cuda.synchronize()
-    return res.cpu().numpy()
+_score = functools.partial(score, mflag=1)
 
 
 def _gathered(pred, gt, **kw):

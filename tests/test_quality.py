@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, load_fixture, fixture_input
-from helpers import device
+from helpers import device, score as _score
 import quality_oracle as Q
 
 CSRC = os.path.join(ROOT, "sesr-pytorch-quantize_amd", "csrc")
@@ -152,14 +152,6 @@ def test_score_refuses_bad_arguments_on_the_host():
 
 
 # ------------------------------------------------------------------------------------------------------------------------ GPU
-def _score(pred, gt, mflag, **kw):
-    import torch
-    from sesrq import quality
-    res = quality.score(torch.as_tensor(pred).to(device()), torch.as_tensor(gt).to(device()), mflag, **kw)
-    torch.cuda.synchronize()
-    return res.cpu().numpy()
-
-
 def _check(got, want_psnr, want_ssim, what):
     for n in range(len(want_psnr)):
         if np.isinf(want_psnr[n]):

@@ -22,12 +22,11 @@ import pytest
 
 import image_oracle as IO
 import quality_oracle as Q
-from helpers import device
+from helpers import OW, PAD, RH, device, nbx, nby, score as _score, score_anchored as _score_anchored, to_device as _dev
 from test_quality import _check, _ssim_scipy
 
 F32 = np.float32
 TOL_SSIM = 1e-6                             # test_quality._check
-OW, RH, PAD = 248, 32, 3                    # csrc/sesrq_eval.hip:30-32 (SSIM columns / rows of a tile, window radius)
 SCALE, ZERO = float(F32(1.0 / 220.0)), -110  # the int8 output domain of tests/golden/quality (make_quality_golden.py:24)
 DY_SCALE = 1.0 / 256.0                      # int8 domain of the k/256 frames: (q + 110) / 256 is on the grid
 
@@ -48,14 +47,6 @@ SEEDS = {(7, 256): 2, (7, 258): 2, (7, 503): 8, (7, 504): 1, (39, 253): 1, (39, 
          (39, 504): 8,
          (40, 255): 1, (70, 255): 2, (71, 255): 23}
 A_SEEDS = {(8, 504): 5, (38, 256): 1, (40, 258): 1, (40, 504): 1}
-
-
-def nbx(W):
-    return -(-(W - 2 * PAD) // OW)          # csrc/sesrq_eval.hip geometry()
-
-
-def nby(H):
-    return -(-(H - 2 * PAD) // RH)
 
 
 def _ro(**kw):
@@ -363,27 +354,6 @@ def test_oracle_propagates_nan_like_np_clip():
 
 
 # ------------------------------------------------------------------------------------------------------------------------ GPU
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.array(a, order="C", copy=True)).to(device())       # the shared frames are read-only
-
-
-def _score(pred, gt, mflag, **kw):
-    import torch
-    from sesrq import quality
-    res = quality.score(_dev(pred), _dev(gt), mflag, **kw)
-    torch.cuda.synchronize()
-    return res.cpu().numpy()
-
-
-def _score_anchored(pred, lr, gt):
-    import torch
-    from sesrq import quality
-    res = quality.score_anchored(_dev(pred), _dev(lr), _dev(gt))
-    torch.cuda.synchronize()
-    return res.cpu().numpy()
-
-
 def _crossed_both_seams(ran):
     assert any(nbx(W) >= 2 for _, W in ran) and any(nby(H) >= 2 for H, _ in ran) and any(nbx(W) >= 3 for _, W in ran) \
         and any(nby(H) >= 3 for H, _ in ran), ran
