@@ -332,7 +332,7 @@ class Engine:
     __call__ = forward
 
     def forward_raw(self, raw: torch.Tensor, want_q: bool = True, want_f: bool = True, out_q=None, out_f=None, stream=None,
-                    slot: int = 0):
+                    slot: int = 0, fmt=None, stride=None, width=None):
         """raw: (N, 1, H, W) or (N, H, W) torch.uint16 12-bit RGGB frames on self.device -> (q int8 | None, y float32 | None).
 
         The frames are unpacked on the device (libsesrq_raw.so, sesrq.raw) into this net's q0 -- a per-(N, H, W, slot) buffer the
@@ -340,7 +340,11 @@ class Engine:
         fp32 input frame (self_dataset.py TestDataset).  Both launches go to `stream` (default: current), ordered as forward() orders
         them; give concurrent in-flight frames different slots.  Only for nets with 3 input channels whose int8 input is q0 (no
         `upstream`) and without the fp32 anchor.  A net narrower than 8 bits takes the unpack's fp32 frame and the fp32 forward (the
-        unpack's q0 is 8-bit): the same bits as forward() on that frame."""
+        unpack's q0 is 8-bit): the same bits as forward() on that frame.
+
+        fmt: a sesrq.sensor.Format -- the frames are in that sensor format (any CFA order and levels; torch.uint16, or torch.uint8
+        rows of MIPI RAW10 / RAW12; `stride` and `width` as sesrq.sensor.frames takes them) and libsesrq_sensor.so unpacks them.
+        Without it nothing changes: 12-bit RGGB through libsesrq_raw.so."""
         from . import raw as rawmod
         if self.bundle.in_channels != 3:
             raise ValueError(f"forward_raw: a raw RGGB frame feeds 3-channel nets; this one takes {self.bundle.in_channels}")
@@ -350,13 +354,24 @@ class Engine:
             raise ValueError("forward_raw: anchor_add needs the fp32 input frame; use raw.unpack(..., want_spread=True) and forward()")
         if not (want_q or want_f):
             raise ValueError("forward_raw: ask for the int8 output, the fp32 output or both")
-        raw = rawmod._frames(raw, self.device)
-        N, H, W = raw.shape
         narrow = self.quan_bits != 8       # the buffer holds q0, or the fp32 frame of a narrow net
+        if fmt is None:
+            if stride is not None or width is not None:
+                raise ValueError("forward_raw: stride and width belong to a sensor format (fmt=...)")
+            raw = rawmod._frames(raw, self.device)
+            N, H, W = raw.shape
 
-        def unpack(src, buf, st):
-            rawmod.launch(self.device, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, src, None if narrow else buf,
-                          buf if narrow else None, st)
+            def unpack(src, buf, st):
+                rawmod.launch(self.device, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, src, None if narrow else buf,
+                              buf if narrow else None, st)
+        else:
+            from . import sensor
+            raw, W, S = sensor.frames(raw, fmt, self.device, stride, width)
+            N, H = raw.shape[0], raw.shape[1]
+
+            def unpack(src, buf, st):
+                sensor.launch(self.device, fmt, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, src, W, S,
+                              None if narrow else buf, buf if narrow else None, st)
         return self._run(raw, _lib.F32 if narrow else _lib.I8, want_q, want_f, out_q if want_q else None, out_f if want_f else None,
                          stream, slot, (N, 3, H, W), unpack)
 

@@ -182,6 +182,13 @@ def score_anchored(pred, lr, gt, stream=None):
 KINDS = ("f32", "raw", "image")
 
 
+def check_mosaic_format(mflag: int, fmt):
+    """The MFLAG 1 metric selects channel (r & 1) + (c & 1) of every pixel, which is the RGGB mosaic: with a sensor format of another
+    CFA order it would score the wrong sites, so it is refused ("Not covered": a CFA-aware mosaic metric)."""
+    if fmt is not None and mflag in FORMS and FORMS[mflag] == FORM_MOSAIC and fmt.cfa != "rggb":
+        raise ValueError(f"MFLAG {mflag}: the mosaic metric scores the RGGB sites; a {fmt.cfa} frame cannot be scored with it")
+
+
 def check_calibration_input(calibrator, mflag: int, kind: str, scored: bool = True):
     """The refusals of evaluate_calibration, before any device work: the input kind must fit the MFLAG (raw frames: 1 ... 4, images:
     5 / 6) and the net's input channels, and the calibrator must be on the min/max rule (the device pass has no entropy variant).
@@ -209,7 +216,7 @@ def check_calibration_input(calibrator, mflag: int, kind: str, scored: bool = Tr
                          "method='entropy' runs on the host pass (Calibrator.observe)")
 
 
-def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32", order: str = "rgb"):
+def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32", order: str = "rgb", fmt=None):
     """The reference's calibration loop (test.py:141-183) on the device: per frame the mode-0 forward (Calibrator.enqueue /
     enqueue_raw / enqueue_image, which also accumulates the running ranges) and the metrics of its output in the form the MFLAG uses
     -- MFLAG 6 the anchored output fl32(gfake + up2(inps)), formed inside the scoring kernel (score_anchored).  One synchronisation at
@@ -218,10 +225,12 @@ def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32",
     kind "f32": frames (1, Cin, H, W) float32 (or one (N, Cin, H, W) tensor, taken frame by frame); "raw": (1, 1, H, W) / (1, H, W) /
     (H, W) uint16 RGGB frames; "image": (H, W, 3) / (1, H, W, 3) uint8 LR images in `order`.  gts, numpy or torch, by dtype: float32
     frames of the output shape, uint16 RGB frames (3, H, W) / (1, 3, H, W) (sesrq.raw.load_gt), or uint8 HR images in `order`
-    (sesrq.image.load_gt).
+    (sesrq.image.load_gt).  fmt: the sesrq.sensor.Format of "raw" frames and uint16 ground truths (default: 12-bit RGGB, sesrq.raw).
     Returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
     import torch
     check_calibration_input(calibrator, mflag, kind)
+    if fmt is not None and kind != "raw":
+        raise ValueError("a sensor format belongs to raw frames (kind='raw')")
     dev = calibrator.device
     form = FORMS[mflag]
     rows = []
@@ -230,7 +239,7 @@ def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32",
         if kind == "f32":
             y = calibrator.enqueue(x.float() if x.dim() == 4 else x.float().unsqueeze(0))
         elif kind == "raw":
-            y = calibrator.enqueue_raw(x)
+            y = calibrator.enqueue_raw(x, fmt=fmt)
         else:
             y = calibrator.enqueue_image(x, order=order)
         g = _lib.host_tensor(g)
@@ -238,8 +247,8 @@ def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32",
             from . import image as imgmod
             g = imgmod.load_gt(g, mflag, dev, order=order)
         elif g.dtype == torch.uint16:        # a 16-bit RGB frame: / 4095, clamped (self_dataset.py:235-243)
-            from . import raw as rawmod
-            g = rawmod.load_gt(g, dev)
+            from . import raw as rawmod, sensor
+            g = rawmod.load_gt(g, dev) if fmt is None else sensor.load_gt(g, fmt, dev)
         else:
             g = (g if g.dim() == 4 else g.unsqueeze(0)).to(dev, dtype=torch.float32, non_blocking=True)
         rows.append(score_anchored(y, calibrator.last_input, g) if form == FORM_X2 else score(y, g, mflag))
@@ -290,23 +299,29 @@ def evaluate(engine, frames, gts, mflag: int):
     return _evaluate(engine, mflag, zip(frames, gts), step)
 
 
-def evaluate_raw(engine, raws, gts_u16, mflag: int):
+def evaluate_raw(engine, raws, gts_u16, mflag: int, fmt=None):
     """The reference's MFLAG 1 ... 4 loop from raw frames to scores (test.py:30-55 with self_dataset.py TestDataset): per frame the
     12-bit RGGB raw frame is unpacked on the device into the net's q0 and run forward (Engine.forward_raw), its 16-bit RGB ground
     truth is mapped to / 4095 and clamped on the device (sesrq.raw.load_gt), and the int8 output is scored as evaluate() scores it.
 
     raws: iterable of (1, 1, H, W) / (1, H, W) / (H, W) uint16 frames (numpy or torch; uploaded at 2 B/px), or one (N, 1, H, W)
     tensor taken frame by frame; gts_u16: the matching (3, H, W) / (1, 3, H, W) uint16 RGB frames.  One synchronisation at the end;
-    returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
+    returns a host float64 array (frames, 3) of (mse, psnr, ssim).
+
+    fmt: a sesrq.sensor.Format -- the frames are unpadded frames of that sensor format (uint16, or uint8 rows of RAW10 / RAW12) and the
+    ground truths are mapped with its levels.  MFLAG 1 scores the RGGB mosaic and refuses every other CFA order."""
     from . import raw as rawmod
     form_of(mflag)
     if mflag not in RAW_MFLAGS:
         raise ValueError(f"MFLAG {mflag}: raw RGGB frames feed the denoise / demosaic nets (MFLAG 1, 2, 3, 4)")
+    check_mosaic_format(mflag, fmt)
     dev = engine.device
+    if fmt is not None:
+        from . import sensor
 
     def step(r, g, fp32):
-        q, _ = engine.forward_raw(_lib.host_tensor(r).to(dev, non_blocking=True), want_q=True, want_f=False)
-        return q, rawmod.load_gt(g, dev)
+        q, _ = engine.forward_raw(_lib.host_tensor(r).to(dev, non_blocking=True), want_q=True, want_f=False, fmt=fmt)
+        return q, rawmod.load_gt(g, dev) if fmt is None else sensor.load_gt(g, fmt, dev)
     return _evaluate(engine, mflag, zip(raws, gts_u16), step)
 
 

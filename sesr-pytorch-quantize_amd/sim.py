@@ -147,7 +147,7 @@ def main(argv=None):
     ap.add_argument("--save", help="write the float result here (.npy)")
     ap.add_argument("--gt", help="ground truth of the output shape (N,Cout,H*r,W*r) float32, .npy or .pt: score the output with the "
                                  "reference's PSNR / SSIM on the device (test.py:141-183) and print them as its loop does; a uint16 "
-                                 "(N,3,H,W) RGB ground truth is taken / 4095 and clamped, as the reference's TestDataset does; an "
+                                 "(N,3,H,W) RGB ground truth is taken / 4095 and clamped, as the reference's TestDataset does (at --black / --white with those levels); an "
                                  "8-bit HR image (.png, or a uint8 .npy with --image) is formed as self_dataset_sr.py forms its gt")
     ap.add_argument("--dump", help="write the parameter store as an output_pt-compatible tree here (what the define.py *_W_FLG "
                                    "switches select, plus weights and activation domains); all dump switches are turned on")
@@ -156,7 +156,15 @@ def main(argv=None):
     ap.add_argument("--engine", choices=("auto", "dot4", "mfma", "mfma-q"), default="auto",
                     help="kernel family of the integer path (sesrq_options.engine).  With --quan-bit below 8, auto, dot4 and mfma run the "
                          "dot4 kernels; mfma-q runs the width-aware MFMA kernels and the fused trio (same bits, several times the rate)")
+    add_sensor_flags(ap)
     args = ap.parse_args(argv)
+    fmt = sensor_format(args, "sim.py", [args.input])
+    if fmt is not None and args.gt:
+        from sesrq import quality
+        try:
+            quality.check_mosaic_format(args.mflag, fmt)
+        except ValueError as e:
+            raise SystemExit(str(e)) from None
     if args.quan_bit is not None:
         define.QUAN_BIT = args.quan_bit
     define.check()
@@ -175,8 +183,11 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("sim.py: the integer path needs a HIP device (no CPU fallback)")
     if args.input.endswith(".raw"):         # the reference's loop: raw frame -> sparse RGGB mosaic / 4095, clamped -> model(inps)
-        from sesrq import raw
-        _, inps = raw.unpack(None, torch.from_numpy(raw.load_raw(args.input)).cuda(), want_q=False, want_spread=True)
+        from sesrq import raw, sensor
+        if fmt is None:
+            _, inps = raw.unpack(None, torch.from_numpy(raw.load_raw(args.input)).cuda(), want_q=False, want_spread=True)
+        else:                               # a sensor's format: CFA order, levels, MIPI packing (sesrq.sensor)
+            _, inps = sensor.unpack(None, torch.from_numpy(sensor.load_raw(args.input, fmt)).cuda(), fmt, want_q=False, want_spread=True)
     elif as_image:                          # self_dataset_sr.py: uint8 LR image / 255 (MFLAG 5: the float64 luma) -> model(inps)
         from sesrq import image
         form = image.form_of(args.mflag)
@@ -196,10 +207,36 @@ def main(argv=None):
         if is_image(args.gt, args.image):   # the HR image: the reference's gt formed on the device
             from sesrq import image
             gts = image.load_gt(image.load_image(args.gt), args.mflag, gfake.device, order=args.order)
-        score_against(args.gt, gfake, inps, args.mflag, gts=gts)
+        score_against(args.gt, gfake, inps, args.mflag, gts=gts, fmt=fmt)
     if args.save_png:
         save_png(args.save_png, gfake, inps, args.mflag)
     return gfake
+
+
+def add_sensor_flags(ap):
+    """--cfa / --black / --white / --packing: the sensor format of *.raw inputs (sesrq.sensor.Format).  Without any of them a raw
+    frame is the reference's dataset format (uint16, RGGB, black 0, white 4095) and takes the route it always took."""
+    ap.add_argument("--cfa", choices=("rggb", "grbg", "gbrg", "bggr"), default=None, help="CFA order of *.raw inputs (default rggb)")
+    ap.add_argument("--black", type=int, default=None, help="black level of *.raw inputs (default 0)")
+    ap.add_argument("--white", type=int, default=None, help="white level of *.raw inputs and uint16 ground truths (default 4095)")
+    ap.add_argument("--packing", choices=("u16", "raw10", "raw12"), default=None,
+                    help="how *.raw inputs hold their pixels: uint16 containers (default), MIPI RAW10 (4 px in 5 bytes) or RAW12 "
+                         "(2 px in 3 bytes); a file is <rows> x the unpadded row bytes")
+
+
+def sensor_format(args, who, inputs):
+    """The sesrq.sensor.Format the sensor flags describe, or None when none is given; a flag error ends the program."""
+    given = {k: v for k, v in (("cfa", args.cfa), ("black", args.black), ("white", args.white), ("packing", args.packing))
+             if v is not None}
+    if not given:
+        return None
+    if not inputs or not all(p.endswith(".raw") for p in inputs):
+        raise SystemExit(f"{who}: --cfa, --black, --white and --packing describe *.raw inputs")
+    from sesrq import sensor
+    try:
+        return sensor.Format(**given)
+    except ValueError as e:
+        raise SystemExit(f"{who}: {e}") from None
 
 
 def is_image(path, image_flag):
@@ -229,7 +266,7 @@ def load_frames(path):
     return torch.load(path, weights_only=True, map_location="cpu") if path.endswith(".pt") else torch.from_numpy(np.load(path))
 
 
-def score_against(path, gfake, inps, mflag, gts=None):
+def score_against(path, gfake, inps, mflag, gts=None, fmt=None):
     """The reference's evaluation loop (test.py:141-183) on the device: anchor for MFLAG 6, clip, PSNR / SSIM per frame; prints each
     frame's PSNR and the mean line.  gts: the ground truth already formed (an 8-bit HR image's), else read from `path`.  Returns the
     (N, 3) float64 host array of (mse, psnr, ssim)."""
@@ -239,8 +276,8 @@ def score_against(path, gfake, inps, mflag, gts=None):
     if tuple(gts.shape) != tuple(gfake.shape):
         raise SystemExit(f"sim.py: --gt has shape {tuple(gts.shape)}, the output is {tuple(gfake.shape)}")
     if gts.dtype == torch.uint16:                   # 16-bit RGB ground truth: / 4095, clamped (self_dataset.py:235-243)
-        from sesrq import raw
-        gts = raw.load_gt(gts, gfake.device)
+        from sesrq import raw, sensor
+        gts = raw.load_gt(gts, gfake.device) if fmt is None else sensor.load_gt(gts, fmt, gfake.device)
     pred = anchored(gfake, inps, mflag)             # test.py:149-155: MFLAG 6 + the nearest-upsampled input
     res = quality.score(pred, gts.float().to(gfake.device), mflag).cpu().numpy()
     totalpsnr = totalssim = 0.0

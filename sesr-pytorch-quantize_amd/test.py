@@ -83,7 +83,9 @@ def main(argv=None):
                     help="merge the long skip through the QAT nets' QuantAdd at scale S (positive, finite): for --params files, which "
                          "carry no QuantAdd state; a QAT --ckpt gives its own")
     ap.add_argument("--float-skip", action="store_true", help="add the long skip in float even for a QAT checkpoint")
+    sim.add_sensor_flags(ap)
     args = ap.parse_args(argv)
+    args.fmt = sim.sensor_format(args, "test.py", args.input)
     if args.quan_bit is not None:
         define.QUAN_BIT = args.quan_bit
     define.check()
@@ -155,7 +157,7 @@ def _frames_of(a, image):
     return [a[i] if image else a[i:i + 1] for i in range(a.shape[0])]
 
 
-def load_inputs(paths, image_flag):
+def load_inputs(paths, image_flag, fmt=None):
     """(kind, [host frame]) of the --input files: "raw" (H, W) uint16, "image" (H, W, 3) uint8, "f32" (1, C, H, W) float32."""
     kinds = {"raw" if p.endswith(".raw") else "image" if sim.is_image(p, image_flag) else "f32" for p in paths}
     if len(kinds) != 1:
@@ -164,8 +166,8 @@ def load_inputs(paths, image_flag):
     frames = []
     for p in paths:
         if kind == "raw":
-            from sesrq import raw
-            frames.append(raw.load_raw(p))
+            from sesrq import raw, sensor
+            frames.append(raw.load_raw(p) if fmt is None else sensor.load_raw(p, fmt))
         elif kind == "image":
             from sesrq import image
             frames += _frames_of(image.load_image(p), True)
@@ -196,7 +198,7 @@ def dataset_pass(args, model):
     if args.frames is not None:
         kind, frames = "f32", [f.astype(np.float32) for f in _frames_of(sim.load_frames(args.frames), False)]
     else:
-        kind, frames = load_inputs(args.input, args.image)
+        kind, frames = load_inputs(args.input, args.image, args.fmt)
     cin = next(m for m in model.modules() if isinstance(m, torch.nn.Conv2d)).in_channels
     try:       # the refusals of forward_raw / forward_image, before any device work
         quality.check_calibration_input(types.SimpleNamespace(in_channels=cin, method=args.method), args.mflag, kind,
@@ -212,7 +214,7 @@ def dataset_pass(args, model):
     cal = lower_calibration(model, dev)
     model.__dict__["_sesrq_cal"] = cal
     if gts is not None:
-        res = quality.evaluate_calibration(cal, frames, gts, args.mflag, kind=kind, order=args.order)
+        res = quality.evaluate_calibration(cal, frames, gts, args.mflag, kind=kind, order=args.order, fmt=args.fmt)
         totalpsnr = totalssim = 0.0
         for _, psnr, ssim in res:
             print(float(psnr))
@@ -223,7 +225,7 @@ def dataset_pass(args, model):
         for f in frames:
             t = torch.from_numpy(np.ascontiguousarray(f)).to(dev)
             if kind == "raw":
-                cal.enqueue_raw(t)
+                cal.enqueue_raw(t, fmt=args.fmt)
             elif kind == "image":
                 cal.enqueue_image(t, order=args.order)
             else:
