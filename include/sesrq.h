@@ -202,6 +202,11 @@ int sesrq_net_shape(const sesrq_net *net, int *cin, int *cout, int *pixel_shuffl
  *   - nothing outside [ptr, ptr + size) of an output, a tap buffer or the workspace is written, and the inputs are not written at all;
  *   - nothing outside [in, in + size) affects the result: what surrounds a frame (NaN, the next frame of a pool) is never used where
  *     the pad value belongs;
+ *   - a +-infinity element of an fp32 frame quantises to the end of the code range on its side, as in the reference; a NaN element
+ *     (quiet or signalling, either sign, any payload) quantises to the lowest code -2^(b-1), where the reference's nan.to(int8) is
+ *     undefined.  This holds for the input quantiser of the forward family on each of its first-layer kernels (MFMA and dot4, every
+ *     exact_div form, every width), and such an element reaches nothing but the code of its own position.  With anchor_add the fp32
+ *     output adds the frame itself: there a NaN or infinity shows in the output pixels of its own position, and only there;
  *   - the workspace's prior contents do not matter, and every byte of an output that was asked for is written by every call. */
 
 /* Bytes of device workspace sesrq_forward needs for N frames of H x W (caller-owned). */

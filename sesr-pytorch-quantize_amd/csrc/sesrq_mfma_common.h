@@ -51,9 +51,14 @@ __device__ __forceinline__ unsigned fbits(float f) { return __builtin_bit_cast(u
 // Every constant sits in a VGPR (InQuantV, filled once per kernel through pin()): a scalar-operand v_mul / v_fma / v_add costs
 // 2.1-2.3 ns per wave on gfx950, the all-VGPR form 1.4-1.5 (tools/op_cost_probe.hip) -- five such instructions per value -- and v_med3
 // with two wave-uniform bounds needs one of them in a VGPR anyway (one SGPR per instruction).
+// A NaN element quantises to the lowest code (include/sesrq.h), as on the dot4 kernel, whose fmaxf drops it: the clamp is written
+// med3(x, xhi, xlo), not med3(x, xlo, xhi).  With a NaN operand v_med3_f32 gives min(min(S0, S1), S2), and in IEEE mode v_min_f32
+// answers a SIGNALLING NaN with that NaN quieted instead of the other operand: (x, xlo, xhi) ends as min(qNaN, xhi) = xhi, the highest
+// code, for every signalling NaN and as xlo for every quiet one (measured; tests/test_input_sweep.py sweeps every payload);
+// (x, xhi, xlo) ends as min(., xlo) = xlo for both.  The same instruction, the same median for every number.
 struct InQuantV { float xlo, xhi, r, ns, r2, z, magic; };
 __device__ __forceinline__ unsigned quantize_in_bits(float x, const InQuantV &c) {
-    const float xc = med3(x, c.xlo, c.xhi);
+    const float xc = med3(x, c.xhi, c.xlo);
     const float q = __fmul_rn(xc, c.r);
     const float q1 = __builtin_fmaf(__builtin_fmaf(c.ns, q, xc), c.r2, q);
     return __builtin_bit_cast(unsigned, __fadd_rn(__fadd_rn(q1, c.z), c.magic));
@@ -62,7 +67,7 @@ __device__ __forceinline__ unsigned quantize_in_bits(float x, const InQuantV &c)
 // The same at a width b < 8: clamp_b of the un-rounded value in front of the rounding add (integer bounds and a monotone rounding
 // commute).  The division form's proof carries over: clamp_b = clamp_b o clamp8.
 __device__ __forceinline__ unsigned quantize_in_bits_q(float x, const InQuantV &c, float qlo, float qhi) {
-    const float xc = med3(x, c.xlo, c.xhi);
+    const float xc = med3(x, c.xhi, c.xlo);      // operand order: a NaN gives xlo (above)
     const float q = __fmul_rn(xc, c.r);
     const float q1 = __builtin_fmaf(__builtin_fmaf(c.ns, q, xc), c.r2, q);
     return __builtin_bit_cast(unsigned, __fadd_rn(med3(__fadd_rn(q1, c.z), qlo, qhi), c.magic));

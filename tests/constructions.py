@@ -10,6 +10,9 @@ probed layer and identity relays (one centre tap, + 128, M * 2^-n == 1, zero poi
   the others, so the interior of a (256 + 2 m)^2 frame contains every (a, b) pair; a ramp row sums a + 256 b + add_const and so takes
   every integer of a 65 536-long interval exactly once -- tests/test_requant_sweep.py.
 
+A third construction, of centre taps only, carries the input quantiser's code of every pixel to the output (Carrier) --
+tests/test_input_sweep.py.
+
 exact_byte is the requant restated in exact integer arithmetic: the independent reference of the sweep.
 """
 import numpy as np
@@ -347,6 +350,71 @@ class Ramp:
             else:
                 out[o] = exact_byte(s, M, n, self.z, relu=(t != 4), b=b)
         return {o: v for o, v in out.items() if o < self.cout}
+
+
+# ------------------------------------------------------------------------------------------------ carrier construction
+class Carrier:
+    """A five-layer net of centre taps only that CARRIES the input quantiser's code of every pixel to the output: the first layer has
+    weight 1 at (2, 2) from input channel c to output channel c, relays stand behind it, and output channel o shows input channel
+    o mod cin.  Every output pixel depends on its own input pixel only: every pixel of a frame is a probe of q0, and padding plays no
+    part.  tests/test_input_sweep.py.
+
+    rc=False    zero[1] = -2^(b-1): layer 0's output is the residual operand too; layers 1..3 relay, the merge halves the two equal
+                operands (HALF).
+    rc=True     zero[1] = z1 != -2^(b-1): layer 0 writes a separate residual tensor, and THAT copy carries the probe: layers 1..3 are
+                off (ic == -2^(b-1), constant), the merge adds it with M_res * 2^-n_res == 1.
+    risky       output rows of layer 0 that carry no probe and whose weights (127 on every tap of input channel 0) let PE 0 leave its
+                accumulator: they choose the hybrid kernel (one row, or rows of one accumulator register: 4 i .. 4 i + 3; rows of two
+                registers: "clamp all four") without touching a probed channel.  Nothing behind layer 0 reads them.
+    bits        the PE accumulator / adder widths: anything but (18, 20) takes the run-time bounds (GEN_ANY) under force_general.
+    The expected output byte of a pixel is lut()[o][q0 - qlo]: the LUT comes from an oracle's forward of a frame of all 2^b codes."""
+
+    def __init__(self, cin, s0, z0, b=8, rc=False, risky=(), cout=16, ps=1, bits=(18, 20), z1=None, name=""):
+        L, half = 5, 1 << (b - 1)
+        if not 1 <= cin <= 4 or cout % (ps * ps) or any(r < cin or r >= 16 for r in risky):
+            raise ValueError("carrier: 1..4 input channels, whole output channels, risky rows beside the probed ones")
+        self.cin, self.b, self.rc, self.cout, self.ps = cin, b, rc, cout, ps
+        rows_of = [[off()] * 16 for _ in range(L)]
+        for c in range(cin):
+            rows_of[0][c] = relay(c)
+            if not rc:
+                for k in (1, 2, 3):
+                    rows_of[k][c] = relay(c)
+        rows_of[L - 1] = [relay(o % cin) for o in range(cout)]
+        zero = [-half] * (L + 1)
+        zero[0] = int(z0)
+        if rc:
+            zero[1] = (-half + 28 if b == 8 else -half + 1) if z1 is None else z1
+            if zero[1] == -half:
+                raise ValueError("carrier: rc=True needs zero[1] != -2^(b-1)")
+        layers = [ramp_layer(5 if k in (0, L - 1) else 3, cin if k == 0 else 16, rows_of[k], (), ONE, relu=(k != L - 1), b=b) for k in range(L)]
+        for r in risky:
+            layers[0].wq[r, 0] = 127
+        res = ONE if rc else HALF
+        self.net = O.Net(layers=layers, scale=[float(s0)] + [1.0] * L, zero=zero, M_res=res[0], n_res=res[1], pixel_shuffle=ps,
+                         acc_bits=bits[0], add_bits=bits[1], quan_bits=b, name=name or f"carrier cin={cin} s0={s0} z0={z0} b={b} rc={rc}")
+
+    def all_codes(self):
+        """int8 (1, cin, 1, 2^b): every code of the width in every channel, channel c rotated by c."""
+        q = np.arange(-(1 << (self.b - 1)), 1 << (self.b - 1), dtype=np.int64)
+        return np.stack([np.roll(q, c) for c in range(self.cin)]).astype(np.int8)[None, :, None, :]
+
+    def unshuffle(self, a):
+        """(1, cout / ps^2, H ps, W ps) -> (cout, H, W): the inverse of O.pixel_shuffle (numpy arrays and torch tensors alike)."""
+        r = self.ps
+        _, c, Hr, Wr = a.shape
+        return a.reshape(c, Hr // r, r, Wr // r, r).permute(0, 2, 4, 1, 3).reshape(c * r * r, Hr // r, Wr // r) if hasattr(a, "permute") else \
+            a.reshape(c, Hr // r, r, Wr // r, r).transpose(0, 2, 4, 1, 3).reshape(c * r * r, Hr // r, Wr // r)
+
+    def lut(self, forward):
+        """int8 (cout, 2^b): the output byte of channel o for every code of its input channel, by `forward` (an oracle's) on the frame
+        of all codes."""
+        q0 = self.all_codes()
+        out = self.unshuffle(forward(self.net, q0)["q_out"])[:, 0, :]
+        lut = np.empty((self.cout, 1 << self.b), np.int8)
+        for o in range(self.cout):
+            lut[o] = np.roll(out[o], -(o % self.cin))            # undo the channel's rotation: index = q0 - qlo
+        return lut
 
 
 # ------------------------------------------------------------------------------------------------ the requant in exact integers
