@@ -1,6 +1,8 @@
 // Host scaffold of the side libraries (libsesrq_eval.so, libsesrq_raw.so, libsesrq_image.so): the error buffer, the launch counters
 // behind their exported instance lists, the input-domain check and host q0 quantiser, and a context that keeps one host table on a
-// device.  Each library stays a library of its own; only this host code is shared.  Everything here has internal
+// device.  For the two Bayer unpack libraries (raw, sensor; their device body is sesrq_bayer_unpack.h) also the q0 table of a level
+// count, the shared argument checks of their unpack entries and a context's publish / destroy.
+// Each library stays a library of its own; only this host code is shared.  Everything here has internal
 // linkage (static, or the anonymous namespace), so a library exports exactly what its own header declares.  No device code.
 #pragma once
 
@@ -67,6 +69,34 @@ struct DeviceTable {
     return (int8_t)fminf(fmaxf(q, -128.f), 127.f);
 }
 
+// q0 of every level d = 0 .. D of a raw format with D + 1 levels: x = clamp(fl32(d) / fl32(D), 0, 1), quantised as the net's input.
+[[maybe_unused]] static void level_table(int D, const InQuant &q, int8_t *table) {
+    for (int d = 0; d <= D; ++d) {
+        float x = (float)d / (float)D;                       // true IEEE quotient, as torch's CPU tensor / scalar
+        x = fminf(fmaxf(x, 0.f), 1.f);
+        table[d] = host_quant(x, q);
+    }
+}
+
+// What every Bayer unpack entry refuses first.
+[[maybe_unused]] static int check_unpack(const char *who, const void *ctx, const void *raw, const void *q0, const void *spread, int N, int H,
+                                         int W) {
+    if (!ctx) return fail("%s: ctx is NULL", who);
+    if (!raw) return fail("%s: raw is NULL", who);
+    if (!q0 && !spread) return fail("%s: neither q0 nor spread requested", who);
+    if (N < 1 || H < 1 || W < 1) return fail("%s: empty frame (N = %d, H = %d, W = %d)", who, N, H, W);
+    return 0;
+}
+
+// The N H ceil(W / seg) items of a grid-stride launch over row segments, which must fit an int together with one grid round.
+[[maybe_unused]] static int segment_items(const char *who, int N, int H, int W, int seg, long long round, int *segs, int *items) {
+    const long long s = (W + seg - 1) / seg, n = (long long)N * H * s;
+    if (n > 0x7fffffffLL - round) return fail("%s: frame of %d x %d x %d is too large", who, N, H, W);
+    *segs = (int)s;
+    *items = (int)n;
+    return 0;
+}
+
 // Upload `bytes` of `host` to the current device; on failure nothing stays allocated.
 [[maybe_unused]] static hipError_t table_create(DeviceTable &t, const void *host, size_t bytes) {
     hipError_t e = hipGetDevice(&t.device);
@@ -83,6 +113,25 @@ struct DeviceTable {
 [[maybe_unused]] static void table_destroy(DeviceTable &t) {
     if (t.ptr) (void)hipFree(t.ptr);
     t.ptr = nullptr;
+}
+
+// The end of a <library>_create whose context `c` (new, with a DeviceTable t) keeps `bytes` of `host`: *out = c, or c is deleted.
+template <class Ctx>
+[[maybe_unused]] static int ctx_publish(const char *who, Ctx *c, const void *host, size_t bytes, Ctx **out) {
+    const hipError_t e = table_create(c->t, host, bytes);
+    if (e != hipSuccess) {
+        delete c;
+        return fail("%s: %s", who, hipGetErrorString(e));
+    }
+    *out = c;
+    return 0;
+}
+
+template <class Ctx>
+[[maybe_unused]] static void ctx_destroy(Ctx *c) {
+    if (!c) return;
+    table_destroy(c->t);
+    delete c;
 }
 
 [[maybe_unused]] static int table_on_current(const char *who, const DeviceTable &t) {

@@ -343,25 +343,15 @@ class Calibrator:
         reference's fp32 input (sesrq.raw, the spread frame: self_dataset.py TestDataset's inp) and calibrated as enqueue() does.
         fmt: a sesrq.sensor.Format -- frames in that sensor format (`stride`, `width` as sesrq.sensor.frames takes them), unpacked by
         libsesrq_sensor.so; without it nothing changes."""
-        from . import raw as rawmod
+        from . import sensor
         self._check_device_pass("enqueue_raw")
         if self.in_channels != 3:
             raise ValueError(f"Calibrator.enqueue_raw: a raw RGGB frame feeds 3-channel nets; this one takes {self.in_channels}")
         st = torch.cuda.current_stream(self.device)
-        if fmt is None:
-            if stride is not None or width is not None:
-                raise ValueError("Calibrator.enqueue_raw: stride and width belong to a sensor format (fmt=...)")
-            raw = rawmod._frames(raw_u16, self.device).contiguous()
-            N, H, W = raw.shape
-            x = self._acts(N, H, W)["input"]
-            rawmod.launch(self.device, 1.0, 0, 0, raw, None, x, st)
-        else:
-            from . import sensor
-            raw, W, S = sensor.frames(raw_u16, fmt, self.device, stride, width)
-            raw = raw.contiguous()
-            N, H = raw.shape[0], raw.shape[1]
-            x = self._acts(N, H, W)["input"]
-            sensor.launch(self.device, fmt, 1.0, 0, 0, raw, W, S, None, x, st)
+        raw, W, S = sensor.frames(raw_u16, fmt, self.device, stride, width, "Calibrator.enqueue_raw: ")
+        raw = raw.contiguous()
+        x = self._acts(raw.shape[0], raw.shape[1], W)["input"]
+        sensor.launch(self.device, fmt, 1.0, 0, 0, raw, W, S, None, x, st)
         self.last_input = x
         return self._forward_device(x, out)
 

@@ -345,7 +345,7 @@ class Engine:
         fmt: a sesrq.sensor.Format -- the frames are in that sensor format (any CFA order and levels; torch.uint16, or torch.uint8
         rows of MIPI RAW10 / RAW12; `stride` and `width` as sesrq.sensor.frames takes them) and libsesrq_sensor.so unpacks them.
         Without it nothing changes: 12-bit RGGB through libsesrq_raw.so."""
-        from . import raw as rawmod
+        from . import sensor
         if self.bundle.in_channels != 3:
             raise ValueError(f"forward_raw: a raw RGGB frame feeds 3-channel nets; this one takes {self.bundle.in_channels}")
         if self.i8_in_scale != 0.0:
@@ -355,23 +355,12 @@ class Engine:
         if not (want_q or want_f):
             raise ValueError("forward_raw: ask for the int8 output, the fp32 output or both")
         narrow = self.quan_bits != 8       # the buffer holds q0, or the fp32 frame of a narrow net
-        if fmt is None:
-            if stride is not None or width is not None:
-                raise ValueError("forward_raw: stride and width belong to a sensor format (fmt=...)")
-            raw = rawmod._frames(raw, self.device)
-            N, H, W = raw.shape
+        raw, W, S = sensor.frames(raw, fmt, self.device, stride, width, "forward_raw: ")
+        N, H = raw.shape[0], raw.shape[1]
 
-            def unpack(src, buf, st):
-                rawmod.launch(self.device, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, src, None if narrow else buf,
-                              buf if narrow else None, st)
-        else:
-            from . import sensor
-            raw, W, S = sensor.frames(raw, fmt, self.device, stride, width)
-            N, H = raw.shape[0], raw.shape[1]
-
-            def unpack(src, buf, st):
-                sensor.launch(self.device, fmt, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, src, W, S,
-                              None if narrow else buf, buf if narrow else None, st)
+        def unpack(src, buf, st):
+            sensor.launch(self.device, fmt, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, src, W, S,
+                          None if narrow else buf, buf if narrow else None, st)
         return self._run(raw, _lib.F32 if narrow else _lib.I8, want_q, want_f, out_q if want_q else None, out_f if want_f else None,
                          stream, slot, (N, 3, H, W), unpack)
 

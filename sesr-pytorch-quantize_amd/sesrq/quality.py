@@ -247,8 +247,8 @@ def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32",
             from . import image as imgmod
             g = imgmod.load_gt(g, mflag, dev, order=order)
         elif g.dtype == torch.uint16:        # a 16-bit RGB frame: / 4095, clamped (self_dataset.py:235-243)
-            from . import raw as rawmod, sensor
-            g = rawmod.load_gt(g, dev) if fmt is None else sensor.load_gt(g, fmt, dev)
+            from . import sensor
+            g = sensor.load_gt(g, fmt, dev)
         else:
             g = (g if g.dim() == 4 else g.unsqueeze(0)).to(dev, dtype=torch.float32, non_blocking=True)
         rows.append(score_anchored(y, calibrator.last_input, g) if form == FORM_X2 else score(y, g, mflag))
@@ -310,18 +310,16 @@ def evaluate_raw(engine, raws, gts_u16, mflag: int, fmt=None):
 
     fmt: a sesrq.sensor.Format -- the frames are unpadded frames of that sensor format (uint16, or uint8 rows of RAW10 / RAW12) and the
     ground truths are mapped with its levels.  MFLAG 1 scores the RGGB mosaic and refuses every other CFA order."""
-    from . import raw as rawmod
+    from . import sensor
     form_of(mflag)
     if mflag not in RAW_MFLAGS:
         raise ValueError(f"MFLAG {mflag}: raw RGGB frames feed the denoise / demosaic nets (MFLAG 1, 2, 3, 4)")
     check_mosaic_format(mflag, fmt)
     dev = engine.device
-    if fmt is not None:
-        from . import sensor
 
     def step(r, g, fp32):
         q, _ = engine.forward_raw(_lib.host_tensor(r).to(dev, non_blocking=True), want_q=True, want_f=False, fmt=fmt)
-        return q, rawmod.load_gt(g, dev) if fmt is None else sensor.load_gt(g, fmt, dev)
+        return q, sensor.load_gt(g, fmt, dev)
     return _evaluate(engine, mflag, zip(raws, gts_u16), step)
 
 

@@ -65,57 +65,19 @@ def raw_size(path: str):
 
 def load_raw(path: str) -> np.ndarray:
     """A reference raw frame as a (rows, cols) uint16 array (little-endian file, row-major, as np.fromfile reads it there)."""
-    rows, cols = raw_size(path)
-    nbytes = os.path.getsize(path)
-    if nbytes != 2 * rows * cols:
-        raise ValueError(f"{path}: {nbytes} bytes, a {rows} x {cols} uint16 frame has {2 * rows * cols}")
-    return np.fromfile(path, dtype="<u2").reshape(rows, cols).astype(np.uint16, copy=False)
-
-
-_levels = {}
+    from . import sensor
+    return sensor.load_raw(path, None)
 
 
 def load_gt(array_u16, device=None):
     """Ground truth of the raw route: a 16-bit RGB frame (N, 3, H, W) or (3, H, W), numpy or torch uint16, as device fp32 (N, 3, H, W)
     = clamp(fl32(v) / 4095, 0, 1), the reference's true fp32 quotient (self_dataset.py:235-243): codes are uploaded at 2 B/px and mapped
     on the device through the 4096 quotients formed on the host (a GPU tensor / scalar division would multiply by fl(1 / 4095))."""
-    import torch
-    g = _lib.host_tensor(array_u16)
-    if not isinstance(g, torch.Tensor) or g.dtype != torch.uint16:
-        raise ValueError("load_gt: the ground truth must be a uint16 array or tensor")
-    if g.dim() == 3:
-        g = g.unsqueeze(0)
-    if g.dim() != 4 or g.shape[1] != 3:
-        raise ValueError(f"load_gt: expected an RGB frame (N, 3, H, W), got {tuple(g.shape)}")
-    dev = torch.device(device) if device is not None else (g.device if g.device.type == "cuda" else
-                                                           torch.device("cuda", torch.cuda.current_device()))
-    lv = _levels.get(dev)
-    if lv is None:
-        codes = np.arange(CODES, dtype=np.float32)
-        lv = _levels[dev] = torch.from_numpy(np.clip(codes / np.float32(WHITE), np.float32(0), np.float32(1))).to(dev)
-    idx = g.to(dev, non_blocking=True).to(torch.int32).clamp_(max=WHITE)
-    return lv[idx.long()]
+    from . import sensor
+    return sensor.load_gt(array_u16, None, device)
 
 
 # ------------------------------------------------------------------------------------------------------------------ device
-def _frames(raw, device):
-    """(N, H, W) view of a (N, 1, H, W) / (N, H, W) / (H, W) uint16 device tensor."""
-    import torch
-    if not isinstance(raw, torch.Tensor) or raw.dtype != torch.uint16:
-        raise ValueError("a raw frame must be a torch.uint16 tensor (N, 1, H, W) or (N, H, W)")
-    if raw.dim() == 4:
-        if raw.shape[1] != 1:
-            raise ValueError(f"a raw frame has one channel, got {tuple(raw.shape)}")
-        raw = raw.reshape(raw.shape[0], raw.shape[2], raw.shape[3])
-    elif raw.dim() == 2:
-        raw = raw.unsqueeze(0)
-    if raw.dim() != 3 or min(raw.shape) < 1:
-        raise ValueError(f"a raw frame is (N, 1, H, W) or (N, H, W), got {tuple(raw.shape)}")
-    if raw.device != device:
-        raise ValueError(f"raw frame is on {raw.device}, expected {device}")
-    return raw
-
-
 def launch(device, scale_in, zero_in, exact_div, raw, q0, spread, stream):
     """Enqueue one unpack of the (N, H, W) contiguous uint16 `raw` into caller-owned q0 / spread (either may be None) on `stream`."""
     N, H, W = raw.shape
@@ -131,21 +93,5 @@ def unpack(engine_or_bundle, raw, want_q: bool = True, want_spread: bool = False
 
     q0 is in the input domain of the net (engine.bundle or the bundle itself: scale[0], zero[0]; an Engine also fixes how x / s0 is
     formed, its exact_div); spread is the reference's fp32 input frame (engine_or_bundle may be None when only spread is asked for).  Enqueued on `stream` (default: current), not synchronised."""
-    import torch
-    if not (want_q or want_spread):
-        raise ValueError("unpack: ask for q0, spread or both")
-    b, scale_in, zero_in, exact_div, dev = _lib.input_domain(engine_or_bundle, want_q, "unpack")
-    if b is not None and b.in_channels != 3:
-        raise ValueError(f"a raw RGGB frame feeds 3-channel nets; this one takes {b.in_channels}")
-    if dev is None:
-        dev = raw.device if isinstance(raw, torch.Tensor) else None
-    raw = _frames(raw, dev)
-    if dev is None or dev.type != "cuda":
-        raise ValueError("the raw frame must be on a HIP device")
-    N, H, W = raw.shape
-    with torch.cuda.device(dev):
-        raw = raw.contiguous()
-        q0 = torch.empty((N, 3, H, W), dtype=torch.int8, device=dev) if want_q else None
-        sp = torch.empty((N, 3, H, W), dtype=torch.float32, device=dev) if want_spread else None
-        launch(dev, scale_in, zero_in, exact_div, raw, q0, sp, _lib.enter_stream(dev, stream, raw, q0, sp))
-    return q0, sp
+    from . import sensor
+    return sensor.unpack(engine_or_bundle, raw, None, want_q, want_spread, stream=stream)

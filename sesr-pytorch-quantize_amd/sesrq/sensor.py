@@ -7,6 +7,10 @@ libsesrq_sensor.so (C ABI include/sesrq_sensor.h, which states the per-pixel ari
 of sesrq_forward -- and, when asked, into the fp32 input frame.  At Format() every byte is the one sesrq.raw gives.  The reference has
 no format knob, so other formats are pinned to a restatement of the header's arithmetic (tests/sensor_oracle.py).  pack / unpack_host
 are host-side numpy, for files and tests; there is no CPU path to q0.
+
+The route's code lives here once.  Everything that takes `fmt` also takes None -- the reference's dataset format on libsesrq_raw.so,
+decided in route() and nowhere else -- and sesrq.raw's load_raw / load_gt / unpack are calls of these with fmt=None; its launch is the
+binding of sesrq_raw_unpack that launch() here calls for fmt=None.
 """
 from __future__ import annotations
 
@@ -16,7 +20,7 @@ import os
 
 import numpy as np
 
-from . import _lib
+from . import _lib, raw as _raw
 from .raw import raw_size
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -107,6 +111,19 @@ def _fmt(fmt) -> Format:
     return fmt
 
 
+REFERENCE = Format()
+
+
+def route(fmt, who: str = "", stride=None, width=None):
+    """The raw route's one decision: (the frames' Format, whether libsesrq_raw.so unpacks them).  fmt=None is the reference's dataset
+    format on libsesrq_raw.so, whose rows are unpadded; a Format, the default one included, goes to libsesrq_sensor.so."""
+    if fmt is None:
+        if stride is not None or width is not None:
+            raise ValueError(f"{who}stride and width belong to a sensor format (fmt=...)")
+        return REFERENCE, True
+    return _fmt(fmt), False
+
+
 def table(fmt: Format, scale_in: float, zero_in: int, exact_div: int = 0) -> np.ndarray:
     """q0 of every d = clamp(code, black, white) - black = 0 .. white - black (host): clamp8(rint(x / s0 + z0)) with x = clamp(fl32(d) /
     fl32(white - black), 0, 1).  exact_div as sesrq_options.exact_div (0 / 1: the true quotient, 2: x * fl(1 / s0))."""
@@ -176,11 +193,12 @@ def unpack_host(rows_u8, fmt: Format, width: int = None) -> np.ndarray:
     return np.stack(px, -1).reshape(r.shape[:-1] + (W,)).astype(np.uint16)
 
 
-def load_raw(path: str, fmt: Format) -> np.ndarray:
+def load_raw(path: str, fmt) -> np.ndarray:
     """A raw frame file ``<name>_<rows>_<cols>.raw`` (the reference's naming) in `fmt`: (rows, cols) uint16 for u16 (little-endian),
     (rows, fmt.row_bytes(cols)) uint8 for the packed formats.  The file holds exactly rows x row_bytes bytes."""
+    fmt, _ = route(fmt)
     rows, cols = raw_size(path)
-    nb = _fmt(fmt).row_bytes(cols)
+    nb = fmt.row_bytes(cols)
     nbytes = os.path.getsize(path)
     if nbytes != rows * nb:
         raise ValueError(f"{path}: {nbytes} bytes, a {rows} x {cols} {fmt.packing} frame has {rows * nb}")
@@ -192,12 +210,12 @@ def load_raw(path: str, fmt: Format) -> np.ndarray:
 _levels = {}
 
 
-def load_gt(array_u16, fmt: Format, device=None):
+def load_gt(array_u16, fmt, device=None):
     """Ground truth of the raw route at the format's levels: a 16-bit RGB frame (N, 3, H, W) or (3, H, W), numpy or torch uint16, as
-    device fp32 (N, 3, H, W) = x(clamp(v, black, white) - black).  As sesrq.raw.load_gt, the quotients are formed on the host and looked
-    up on the device (a GPU tensor / scalar division would multiply by a reciprocal)."""
+    device fp32 (N, 3, H, W) = x(clamp(v, black, white) - black).  The quotients are formed on the host and looked up on the device (a
+    GPU tensor / scalar division would multiply by a reciprocal)."""
     import torch
-    _fmt(fmt)
+    fmt, _ = route(fmt)
     g = _lib.host_tensor(array_u16)
     if not isinstance(g, torch.Tensor) or g.dtype != torch.uint16:
         raise ValueError("load_gt: the ground truth must be a uint16 array or tensor")
@@ -216,13 +234,13 @@ def load_gt(array_u16, fmt: Format, device=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------ device
-def frames(raw, fmt: Format, device, stride: int = None, width: int = None):
-    """((N, H, S) view of the frames, W, row stride in bytes) of a device tensor in `fmt`.
+def frames(raw, fmt, device, stride: int = None, width: int = None, who: str = ""):
+    """((N, H, S) view of the frames, W, row stride in bytes) of a device tensor in `fmt`; `who` goes in front of route()'s refusal.
 
     u16: torch.uint16 (N, 1, H, S) / (N, H, S) / (H, S); packed: torch.uint8 (N, H, S) / (H, S), S bytes per row.  Without `stride` the
     rows are unpadded and W follows from S; a padded frame gives its row stride in bytes (it must be the tensor's) and its `width`."""
     import torch
-    _fmt(fmt)
+    fmt, _ = route(fmt, who, stride, width)
     want = torch.uint16 if fmt.packing == "u16" else torch.uint8
     if not isinstance(raw, torch.Tensor) or raw.dtype != want:
         raise ValueError(f"a {fmt.packing} raw frame must be a torch.{'uint16' if want == torch.uint16 else 'uint8'} tensor")
@@ -271,6 +289,9 @@ def context(device, fmt: Format, scale_in, zero_in, exact_div):
 
 def launch(device, fmt, scale_in, zero_in, exact_div, raw, W, S, q0, spread, stream):
     """Enqueue one unpack of the contiguous (N, H, S bytes) `raw` of W pixels a row into caller-owned q0 / spread (either may be None)."""
+    fmt, reference = route(fmt)
+    if reference:          # libsesrq_raw.so: the (N, H, W) uint16 tensor says its own W and rows are unpadded
+        return _raw.launch(device, scale_in, zero_in, exact_div, raw, q0, spread, stream)
     N, H = raw.shape[0], raw.shape[1]
     h = context(device, fmt, scale_in, zero_in, exact_div)
     rc = lib().sesrq_sensor_unpack(h, raw.data_ptr(), S, q0.data_ptr() if q0 is not None else None,
@@ -279,7 +300,7 @@ def launch(device, fmt, scale_in, zero_in, exact_div, raw, W, S, q0, spread, str
         raise ValueError(last_error())
 
 
-def unpack(engine_or_bundle, raw, fmt: Format, want_q: bool = True, want_spread: bool = False, stride: int = None, stream=None,
+def unpack(engine_or_bundle, raw, fmt, want_q: bool = True, want_spread: bool = False, stride: int = None, stream=None,
            width: int = None):
     """raw in `fmt` on a HIP device (see frames()) -> (q0 int8 (N, 3, H, W) | None, spread fp32 (N, 3, H, W) | None).
 

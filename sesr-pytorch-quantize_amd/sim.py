@@ -183,11 +183,8 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("sim.py: the integer path needs a HIP device (no CPU fallback)")
     if args.input.endswith(".raw"):         # the reference's loop: raw frame -> sparse RGGB mosaic / 4095, clamped -> model(inps)
-        from sesrq import raw, sensor
-        if fmt is None:
-            _, inps = raw.unpack(None, torch.from_numpy(raw.load_raw(args.input)).cuda(), want_q=False, want_spread=True)
-        else:                               # a sensor's format: CFA order, levels, MIPI packing (sesrq.sensor)
-            _, inps = sensor.unpack(None, torch.from_numpy(sensor.load_raw(args.input, fmt)).cuda(), fmt, want_q=False, want_spread=True)
+        from sesrq import sensor           # fmt: a sensor's format (CFA order, levels, MIPI packing), or None for the reference's
+        _, inps = sensor.unpack(None, torch.from_numpy(sensor.load_raw(args.input, fmt)).cuda(), fmt, want_q=False, want_spread=True)
     elif as_image:                          # self_dataset_sr.py: uint8 LR image / 255 (MFLAG 5: the float64 luma) -> model(inps)
         from sesrq import image
         form = image.form_of(args.mflag)
@@ -276,8 +273,8 @@ def score_against(path, gfake, inps, mflag, gts=None, fmt=None):
     if tuple(gts.shape) != tuple(gfake.shape):
         raise SystemExit(f"sim.py: --gt has shape {tuple(gts.shape)}, the output is {tuple(gfake.shape)}")
     if gts.dtype == torch.uint16:                   # 16-bit RGB ground truth: / 4095, clamped (self_dataset.py:235-243)
-        from sesrq import raw, sensor
-        gts = raw.load_gt(gts, gfake.device) if fmt is None else sensor.load_gt(gts, fmt, gfake.device)
+        from sesrq import sensor
+        gts = sensor.load_gt(gts, fmt, gfake.device)
     pred = anchored(gfake, inps, mflag)             # test.py:149-155: MFLAG 6 + the nearest-upsampled input
     res = quality.score(pred, gts.float().to(gfake.device), mflag).cpu().numpy()
     totalpsnr = totalssim = 0.0

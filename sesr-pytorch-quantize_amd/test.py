@@ -166,8 +166,8 @@ def load_inputs(paths, image_flag, fmt=None):
     frames = []
     for p in paths:
         if kind == "raw":
-            from sesrq import raw, sensor
-            frames.append(raw.load_raw(p) if fmt is None else sensor.load_raw(p, fmt))
+            from sesrq import sensor
+            frames.append(sensor.load_raw(p, fmt))
         elif kind == "image":
             from sesrq import image
             frames += _frames_of(image.load_image(p), True)
