@@ -209,6 +209,16 @@ int sesrq_net_shape(const sesrq_net *net, int *cin, int *cout, int *pixel_shuffl
  *     output adds the frame itself: there a NaN or infinity shows in the output pixels of its own position, and only there;
  *   - the workspace's prior contents do not matter, and every byte of an output that was asked for is written by every call. */
 
+/* Frame geometry of the forward family, pinned by tests/test_geometry_limits.py on frames built periodic and compared byte for byte:
+ *   - N * H * W <= 2^31 pixels per call ("frame batch too large" otherwise, before anything is enqueued);
+ *   - on the MFMA kernels and the fused trio a frame has H * W < 2^24 pixels (32-bit offsets inside a frame's 16-byte-per-pixel image;
+ *     "frame too large for 32-bit buffer offsets" otherwise); inside that bound any shape runs: one row of 4 194 241 pixels (65536 and
+ *     more 64- or 60-column strips: the kernels then divide where they multiply below), one column of 2^24 - 1 rows.  The dot4 engine
+ *     has no per-frame bound (run at 2^24 + 5 pixels in one row and in one column);
+ *   - N is not bounded by a grid dimension: the frames ride in gridDim.z and eight-row blocks of the dot4 kernels in gridDim.y, and
+ *     the runtime launches both above 65535 (measured at 65536 and 65537 frames, and at 65536 / 65537 / 2 097 152 row blocks);
+ *   - per-frame bases are 64-bit: a workspace tensor, an output or an input may cross 2^32 bytes. */
+
 /* Bytes of device workspace sesrq_forward needs for N frames of H x W (caller-owned). */
 size_t sesrq_workspace_bytes(const sesrq_net *net, int N, int H, int W);
 

@@ -89,6 +89,10 @@ inline RunCut cut_runs(int strips, int units, int N, int wg_budget, int slots_pe
 }
 // the kernels address a frame's NHWC16 image (16 bytes per pixel) with 32-bit buffer offsets: H * W stays below 2^24 pixels
 inline bool frame_fits_32bit_offsets(int H, int W) { return (size_t)H * W * 16 < ((size_t)1 << 28); }
+// Tile row of a staged pixel whose COLUMN lies outside the frame, so that the stages' row test lo <= ty < hi sends it to the pad value.
+// A frame the bound above admits has up to 2^24 - 1 rows and lo goes down to -(2^24): the marker lies below every lo.  (It was -(2^20):
+// from row 2^20 on it passed the row test and a column outside the frame was staged as the 0 of its out-of-range load, not as the pad.)
+constexpr int NO_ROW = -(1 << 30);
 
 enum Epi { EPI_MID = 0, EPI_PRERES = 1, EPI_LAST = 2 };
 

@@ -305,7 +305,7 @@ struct StageNHWC16 {
             const int gx = x0 - R + tx;
             const bool okx = (gx >= 0) & (gx < a.W) & (i < SH * SW);
             voff[it] = okx ? (ty[it] * a.W + gx) * 16 : (int)0x80000000;
-            if (!okx) ty[it] = -(1 << 20);       // never a valid row -> pad
+            if (!okx) ty[it] = NO_ROW;       // never a valid row -> pad
         }
     }
     // y0 >= R only (every tile but the first of the frame): offsets stay non-negative
@@ -549,7 +549,7 @@ struct StageFrame {
             const int tx = i - ty[it] * SWP, gx = x0 - 2 + tx;
             const bool okx = (gx >= 0) & (gx < a.W) & (i < SH * SWP);
             voff[it] = okx ? (ty[it] * a.W + gx) * ESZ : (int)0x80000000;
-            if (!okx) ty[it] = -(1 << 20);
+            if (!okx) ty[it] = NO_ROW;
         }
     }
     // Tiles of a run are stacked: the top CARRY = SH - TH rows of the next tile's staged window are the bottom CARRY rows of this

@@ -69,7 +69,7 @@ struct TrioStage {
             const int gx = x0 - 1 + tx[it];
             const bool okx = (gx >= 0) & (gx < a.W) & (i < TR * TP);
             voff[it] = okx ? (ty[it] * a.W + gx) * 16 : OOB;
-            if (!okx) ty[it] = -(1 << 20);          // never a valid row -> pad
+            if (!okx) ty[it] = NO_ROW;          // never a valid row -> pad
         }
         voff2s = (ty[2] < TH) ? voff[2] : OOB;
     }

@@ -12,6 +12,49 @@ from sesrq import _lib
 LIMIT = 1 << 22                # |s| the biased accumulator cannot hold (one binade of 1.5 * 2^23 + s)
 
 
+# Launch geometry, restated (csrc: MTW / TV / TW, cut_runs and xcd_block): columns per block in x of the per-layer MFMA kernels, the fused
+# trio (60 valid columns of a 64-column window) and the dot4 kernels; the block -> (strip, run) split of the MFMA kernels and the trio is
+# a multiply-high while strips and strips * runs stay below 2^16, and a division from there on.
+STRIP_COLS = {"mfma": 64, "trio": 60, "dot4": 32}
+SPLIT_LIMIT = 1 << 16
+
+
+def strip_count(W, family):
+    return -(-W // STRIP_COLS[family])
+
+
+def widths_around(strips, family):
+    """(the largest width with `strips` strips, the smallest with one more)."""
+    return strips * STRIP_COLS[family], strips * STRIP_COLS[family] + 1
+
+
+def run_count(strips, units, N, slots):
+    """cut_runs' k: vertical runs per strip for a chip of `slots` workgroup slots."""
+    return max(1, min(slots // (strips * N), units))
+
+
+def split_divides(strips, runs):
+    """True where the kernels' prologue divides (inv_nx == 0), False where it multiplies."""
+    return not (strips * runs < SPLIT_LIMIT and strips < SPLIT_LIMIT)
+
+
+def xcd_split(nx, ny, multiply):
+    """xcd_block, restated for a whole grid of nx strips x ny runs: the (strip, run) every block (x, y) works on, as two int64 arrays
+    in block order id = y nx + x.  The first total - total % 8 blocks are dealt round-robin to eight groups (v = (id & 7) per + (id >> 3)),
+    then v is split into (v mod nx, v div nx): with `multiply` the quotient is mulhi(v, ceil(2^32 / nx)) as the kernels form it while
+    inv_nx != 0, else the division."""
+    total = nx * ny
+    per = total >> 3
+    ident = np.arange(total, dtype=np.int64)
+    v = np.where(ident < per * 8, (ident & 7) * per + (ident >> 3), ident)
+    inv = ((1 << 32) + nx - 1) // nx
+    assert int(v.max()) * inv < 1 << 63                   # the 64-bit product the kernels' __umulhi takes the high word of
+    q = (v * inv) >> 32 if multiply else v // nx
+    by = np.where(ident < per * 8, q, ident // nx)
+    bx = np.where(ident < per * 8, v - q * nx, ident % nx)
+    return bx, by
+
+
 def np_verdict(wq, add_const, zero, acc_bits, add_bits):
     """saturation_free + the biased-range guard, restated from their definition: per output channel and PE (input channels p mod 4) the
     extreme sums over q in [-128, 127] are hi = 127 S+ + 128 S-, -lo = -(128 S+ + 127 S-)."""
