@@ -338,11 +338,14 @@ class Calibrator:
         self.last_input = x
         return self._forward_device(x, out)
 
-    def enqueue_raw(self, raw_u16: torch.Tensor, out: Optional[torch.Tensor] = None, fmt=None, stride=None, width=None) -> torch.Tensor:
+    def enqueue_raw(self, raw_u16: torch.Tensor, out: Optional[torch.Tensor] = None, fmt=None, stride=None, width=None,
+                    noise=None) -> torch.Tensor:
         """12-bit RGGB raw frames (N, 1, H, W) / (N, H, W) / (H, W) torch.uint16 on the device, unpacked on the device into the
         reference's fp32 input (sesrq.raw, the spread frame: self_dataset.py TestDataset's inp) and calibrated as enqueue() does.
         fmt: a sesrq.sensor.Format -- frames in that sensor format (`stride`, `width` as sesrq.sensor.frames takes them), unpacked by
-        libsesrq_sensor.so; without it nothing changes."""
+        libsesrq_sensor.so; without it nothing changes.  noise: a sesrq.noise.NoiseModel -- libsesrq_noise.so unpacks the frames and
+        adds the model's shot and read noise (the reference's TEST_RAW_ADD_NOISE; frame n is the model's frame0 + n); without it
+        nothing changes."""
         from . import sensor
         self._check_device_pass("enqueue_raw")
         if self.in_channels != 3:
@@ -351,7 +354,11 @@ class Calibrator:
         raw, W, S = sensor.frames(raw_u16, fmt, self.device, stride, width, "Calibrator.enqueue_raw: ")
         raw = raw.contiguous()
         x = self._acts(raw.shape[0], raw.shape[1], W)["input"]
-        sensor.launch(self.device, fmt, 1.0, 0, 0, raw, W, S, None, x, st)
+        if noise is None:
+            sensor.launch(self.device, fmt, 1.0, 0, 0, raw, W, S, None, x, st)
+        else:
+            from . import noise as noisemod
+            noisemod.launch(self.device, fmt, 1.0, 0, 0, raw, W, S, None, x, st, noise)
         self.last_input = x
         return self._forward_device(x, out)
 

@@ -332,7 +332,7 @@ class Engine:
     __call__ = forward
 
     def forward_raw(self, raw: torch.Tensor, want_q: bool = True, want_f: bool = True, out_q=None, out_f=None, stream=None,
-                    slot: int = 0, fmt=None, stride=None, width=None):
+                    slot: int = 0, fmt=None, stride=None, width=None, noise=None):
         """raw: (N, 1, H, W) or (N, H, W) torch.uint16 12-bit RGGB frames on self.device -> (q int8 | None, y float32 | None).
 
         The frames are unpacked on the device (libsesrq_raw.so, sesrq.raw) into this net's q0 -- a per-(N, H, W, slot) buffer the
@@ -344,7 +344,11 @@ class Engine:
 
         fmt: a sesrq.sensor.Format -- the frames are in that sensor format (any CFA order and levels; torch.uint16, or torch.uint8
         rows of MIPI RAW10 / RAW12; `stride` and `width` as sesrq.sensor.frames takes them) and libsesrq_sensor.so unpacks them.
-        Without it nothing changes: 12-bit RGGB through libsesrq_raw.so."""
+        Without it nothing changes: 12-bit RGGB through libsesrq_raw.so.
+
+        noise: a sesrq.noise.NoiseModel -- the reference's TEST_RAW_ADD_NOISE: libsesrq_noise.so unpacks the frames (in `fmt`, or the
+        reference's format) and adds the model's shot and read noise on the way; frame n of the call is the model's frame0 + n.  The
+        results are those of forward() on noise.apply(..., want_spread=True)'s frame.  Without it nothing changes."""
         from . import sensor
         if self.bundle.in_channels != 3:
             raise ValueError(f"forward_raw: a raw RGGB frame feeds 3-channel nets; this one takes {self.bundle.in_channels}")
@@ -358,9 +362,17 @@ class Engine:
         raw, W, S = sensor.frames(raw, fmt, self.device, stride, width, "forward_raw: ")
         N, H = raw.shape[0], raw.shape[1]
 
+        if noise is not None:
+            from . import noise as noisemod
+            noisemod._model(noise)
+
         def unpack(src, buf, st):
-            sensor.launch(self.device, fmt, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, src, W, S,
-                          None if narrow else buf, buf if narrow else None, st)
+            args = (self.device, fmt, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, src, W, S,
+                    None if narrow else buf, buf if narrow else None, st)
+            if noise is None:
+                sensor.launch(*args)
+            else:
+                noisemod.launch(*args, noise)
         return self._run(raw, _lib.F32 if narrow else _lib.I8, want_q, want_f, out_q if want_q else None, out_f if want_f else None,
                          stream, slot, (N, 3, H, W), unpack)
 

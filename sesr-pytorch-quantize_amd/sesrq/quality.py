@@ -216,7 +216,7 @@ def check_calibration_input(calibrator, mflag: int, kind: str, scored: bool = Tr
                          "method='entropy' runs on the host pass (Calibrator.observe)")
 
 
-def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32", order: str = "rgb", fmt=None):
+def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32", order: str = "rgb", fmt=None, noise=None):
     """The reference's calibration loop (test.py:141-183) on the device: per frame the mode-0 forward (Calibrator.enqueue /
     enqueue_raw / enqueue_image, which also accumulates the running ranges) and the metrics of its output in the form the MFLAG uses
     -- MFLAG 6 the anchored output fl32(gfake + up2(inps)), formed inside the scoring kernel (score_anchored).  One synchronisation at
@@ -226,11 +226,16 @@ def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32",
     (H, W) uint16 RGGB frames; "image": (H, W, 3) / (1, H, W, 3) uint8 LR images in `order`.  gts, numpy or torch, by dtype: float32
     frames of the output shape, uint16 RGB frames (3, H, W) / (1, 3, H, W) (sesrq.raw.load_gt), or uint8 HR images in `order`
     (sesrq.image.load_gt).  fmt: the sesrq.sensor.Format of "raw" frames and uint16 ground truths (default: 12-bit RGGB, sesrq.raw).
+    noise: a sesrq.noise.NoiseModel for "raw" frames -- shot and read noise added on the device, consecutive frames getting
+    consecutive frame numbers from the model's frame0 (the reference's TEST_RAW_ADD_NOISE).
     Returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
     import torch
     check_calibration_input(calibrator, mflag, kind)
     if fmt is not None and kind != "raw":
         raise ValueError("a sensor format belongs to raw frames (kind='raw')")
+    if noise is not None and kind != "raw":
+        raise ValueError("noise belongs to raw frames (kind='raw')")
+    done = 0             # raw frames so far
     dev = calibrator.device
     form = FORMS[mflag]
     rows = []
@@ -239,7 +244,11 @@ def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32",
         if kind == "f32":
             y = calibrator.enqueue(x.float() if x.dim() == 4 else x.float().unsqueeze(0))
         elif kind == "raw":
-            y = calibrator.enqueue_raw(x, fmt=fmt)
+            if noise is None:
+                y = calibrator.enqueue_raw(x, fmt=fmt)
+            else:
+                y = calibrator.enqueue_raw(x, fmt=fmt, noise=noise.advance(done))
+                done += y.shape[0]
         else:
             y = calibrator.enqueue_image(x, order=order)
         g = _lib.host_tensor(g)
@@ -299,7 +308,7 @@ def evaluate(engine, frames, gts, mflag: int):
     return _evaluate(engine, mflag, zip(frames, gts), step)
 
 
-def evaluate_raw(engine, raws, gts_u16, mflag: int, fmt=None):
+def evaluate_raw(engine, raws, gts_u16, mflag: int, fmt=None, noise=None):
     """The reference's MFLAG 1 ... 4 loop from raw frames to scores (test.py:30-55 with self_dataset.py TestDataset): per frame the
     12-bit RGGB raw frame is unpacked on the device into the net's q0 and run forward (Engine.forward_raw), its 16-bit RGB ground
     truth is mapped to / 4095 and clamped on the device (sesrq.raw.load_gt), and the int8 output is scored as evaluate() scores it.
@@ -309,16 +318,29 @@ def evaluate_raw(engine, raws, gts_u16, mflag: int, fmt=None):
     returns a host float64 array (frames, 3) of (mse, psnr, ssim).
 
     fmt: a sesrq.sensor.Format -- the frames are unpadded frames of that sensor format (uint16, or uint8 rows of RAW10 / RAW12) and the
-    ground truths are mapped with its levels.  MFLAG 1 scores the RGGB mosaic and refuses every other CFA order."""
+    ground truths are mapped with its levels.  MFLAG 1 scores the RGGB mosaic and refuses every other CFA order.
+
+    noise: a sesrq.noise.NoiseModel -- the frames are clean and the model's shot and read noise is added on the device (the reference's
+    TEST_RAW_ADD_NOISE).  The pass's first frame is the model's frame0 and consecutive frames get consecutive frame numbers, so the
+    scores follow from the model alone, whatever the batch split."""
     from . import sensor
     form_of(mflag)
     if mflag not in RAW_MFLAGS:
         raise ValueError(f"MFLAG {mflag}: raw RGGB frames feed the denoise / demosaic nets (MFLAG 1, 2, 3, 4)")
     check_mosaic_format(mflag, fmt)
     dev = engine.device
+    if noise is not None:
+        from . import noise as noisemod
+        noisemod._model(noise)
+    done = [0]           # frames so far
 
     def step(r, g, fp32):
-        q, _ = engine.forward_raw(_lib.host_tensor(r).to(dev, non_blocking=True), want_q=True, want_f=False, fmt=fmt)
+        if noise is None:
+            q, _ = engine.forward_raw(_lib.host_tensor(r).to(dev, non_blocking=True), want_q=True, want_f=False, fmt=fmt)
+        else:
+            q, _ = engine.forward_raw(_lib.host_tensor(r).to(dev, non_blocking=True), want_q=True, want_f=False, fmt=fmt,
+                                      noise=noise.advance(done[0]))
+            done[0] += q.shape[0]
         return q, sensor.load_gt(g, fmt, dev)
     return _evaluate(engine, mflag, zip(raws, gts_u16), step)
 

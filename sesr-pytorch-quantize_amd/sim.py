@@ -157,8 +157,10 @@ def main(argv=None):
                     help="kernel family of the integer path (sesrq_options.engine).  With --quan-bit below 8, auto, dot4 and mfma run the "
                          "dot4 kernels; mfma-q runs the width-aware MFMA kernels and the fused trio (same bits, several times the rate)")
     add_sensor_flags(ap)
+    add_noise_flags(ap)
     args = ap.parse_args(argv)
     fmt = sensor_format(args, "sim.py", [args.input])
+    noise_m = noise_model(args, "sim.py", [args.input])
     if fmt is not None and args.gt:
         from sesrq import quality
         try:
@@ -184,7 +186,12 @@ def main(argv=None):
         raise SystemExit("sim.py: the integer path needs a HIP device (no CPU fallback)")
     if args.input.endswith(".raw"):         # the reference's loop: raw frame -> sparse RGGB mosaic / 4095, clamped -> model(inps)
         from sesrq import sensor           # fmt: a sensor's format (CFA order, levels, MIPI packing), or None for the reference's
-        _, inps = sensor.unpack(None, torch.from_numpy(sensor.load_raw(args.input, fmt)).cuda(), fmt, want_q=False, want_spread=True)
+        raw = torch.from_numpy(sensor.load_raw(args.input, fmt)).cuda()
+        if noise_m is None:
+            _, inps = sensor.unpack(None, raw, fmt, want_q=False, want_spread=True)
+        else:                               # TEST_RAW_ADD_NOISE: shot and read noise added while the frame is unpacked
+            from sesrq import noise
+            _, inps = noise.apply(None, raw, fmt, noise_m, want_q=False, want_spread=True)
     elif as_image:                          # self_dataset_sr.py: uint8 LR image / 255 (MFLAG 5: the float64 luma) -> model(inps)
         from sesrq import image
         form = image.form_of(args.mflag)
@@ -219,6 +226,39 @@ def add_sensor_flags(ap):
     ap.add_argument("--packing", choices=("u16", "raw10", "raw12"), default=None,
                     help="how *.raw inputs hold their pixels: uint16 containers (default), MIPI RAW10 (4 px in 5 bytes) or RAW12 "
                          "(2 px in 3 bytes); a file is <rows> x the unpadded row bytes")
+
+
+def add_noise_flags(ap):
+    """--add-noise / --shot / --read / --noise-seed: the reference's TEST_RAW_ADD_NOISE on clean *.raw inputs (sesrq.noise)."""
+    ap.add_argument("--add-noise", action=argparse.BooleanOptionalAction, default=None,
+                    help="add shot and read noise to *.raw inputs on the device while they are unpacked, as the reference's dataset does "
+                         "under define.TEST_RAW_ADD_NOISE (the default: without the flag, that constant decides)")
+    ap.add_argument("--shot", type=float, default=None, metavar="S", help="shot noise level (with --read; without them a level is drawn "
+                                                                          "per frame as the reference's random_noise_levels draws it)")
+    ap.add_argument("--read", type=float, default=None, metavar="R", help="read noise level (with --shot)")
+    ap.add_argument("--noise-seed", type=int, default=None, metavar="K", help="seed of the noise stream (default 0): frame f of a run "
+                                                                              "gets the same noise whenever the seed is the same")
+
+
+def noise_model(args, who, inputs):
+    """The sesrq.noise.NoiseModel the noise flags describe, or None without --add-noise (or, with define.TEST_RAW_ADD_NOISE alone,
+    when the inputs are no raw frames: the reference adds noise to raw frames only); a flag error ends the program."""
+    given = [k for k in ("shot", "read", "noise_seed") if getattr(args, k) is not None]
+    raws = bool(inputs) and all(p.endswith(".raw") for p in inputs)
+    explicit = args.add_noise is not None
+    if not (args.add_noise if explicit else define.TEST_RAW_ADD_NOISE):
+        if given:
+            raise SystemExit(f"{who}: --shot, --read and --noise-seed belong to --add-noise")
+        return None
+    if not raws:
+        if given or explicit:
+            raise SystemExit(f"{who}: --add-noise adds noise to *.raw inputs")
+        return None
+    from sesrq import noise
+    try:
+        return noise.NoiseModel(args.shot, args.read, seed=args.noise_seed or 0)
+    except ValueError as e:
+        raise SystemExit(f"{who}: {e}") from None
 
 
 def sensor_format(args, who, inputs):

@@ -84,8 +84,10 @@ def main(argv=None):
                          "carry no QuantAdd state; a QAT --ckpt gives its own")
     ap.add_argument("--float-skip", action="store_true", help="add the long skip in float even for a QAT checkpoint")
     sim.add_sensor_flags(ap)
+    sim.add_noise_flags(ap)
     args = ap.parse_args(argv)
     args.fmt = sim.sensor_format(args, "test.py", args.input)
+    args.noise = sim.noise_model(args, "test.py", args.input)
     if args.quan_bit is not None:
         define.QUAN_BIT = args.quan_bit
     define.check()
@@ -214,7 +216,7 @@ def dataset_pass(args, model):
     cal = lower_calibration(model, dev)
     model.__dict__["_sesrq_cal"] = cal
     if gts is not None:
-        res = quality.evaluate_calibration(cal, frames, gts, args.mflag, kind=kind, order=args.order, fmt=args.fmt)
+        res = quality.evaluate_calibration(cal, frames, gts, args.mflag, kind=kind, order=args.order, fmt=args.fmt, noise=args.noise)
         totalpsnr = totalssim = 0.0
         for _, psnr, ssim in res:
             print(float(psnr))
@@ -222,10 +224,10 @@ def dataset_pass(args, model):
             totalssim += float(ssim)
         print(quality.TASKS[args.mflag] + ' mean psnr is: ', totalpsnr / len(res), ' ssim is: ', totalssim / len(res))
     else:
-        for f in frames:
+        for i, f in enumerate(frames):
             t = torch.from_numpy(np.ascontiguousarray(f)).to(dev)
-            if kind == "raw":
-                cal.enqueue_raw(t, fmt=args.fmt)
+            if kind == "raw":          # --add-noise: frame i of the pass is frame i of the noise stream
+                cal.enqueue_raw(t, fmt=args.fmt, noise=args.noise.advance(i) if args.noise is not None else None)
             elif kind == "image":
                 cal.enqueue_image(t, order=args.order)
             else:
