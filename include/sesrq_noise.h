@@ -23,6 +23,8 @@
  *             sesrq_sensor.h forms it; 0.0f at the two non-sites
  *   combine   v = fl(fl(x_c * shot) + read)   sigma = sqrtf(v)   y = fl(x_c + fl(sigma * z[c]))        each step one IEEE fp32 operation
  *             spread = min(max(y, 0), 1)      non-sites get read noise too: the noise goes onto the whole 3-channel frame
+ *             The clamp is fminf(fmaxf(y, 0), 1), so the frame never holds a NaN: where sigma is infinite (levels near FLT_MAX) and
+ *             z[c] is exactly 0, y = x_c + inf * 0 is a NaN and spread is 0.
  *   quantise  q0 = clamp8(rint(fl(fl(spread / s0) + z0)))    exact_div 0 / 1: the true fp32 quotient; 2: spread * fl(1 / s0)
  *             the input quantiser of sesrq_forward applied to that fp32 value
  *

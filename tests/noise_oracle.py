@@ -34,6 +34,13 @@ def words(seed, frame, H, W):
     return philox((x, y, U64(frame & 0xFFFFFFFF), U64(frame >> 32)), (seed & 0xFFFFFFFF, seed >> 32))
 
 
+def words_at(seed, frame, y, x):
+    """(w0, w1, w2, w3) of one pixel, as ints."""
+    seed, frame = int(seed) & (2 ** 64 - 1), int(frame) & (2 ** 64 - 1)
+    w = philox([np.array([v], U64) for v in (x, y, frame & 0xFFFFFFFF, frame >> 32)], (seed & 0xFFFFFFFF, seed >> 32))
+    return tuple(int(v[0]) for v in w)
+
+
 def u_r(w):
     return ((w >> U64(9)).astype(np.float64) + 0.5) * 2.0 ** -23
 
@@ -74,11 +81,13 @@ def clean(codes, cfa, black, white):
 
 
 def frame(codes, cfa, black, white, levels, z, s0, z0, exact_div=0):
-    """(spread, q0) of the noisy frame.  levels: (shot, read), or an (N, 2) array of them per frame; z: (N, 3, H, W) deviates."""
+    """(spread, q0) of the noisy frame.  levels: (shot, read), or an (N, 2) array of them per frame; z: (N, 3, H, W) deviates.  The
+    clamp is the header's fminf(fmaxf(y, 0), 1): a NaN y (sigma = inf times a deviate that is exactly 0) gives 0, never a NaN."""
     x = clean(codes, cfa, black, white)
     lv = np.asarray(levels, F32)
     shot, read = (lv[0], lv[1]) if lv.ndim == 1 else (lv[:, 0].reshape(-1, 1, 1, 1), lv[:, 1].reshape(-1, 1, 1, 1))
-    y = combine(x, shot, read, z)
-    sp = np.minimum(np.maximum(y, F32(0)), F32(1)).astype(F32)
+    with np.errstate(over="ignore", invalid="ignore"):          # levels at the top of what the header accepts: v = inf, inf * 0
+        y = combine(x, shot, read, z)
+    sp = np.fmin(np.fmax(y, F32(0)), F32(1)).astype(F32)
     return sp, O.quantize_input(sp, s0, z0, reciprocal=exact_div == 2)
 
