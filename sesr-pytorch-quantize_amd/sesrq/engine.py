@@ -411,6 +411,37 @@ class Engine:
         return self._run(img, _lib.F32 if fp else _lib.I8, want_q, want_f, out_q if want_q else None, out_f if want_f else None,
                          stream, slot, (N, cin, H, W), decode)
 
+    def forward_colour(self, img_u8: torch.Tensor, order: str = "rgb", out=None, stream=None, slot: int = 0):
+        """img_u8: (N, H, W, 3) or (H, W, 3) torch.uint8 colour images on self.device, interleaved in `order` -> the colour
+        super-resolved images (N, r H, r W, 3) torch.uint8 in the same order, r the net's PixelShuffle factor.
+
+        For luma nets (1 channel in, 1 channel out: SESR-x4, MFLAG 5): forward_image in the Y form, int8 output only, followed by
+        the fused colour export (libsesrq_colour.so, sesrq.colour) from that int8 output and the same LR image -- the net's Y, the
+        LR image's Cb and Cr upscaled bicubically, back to RGB bytes.  out: a contiguous uint8 tensor of the output shape to write
+        into.  All launches go to `stream` (default: current), ordered as forward() orders them; give concurrent in-flight frames
+        different slots."""
+        from . import colour, image as imgmod
+        b = self.bundle
+        if b.in_channels != 1 or b.out_channels != 1:
+            raise ValueError(f"forward_colour: colour is rebuilt around a luma net (1 channel in, 1 out); this net takes "
+                             f"{b.in_channels} and gives {b.out_channels}: RGB nets export their own colour through "
+                             "forward_image and image.export")
+        r = colour._factor(b.pixel_shuffle)
+        colour._order(order)
+        img = imgmod._images(img_u8, self.device)
+        N, H, W, _ = img.shape
+        shape = (N, r * H, r * W, 3)
+        if out is not None:
+            colour.check_out(out, shape, self.device, "forward_colour")
+        with torch.cuda.device(self.device):
+            img = img.contiguous()
+            q, _ = self.forward_image(img, form="y", order=order, want_q=True, want_f=False, stream=stream, slot=slot)
+            if out is None:
+                out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+            st = _lib.enter_stream(self.device, stream, img, q, out)
+            colour.launch(q, b.scale[b.L], b.zero[b.L], img, order, r, out, st)
+        return out
+
     def submission(self, frames, outs_q, streams, outs_f=None, group: int = 1):
         """A prepared batch of independent forwards for sesrq_forward_many: frame k = frames[k] -> outs_q[k] (/ outs_f[k]; either may be None) on
         streams[k % len(streams)] with workspace slot k % len(streams).  Returns a Submission; .enqueue(count, first=0) issues frames

@@ -10,6 +10,7 @@ test.py produced (an ``output_pt`` directory) or from a bundle/fixture file.
     python sim.py --mflag 5 --ckpt x4sesr.pth --calib output_pt --input rand_SR_Input_80x960.pt
     python sim.py --mflag 5 --params tests/golden/sesr_x4.params.npz --input tests/golden/rand_SR_Input_80x960.npy
     python sim.py --mflag 6 --params ... --input LR.png --gt HR.png --save-png SR.png      # 8-bit images (MFLAG 5 / 6)
+    python sim.py --mflag 5 --params ... --input LR.png --colour --save-png SR.png         # the x4 luma net's output in colour
     python sim.py --mflag 1 --ckpt nr_G.pth --calib output_pt --input a_132_128.raw --gt gt16.npy     # nr: scored on the Bayer mosaic
 """
 import argparse
@@ -144,6 +145,9 @@ def main(argv=None):
     ap.add_argument("--order", choices=("rgb", "bgr"), default="rgb", help="byte order of uint8 .npy images (PNGs are read as RGB)")
     ap.add_argument("--save-png", help="write the output as an 8-bit PNG here (the reference's export: clip to [0, 1], * 255, "
                                        "truncate; MFLAG 6 the anchored output); frame k of a batch goes to <stem>_<k>.png")
+    ap.add_argument("--colour", action="store_true", help="MFLAG 5 with an 8-bit LR image and --save-png: write the COLOUR image -- the "
+                                                          "net's luma, the LR image's Cb / Cr upscaled bicubically, back to RGB "
+                                                          "(sesrq.colour); without the flag the PNG is the grey luma, as the reference's")
     ap.add_argument("--save", help="write the float result here (.npy)")
     ap.add_argument("--gt", help="ground truth of the output shape (N,Cout,H*r,W*r) float32, .npy or .pt: score the output with the "
                                  "reference's PSNR / SSIM on the device (test.py:141-183) and print them as its loop does; a uint16 "
@@ -179,6 +183,10 @@ def main(argv=None):
     from sesrq import _lib
     model.__dict__["sesrq_engine_option"] = _lib.ENGINE_NAMES[args.engine]
     as_image = is_image(args.input, args.image)
+    if args.colour and not (args.mflag == 5 and as_image and args.save_png):
+        raise SystemExit("sim.py: --colour rebuilds colour around the luma net: it needs --mflag 5, an 8-bit LR image as --input "
+                         "(.png, or a uint8 .npy with --image) and --save-png")
+    lr_u8 = None
     if not args.input.endswith(".raw") and not as_image:
         inps = torch.load(args.input, weights_only=True, map_location="cpu") if args.input.endswith(".pt") else \
             torch.from_numpy(np.load(args.input))
@@ -195,8 +203,8 @@ def main(argv=None):
     elif as_image:                          # self_dataset_sr.py: uint8 LR image / 255 (MFLAG 5: the float64 luma) -> model(inps)
         from sesrq import image
         form = image.form_of(args.mflag)
-        _, inps = image.decode(None, torch.from_numpy(image.load_image(args.input)).cuda(), form, order=args.order, want_q=False,
-                               want_f=True)
+        lr_u8 = torch.from_numpy(image.load_image(args.input)).cuda()
+        _, inps = image.decode(None, lr_u8, form, order=args.order, want_q=False, want_f=True)
     gfake = model(inps.float().cuda())
     torch.cuda.synchronize()
     banner(args.mflag)
@@ -212,7 +220,9 @@ def main(argv=None):
             from sesrq import image
             gts = image.load_gt(image.load_image(args.gt), args.mflag, gfake.device, order=args.order)
         score_against(args.gt, gfake, inps, args.mflag, gts=gts, fmt=fmt)
-    if args.save_png:
+    if args.save_png and args.colour:
+        save_colour_png(args.save_png, gfake, lr_u8, args.order)
+    elif args.save_png:
         save_png(args.save_png, gfake, inps, args.mflag)
     return gfake
 
@@ -293,6 +303,20 @@ def save_png(path, gfake, inps, mflag):
     bytes, so no channel flip."""
     from sesrq import image
     u8 = image.export(anchored(gfake, inps, mflag), order="rgb").cpu().numpy()
+    stem, ext = os.path.splitext(path)
+    for k in range(u8.shape[0]):
+        image.save_png(path if u8.shape[0] == 1 else f"{stem}_{k}{ext or '.png'}", u8[k])
+    print("png:", path, tuple(u8.shape))
+
+
+def save_colour_png(path, gfake, lr_u8, order):
+    """--colour: the net's luma with the LR image's chroma, upscaled bicubically, as an RGB PNG (sesrq.colour.export; the fp32 output
+    is the dequantised int8 output, so the bytes are Engine.forward_colour's)."""
+    from sesrq import colour, image
+    lr = lr_u8 if lr_u8.dim() == 4 else lr_u8.unsqueeze(0)
+    if order == "bgr":                      # PIL takes RGB bytes
+        lr = lr.flip(-1)
+    u8 = colour.export(gfake, lr, gfake.shape[2] // lr.shape[1], order="rgb").cpu().numpy()
     stem, ext = os.path.splitext(path)
     for k in range(u8.shape[0]):
         image.save_png(path if u8.shape[0] == 1 else f"{stem}_{k}{ext or '.png'}", u8[k])
