@@ -23,24 +23,22 @@
 
 #include "sesrq_image.h"
 #include "sesrq_side.h"
+#include "sesrq_image_decode.h"
 
 namespace sesrq_imgk {
 
 constexpr int THREADS = 128;
 constexpr int SEG = 16;                       // pixels per lane and run
 constexpr int BLOCKS_PER_CU = 16;             // 128-thread blocks: a full CU (32 waves)
-constexpr int CODES = SESRQ_IMAGE_CODES;
+constexpr int CODES = sesrq_imgdec::CODES;
 enum { OUT_Q = 1, OUT_F = 2 };
 
-// one device allocation per context
-struct Tables {
-    double y[3][CODES];   // 65.481 d(v), 128.553 d(v), 24.966 d(v): the Y form's three products, each rounded once in float64
-    float x[CODES];       // RGB form: clip(fl32(d(v)), 0, 1)
-    int8_t q[CODES];      // RGB form: q0 of x[v]
-};
-constexpr int Y_WORDS = sizeof(double) * 3 * CODES / 16;                    // 384
-constexpr int RGB_WORDS = (sizeof(float) + 1) * CODES / 16;                  // 80
-static_assert(sizeof(Tables) == 16 * (Y_WORDS + RGB_WORDS), "tables are whole 16-byte words");
+using sesrq_imgdec::Tables;
+using sesrq_imgdec::Y_WORDS;
+using sesrq_imgdec::RGB_WORDS;
+using sesrq_imgdec::Quant;
+using sesrq_imgdec::quant;
+using sesrq_imgdec::luma;
 static_assert(Y_WORDS % THREADS == 0 && RGB_WORDS <= THREADS, "staging: whole words per thread");
 
 struct DecodeArgs {
@@ -48,8 +46,8 @@ struct DecodeArgs {
     const Tables *tab;
     int8_t *q0;
     float *x;
-    int HW, segs, items, bgr, recip, planes16;
-    float s0, r0, z0;     // quantiser: x / s0 (recip 0) or x * r0 (recip 1), + z0
+    int HW, segs, items, bgr, planes16;
+    Quant q;              // the input quantiser
 };
 
 struct ExportArgs {
@@ -62,24 +60,10 @@ struct ExportArgs {
 
 __device__ inline unsigned byte_of(const unsigned (&w)[12], int j) { return (w[j >> 2] >> (8 * (j & 3))) & 0xffu; }
 
-__device__ inline int8_t quant(float x, const DecodeArgs &a) {
-    const float t = a.recip ? __fmul_rn(x, a.r0) : __fdiv_rn(x, a.s0);
-    return (int8_t)fminf(fmaxf(rintf(__fadd_rn(t, a.z0)), -128.f), 127.f);
-}
-
-// the Y form of one pixel from its three bytes (R, G, B)
-__device__ inline float luma(const double (*ty)[CODES], unsigned r, unsigned g, unsigned b) {
-    double s = __dadd_rn(ty[0][r], ty[1][g]);
-    s = __dadd_rn(s, ty[2][b]);
-    s = __dadd_rn(s, 16.0);
-    const double y = __ddiv_rn(s, 255.0);                 // a true quotient: no reciprocal multiply
-    return (float)fmin(fmax(y, 0.0), 1.0);
-}
-
 template <int FORM, int OUT>
 __global__ __launch_bounds__(THREADS) void image_decode(DecodeArgs a) {
     constexpr int C = FORM == SESRQ_IMAGE_Y ? 1 : 3;
-    constexpr int WORDS = FORM == SESRQ_IMAGE_Y ? Y_WORDS : RGB_WORDS;
+    constexpr int WORDS = sesrq_imgdec::table_words<FORM>();
     __shared__ uint4 s_tab[WORDS];
     const int stride = gridDim.x * THREADS;
     const size_t HW = (size_t)a.HW;
@@ -112,12 +96,11 @@ __global__ __launch_bounds__(THREADS) void image_decode(DecodeArgs a) {
         run(i, src, o, npx, vec);
         if (vec) load();
     }
-    const uint4 *g4 = reinterpret_cast<const uint4 *>(FORM == SESRQ_IMAGE_Y ? (const void *)a.tab->y : (const void *)a.tab->x);
-    for (int k = threadIdx.x; k < WORDS; k += THREADS) s_tab[k] = g4[k];
+    sesrq_imgdec::stage_tables<FORM, THREADS>(s_tab, a.tab);
     __syncthreads();
-    const double(*ty)[CODES] = reinterpret_cast<const double(*)[CODES]>(s_tab);
-    const float *tx = reinterpret_cast<const float *>(s_tab);
-    const int8_t *tq = reinterpret_cast<const int8_t *>(tx + CODES);
+    const double(*ty)[CODES] = sesrq_imgdec::table_y(s_tab);
+    const float *tx = sesrq_imgdec::table_x(s_tab);
+    const int8_t *tq = sesrq_imgdec::table_q(s_tab);
     // byte position of R in a pixel (B sits at 2 - ir); RGB form: plane c takes byte c (RGB) or 2 - c (BGR)
     const int ir = a.bgr ? 2 : 0;
 
@@ -133,7 +116,7 @@ __global__ __launch_bounds__(THREADS) void image_decode(DecodeArgs a) {
                 if (OUT & OUT_Q) {
                     unsigned qq[4] = {0, 0, 0, 0};
 #pragma unroll
-                    for (int k = 0; k < SEG; ++k) qq[k >> 2] |= (unsigned)(uint8_t)quant(f[k], a) << (8 * (k & 3));
+                    for (int k = 0; k < SEG; ++k) qq[k >> 2] |= (unsigned)(uint8_t)quant(f[k], a.q) << (8 * (k & 3));
                     *reinterpret_cast<uint4 *>(a.q0 + o) = make_uint4(qq[0], qq[1], qq[2], qq[3]);
                 }
                 if (OUT & OUT_F) {
@@ -165,7 +148,7 @@ __global__ __launch_bounds__(THREADS) void image_decode(DecodeArgs a) {
                 const unsigned b0 = src[3 * k], b1 = src[3 * k + 1], b2 = src[3 * k + 2];
                 if (FORM == SESRQ_IMAGE_Y) {
                     const float f = luma(ty, ir ? b2 : b0, b1, ir ? b0 : b2);
-                    if (OUT & OUT_Q) a.q0[o + k] = quant(f, a);
+                    if (OUT & OUT_Q) a.q0[o + k] = quant(f, a.q);
                     if (OUT & OUT_F) a.x[o + k] = f;
                 } else {
                     const unsigned v[3] = {b0, b1, b2};
@@ -258,17 +241,7 @@ static const char *const kNames[K_COUNT] = {
     "image_decode<RGB,q0,x>", "image_export<f32,C1>", "image_export<f32,C3>", "image_export<i8,C1>", "image_export<i8,C3>"};
 static Counters<K_COUNT> g_count{kNames};
 
-static void build(const InQuant &q, Tables &t) {
-    for (int v = 0; v < CODES; ++v) {
-        const volatile double d = (double)v / 255.0;      // d(v), correctly rounded
-        t.y[0][v] = 65.481 * d;
-        t.y[1][v] = 128.553 * d;
-        t.y[2][v] = 24.966 * d;
-        const float x = fminf(fmaxf((float)d, 0.f), 1.f);
-        t.x[v] = x;
-        t.q[v] = host_quant(x, q);
-    }
-}
+using sesrq_imgdec::build;
 
 extern "C" int sesrq_image_table(float scale_in, int zero_in, int exact_div, int8_t q[SESRQ_IMAGE_CODES], float x[SESRQ_IMAGE_CODES]) {
     g_err[0] = 0;
@@ -341,11 +314,8 @@ extern "C" int sesrq_image_decode(sesrq_image_ctx c, const uint8_t *img, int for
     a.segs = segs;
     a.items = items;
     a.bgr = order == SESRQ_IMAGE_ORDER_BGR;
-    a.recip = c->q.recip;
     a.planes16 = a.HW % SEG == 0;
-    a.s0 = c->q.s0;
-    a.r0 = c->q.r0;
-    a.z0 = c->q.z0;
+    a.q = sesrq_imgdec::quant_of(c->q);
     const int grid = grid_cap(items, THREADS, c->t.num_cu, BLOCKS_PER_CU);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int out = (q0 ? OUT_Q : 0) | (x ? OUT_F : 0);

@@ -14,7 +14,7 @@ histogram of every quantiser input over its observed range (sesrq_calib_histogra
 by the clipping range that minimises the KL divergence between the observed distribution and its 256-level quantisation
 (`entropy_range`).  The output domain keeps the reference's rule (min := 0).
 
-Device-resident pass (`enqueue`, `enqueue_raw`, `enqueue_image`): the same forward with no host round trip.  `observe` reads each
+Device-resident pass (`enqueue`, `enqueue_raw`, `enqueue_image`, `enqueue_hr`): the same forward with no host round trip.  `observe` reads each
 quantiser's min/max back to the host to form the next conv's (scale, zero); here one device slot per quantiser input holds the batch's
 extrema, the running extrema and the domain derived from them (sesrq_calib_observe_slot), and the conv / fake-quantiser read it there
 (sesrq_calib_conv_slot / _fakequant_slot).  Nothing waits on the host until `finalize()` (or `sync()`) reads the slots back.  Bit for
@@ -376,6 +376,28 @@ class Calibrator:
         N, H, W, _ = img.shape
         x = self._acts(N, H, W)["input"]
         imgmod.launch(self.device, 1.0, 0, 0, img, form, order, None, x, torch.cuda.current_stream(self.device))
+        self.last_input = x
+        return self._forward_device(x, out)
+
+    def enqueue_hr(self, hr_u8: torch.Tensor, order: str = "rgb", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """8-bit HR images (N, H, W, 3) / (H, W, 3) torch.uint8 on the device, in `order`, sizes multiples of the net's PixelShuffle
+        factor r: downscaled bicubically by r and decoded in one kernel (sesrq.downscale) into the fp32 input enqueue_image forms
+        from the LR file, and calibrated as enqueue() does."""
+        from . import downscale as ds
+        self._check_device_pass("enqueue_hr")
+        form = ds.Y if self.in_channels == 1 else ds.RGB if self.in_channels == 3 else None
+        if form is None:
+            raise ValueError(f"Calibrator.enqueue_hr: an 8-bit image feeds 1- or 3-channel nets; this one takes {self.in_channels}")
+        r = self.pixel_shuffle
+        if r not in ds.FACTORS:
+            raise ValueError(f"Calibrator.enqueue_hr: the HR image is downscaled by the net's PixelShuffle factor, 2 or 4; this net's is {r}")
+        ds._order(order)
+        img = ds.hr_images(hr_u8, r, who="Calibrator.enqueue_hr")
+        ds._on_device(img, self.device, "Calibrator.enqueue_hr")
+        img = img.contiguous()
+        N, H, W, _ = img.shape
+        x = self._acts(N, H // r, W // r)["input"]
+        ds.launch(self.device, 1.0, 0, 0, img, order, r, form, None, None, x, torch.cuda.current_stream(self.device))
         self.last_input = x
         return self._forward_device(x, out)
 

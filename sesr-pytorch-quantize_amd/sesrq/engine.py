@@ -411,6 +411,40 @@ class Engine:
         return self._run(img, _lib.F32 if fp else _lib.I8, want_q, want_f, out_q if want_q else None, out_f if want_f else None,
                          stream, slot, (N, cin, H, W), decode)
 
+    def forward_hr(self, hr_u8: torch.Tensor, order: str = "rgb", want_q: bool = True, want_f: bool = True, out_q=None, out_f=None,
+                   stream=None, slot: int = 0):
+        """hr_u8: (N, H, W, 3) or (H, W, 3) torch.uint8 HR images (the ground truths) on self.device, interleaved in `order`, H and W
+        multiples of the net's PixelShuffle factor r -> (q int8 | None, y float32 | None) of the output shape (N, C, H, W).
+
+        forward_image of the bicubically downscaled image, without that image: one kernel (libsesrq_downscale.so, sesrq.downscale)
+        downscales the HR image by r and decodes the result into this net's kept input buffer, exactly as forward_image decodes an LR
+        file -- q0, or the fp32 frame for an anchor_add engine and for a net narrower than 8 bits.  r and the form come from the net:
+        x4 luma (1 channel in), x2 RGB (3 channels in).  Launches, streams, slots and the refusals of caller outputs are
+        forward_image's."""
+        from . import downscale as ds
+        cin, r = self.bundle.in_channels, self.bundle.pixel_shuffle
+        if cin not in (1, 3):
+            raise ValueError(f"forward_hr: an 8-bit image feeds 1- or 3-channel nets; this one takes {cin}")
+        if r not in ds.FACTORS:
+            raise ValueError(f"forward_hr: the HR image is downscaled by the net's PixelShuffle factor, 2 or 4; this net's is {r}")
+        if self.i8_in_scale != 0.0:
+            raise ValueError("forward_hr: this engine takes an upstream net's int8 output as input (upstream=...), not an image")
+        if not (want_q or want_f):
+            raise ValueError("forward_hr: ask for the int8 output, the fp32 output or both")
+        ds._order(order)
+        f = ds.Y if cin == 1 else ds.RGB
+        img = ds.hr_images(hr_u8, r, who="forward_hr")
+        ds._on_device(img, self.device, "forward_hr")
+        N, H, W, _ = img.shape
+        # the buffer holds q0, or the fp32 frame an anchored forward adds back / a narrow net quantises itself
+        fp = self.anchor_add or self.quan_bits != 8
+
+        def decode(src, buf, st):
+            ds.launch(self.device, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, src, order, r, f, None,
+                      None if fp else buf, buf if fp else None, st)
+        return self._run(img, _lib.F32 if fp else _lib.I8, want_q, want_f, out_q if want_q else None, out_f if want_f else None,
+                         stream, slot, (N, cin, H // r, W // r), decode)
+
     def forward_colour(self, img_u8: torch.Tensor, order: str = "rgb", out=None, stream=None, slot: int = 0):
         """img_u8: (N, H, W, 3) or (H, W, 3) torch.uint8 colour images on self.device, interleaved in `order` -> the colour
         super-resolved images (N, r H, r W, 3) torch.uint8 in the same order, r the net's PixelShuffle factor.

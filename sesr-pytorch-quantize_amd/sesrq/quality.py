@@ -179,7 +179,7 @@ def score_anchored(pred, lr, gt, stream=None):
     return _run(_so, anchored_lib().sesrq_eval_anchored, d, (pred, lr, gt), (N, Ch, H, W), stream)
 
 
-KINDS = ("f32", "raw", "image")
+KINDS = ("f32", "raw", "image", "hr")
 
 
 def check_mosaic_format(mflag: int, fmt):
@@ -206,11 +206,16 @@ def check_calibration_input(calibrator, mflag: int, kind: str, scored: bool = Tr
             raise ValueError(f"MFLAG {mflag}: raw RGGB frames feed the denoise / demosaic nets (MFLAG 1, 2, 3, 4)")
         if cin != 3:
             raise ValueError(f"a raw RGGB frame feeds 3-channel nets; this one takes {cin}")
-    if kind == "image":
+    if kind in ("image", "hr"):
         from . import image as imgmod
         f = imgmod.form_of(mflag)
         if imgmod.CHANNELS[imgmod._form(f)] != cin:
             raise ValueError(f"MFLAG {mflag} images give {imgmod.CHANNELS[imgmod._form(f)]} channel(s); this net takes {cin}")
+    if kind == "hr":           # the HR image is the input's source: downscaled by the MFLAG's factor, which must be the net's
+        from . import downscale
+        r = getattr(calibrator, "pixel_shuffle", None)
+        if r is not None and r != downscale.factor_of(mflag):
+            raise ValueError(f"MFLAG {mflag} downscales the HR image by {downscale.factor_of(mflag)}; this net upscales by {r}")
     if calibrator.method != "minmax":
         raise ValueError("evaluate_calibration: the device-resident calibration pass computes the reference's min/max ranges only; "
                          "method='entropy' runs on the host pass (Calibrator.observe)")
@@ -225,7 +230,9 @@ def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32",
     kind "f32": frames (1, Cin, H, W) float32 (or one (N, Cin, H, W) tensor, taken frame by frame); "raw": (1, 1, H, W) / (1, H, W) /
     (H, W) uint16 RGGB frames; "image": (H, W, 3) / (1, H, W, 3) uint8 LR images in `order`.  gts, numpy or torch, by dtype: float32
     frames of the output shape, uint16 RGB frames (3, H, W) / (1, 3, H, W) (sesrq.raw.load_gt), or uint8 HR images in `order`
-    (sesrq.image.load_gt).  fmt: the sesrq.sensor.Format of "raw" frames and uint16 ground truths (default: 12-bit RGGB, sesrq.raw).
+    (sesrq.image.load_gt); "hr": (H, W, 3) / (1, H, W, 3) uint8 HR images in `order`, sizes multiples of the net's factor -- each is
+    its own ground truth and the source of its input (Calibrator.enqueue_hr; the matching entry of gts is not read).
+    fmt: the sesrq.sensor.Format of "raw" frames and uint16 ground truths (default: 12-bit RGGB, sesrq.raw).
     noise: a sesrq.noise.NoiseModel for "raw" frames -- shot and read noise added on the device, consecutive frames getting
     consecutive frame numbers from the model's frame0 (the reference's TEST_RAW_ADD_NOISE).
     Returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
@@ -249,6 +256,9 @@ def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32",
             else:
                 y = calibrator.enqueue_raw(x, fmt=fmt, noise=noise.advance(done))
                 done += y.shape[0]
+        elif kind == "hr":     # one upload: the HR image is downscaled and decoded on the device, and is the ground truth
+            y = calibrator.enqueue_hr(x, order=order)
+            g = x
         else:
             y = calibrator.enqueue_image(x, order=order)
         g = _lib.host_tensor(g)
@@ -364,3 +374,26 @@ def evaluate_image(engine, lr_imgs, hr_imgs, mflag: int, order: str = "rgb"):
         q, y = engine.forward_image(lr, order=order, want_q=not fp32, want_f=fp32)
         return (y if fp32 else q), g
     return _evaluate(engine, mflag, zip(lr_imgs, hr_imgs), step)
+
+
+def evaluate_hr(engine, hr_imgs, mflag: int, order: str = "rgb"):
+    """evaluate_image without the LR files: per frame ONE upload, the uint8 HR image, which is both the ground truth
+    (sesrq.image.load_gt) and, downscaled bicubically by the net's factor and decoded in one kernel, the input
+    (Engine.forward_hr, sesrq.downscale); the output is scored as evaluate_image scores it -- MFLAG 5 the int8 output, MFLAG 6 the
+    anchored fp32 output (the engine must have been created with anchor_add=True).
+
+    hr_imgs: an iterable of (H, W, 3) / (1, H, W, 3) uint8 images (numpy or torch), in `order`, H and W multiples of the factor
+    (sesrq.downscale.modcrop).  One synchronisation at the end; returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
+    from . import downscale, image as imgmod
+    form_of(mflag)
+    imgmod.form_of(mflag)
+    r = downscale.factor_of(mflag)
+    if engine.bundle.pixel_shuffle != r:
+        raise ValueError(f"MFLAG {mflag} downscales the HR image by {r}; this net upscales by {engine.bundle.pixel_shuffle}")
+    dev = engine.device
+
+    def step(hr, _, fp32):
+        hr = _lib.host_tensor(hr).to(dev, non_blocking=True)
+        q, y = engine.forward_hr(hr, order=order, want_q=not fp32, want_f=fp32)
+        return (y if fp32 else q), imgmod.load_gt(hr, mflag, dev, order=order)
+    return _evaluate(engine, mflag, ((h, None) for h in hr_imgs), step)

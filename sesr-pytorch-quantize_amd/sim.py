@@ -11,6 +11,7 @@ test.py produced (an ``output_pt`` directory) or from a bundle/fixture file.
     python sim.py --mflag 5 --params tests/golden/sesr_x4.params.npz --input tests/golden/rand_SR_Input_80x960.npy
     python sim.py --mflag 6 --params ... --input LR.png --gt HR.png --save-png SR.png      # 8-bit images (MFLAG 5 / 6)
     python sim.py --mflag 5 --params ... --input LR.png --colour --save-png SR.png         # the x4 luma net's output in colour
+    python sim.py --mflag 6 --params ... --hr HR.png --save-lr LR.png                      # the HR image alone: input and ground truth
     python sim.py --mflag 1 --ckpt nr_G.pth --calib output_pt --input a_132_128.raw --gt gt16.npy     # nr: scored on the Bayer mosaic
 """
 import argparse
@@ -135,7 +136,7 @@ def main(argv=None):
     ap.add_argument("--ckpt", help="reference float checkpoint (.pth state_dict)")
     ap.add_argument("--params", help=".npz with collapsed float convs (+ calibrated domains)")
     ap.add_argument("--calib", help="output_pt directory written by the reference's test.py")
-    ap.add_argument("--input", required=True, help="frame tensor: .pt (torch) or .npy, shape (N,C,H,W) float32; or a 12-bit RGGB raw frame "
+    ap.add_argument("--input", help="frame tensor: .pt (torch) or .npy, shape (N,C,H,W) float32; or a 12-bit RGGB raw frame "
                                                    "<name>_<rows>_<cols>.raw (uint16), spread on the device into the reference's "
                                                    "3-channel input (self_dataset.py TestDataset); or an 8-bit LR image (.png, or a "
                                                    "uint8 .npy with --image), decoded on the device as self_dataset_sr.py does "
@@ -148,6 +149,13 @@ def main(argv=None):
     ap.add_argument("--colour", action="store_true", help="MFLAG 5 with an 8-bit LR image and --save-png: write the COLOUR image -- the "
                                                           "net's luma, the LR image's Cb / Cr upscaled bicubically, back to RGB "
                                                           "(sesrq.colour); without the flag the PNG is the grey luma, as the reference's")
+    ap.add_argument("--hr", help="MFLAG 5 / 6, in place of --input and --gt: an 8-bit HR image (.png, or a uint8 .npy with --image) that is "
+                                 "both the ground truth and, downscaled bicubically by the net's factor on the device, the input "
+                                 "(sesrq.downscale); the output is scored against it")
+    ap.add_argument("--modcrop", action=argparse.BooleanOptionalAction, default=True,
+                    help="crop the --hr image to multiples of 12 each way first (top left), as the datasets' GTmod12 folders were made "
+                         "(the default; --no-modcrop takes it as it is, its size must then be a multiple of the factor)")
+    ap.add_argument("--save-lr", help="with --hr: write the device-made LR image as an 8-bit PNG here")
     ap.add_argument("--save", help="write the float result here (.npy)")
     ap.add_argument("--gt", help="ground truth of the output shape (N,Cout,H*r,W*r) float32, .npy or .pt: score the output with the "
                                  "reference's PSNR / SSIM on the device (test.py:141-183) and print them as its loop does; a uint16 "
@@ -163,8 +171,19 @@ def main(argv=None):
     add_sensor_flags(ap)
     add_noise_flags(ap)
     args = ap.parse_args(argv)
-    fmt = sensor_format(args, "sim.py", [args.input])
-    noise_m = noise_model(args, "sim.py", [args.input])
+    if args.hr is None:
+        if args.input is None:
+            ap.error("the following arguments are required: --input")
+        if args.save_lr:
+            raise SystemExit("sim.py: --save-lr writes the LR image made from --hr")
+    else:
+        if args.input is not None or args.gt is not None:
+            raise SystemExit("sim.py: --hr is the input's source and the ground truth; give neither --input nor --gt with it")
+        if args.mflag not in (5, 6) or not is_image(args.hr, args.image):
+            raise SystemExit("sim.py: --hr takes an 8-bit HR image (.png, or a uint8 .npy with --image) for the super-resolution nets "
+                             "(--mflag 5 or 6)")
+    fmt = sensor_format(args, "sim.py", [args.input] if args.input else [])
+    noise_m = noise_model(args, "sim.py", [args.input] if args.input else [])
     if fmt is not None and args.gt:
         from sesrq import quality
         try:
@@ -182,17 +201,28 @@ def main(argv=None):
     model = splice(float_model(args.mflag, args.ckpt, args.params))
     from sesrq import _lib
     model.__dict__["sesrq_engine_option"] = _lib.ENGINE_NAMES[args.engine]
-    as_image = is_image(args.input, args.image)
+    as_image = args.hr is not None or is_image(args.input, args.image)
     if args.colour and not (args.mflag == 5 and as_image and args.save_png):
         raise SystemExit("sim.py: --colour rebuilds colour around the luma net: it needs --mflag 5, an 8-bit LR image as --input "
                          "(.png, or a uint8 .npy with --image) and --save-png")
-    lr_u8 = None
-    if not args.input.endswith(".raw") and not as_image:
+    lr_u8 = hr_u8 = None
+    if not as_image and not args.input.endswith(".raw"):
         inps = torch.load(args.input, weights_only=True, map_location="cpu") if args.input.endswith(".pt") else \
             torch.from_numpy(np.load(args.input))
     if not torch.cuda.is_available():
         raise SystemExit("sim.py: the integer path needs a HIP device (no CPU fallback)")
-    if args.input.endswith(".raw"):         # the reference's loop: raw frame -> sparse RGGB mosaic / 4095, clamped -> model(inps)
+    if args.hr is not None:                 # the HR image alone: its bicubic downscale, decoded in the same kernel -> model(inps)
+        from sesrq import downscale, image
+        r = downscale.factor_of(args.mflag)
+        hr = image.load_image(args.hr)
+        try:
+            hr_u8 = torch.from_numpy(np.ascontiguousarray(downscale.modcrop(hr, 12) if args.modcrop else hr)).cuda()
+            _, inps = downscale.decode(None, hr_u8, r, image.form_of(args.mflag), order=args.order, want_q=False, want_f=True)
+            if args.colour or args.save_lr:
+                lr_u8 = downscale.downscale(hr_u8, r, order=args.order)
+        except ValueError as e:
+            raise SystemExit(f"sim.py: {e}") from None
+    elif args.input.endswith(".raw"):       # the reference's loop: raw frame -> sparse RGGB mosaic / 4095, clamped -> model(inps)
         from sesrq import sensor           # fmt: a sensor's format (CFA order, levels, MIPI packing), or None for the reference's
         raw = torch.from_numpy(sensor.load_raw(args.input, fmt)).cuda()
         if noise_m is None:
@@ -214,6 +244,11 @@ def main(argv=None):
     if args.dump:
         STORE.save_output_pt(args.dump)
         print("dumped:", args.dump)
+    if args.hr is not None:
+        from sesrq import image
+        score_against(args.hr, gfake, inps, args.mflag, gts=image.load_gt(hr_u8, args.mflag, gfake.device, order=args.order))
+        if args.save_lr:
+            save_lr_png(args.save_lr, lr_u8, args.order)
     if args.gt:
         gts = None
         if is_image(args.gt, args.image):   # the HR image: the reference's gt formed on the device
@@ -307,6 +342,16 @@ def save_png(path, gfake, inps, mflag):
     for k in range(u8.shape[0]):
         image.save_png(path if u8.shape[0] == 1 else f"{stem}_{k}{ext or '.png'}", u8[k])
     print("png:", path, tuple(u8.shape))
+
+
+def save_lr_png(path, lr_u8, order):
+    """--save-lr: the LR image the device made from --hr, as an RGB PNG."""
+    from sesrq import image
+    u8 = (lr_u8.flip(-1) if order == "bgr" else lr_u8).cpu().numpy()          # PIL takes RGB bytes
+    stem, ext = os.path.splitext(path)
+    for k in range(u8.shape[0]):
+        image.save_png(path if u8.shape[0] == 1 else f"{stem}_{k}{ext or '.png'}", u8[k])
+    print("lr:", path, tuple(u8.shape))
 
 
 def save_colour_png(path, gfake, lr_u8, order):

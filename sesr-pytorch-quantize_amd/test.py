@@ -3,7 +3,7 @@ qmode = 0, :141-183 loop over calibration frames, :185-217 scale/zero derivation
 dataset is private; frames come from ``--frames`` (.npy / .pt, (N,C,H,W) float32, one batch per N), or from ``--input``: what
 sim.py reads -- 12-bit RGGB raw frames (``*.raw``, MFLAG 1 ... 4), 8-bit images (``.png``, or uint8 ``.npy`` with ``--image``; MFLAG
 5 / 6) or fp32 ``.npy`` / ``.pt`` frames -- decoded on the device and calibrated frame by frame without a host round trip
-(Calibrator.enqueue*).  With ``--gt`` every frame's mode-0 output is scored as the reference's loop scores it (each frame's PSNR, then
+(Calibrator.enqueue*), or from ``--hr``: 8-bit HR images alone, downscaled on the device.  With ``--gt`` every frame's mode-0 output is scored as the reference's loop scores it (each frame's PSNR, then
 the mean line) before the domains are printed -- not for MFLAG 1 (nr), whose mosaic metric the scored loop does not have: ``--mflag 1``
 calibrates without ``--gt``.
 
@@ -65,6 +65,11 @@ def main(argv=None):
     ap.add_argument("--gt", nargs="+", help="ground truths, one per --input file (or one batch .npy / .pt): score every frame's mode-0 "
                                            "output and print its PSNR and the mean line, as the reference's test.py does.  fp32 or "
                                            "uint16 RGB (N,3,H,W) .npy / .pt, or 8-bit HR images (.png, uint8 .npy with --image)")
+    ap.add_argument("--hr", nargs="+", help="MFLAG 5 / 6, in place of --input and --gt: 8-bit HR images (.png, or uint8 .npy with --image), "
+                                           "each both the ground truth and, downscaled bicubically by the net's factor on the device, "
+                                           "the input (sesrq.downscale); calibrated on the device-resident pass and scored")
+    ap.add_argument("--modcrop", action=argparse.BooleanOptionalAction, default=True,
+                    help="crop every --hr image to multiples of 12 each way first (top left), as the datasets' GTmod12 folders were made")
     ap.add_argument("--image", action="store_true", help="--input / --gt .npy files are uint8 (H, W, 3) or (N, H, W, 3) images")
     ap.add_argument("--order", choices=("rgb", "bgr"), default="rgb", help="byte order of uint8 .npy images (PNGs are read as RGB)")
     ap.add_argument("--method", default="minmax", choices=["minmax", "entropy"],
@@ -93,7 +98,11 @@ def main(argv=None):
     define.check()
     print("QUAN_BIT:", define.QUAN_BIT)
     STORE.clear()
-    if (args.frames is None) == (args.input is None):
+    if args.hr is not None:
+        if args.frames is not None or args.input is not None or args.gt is not None:
+            raise SystemExit("test.py: --hr images are the inputs' source and the ground truths; give none of --frames, --input and --gt "
+                             "with them")
+    elif (args.frames is None) == (args.input is None):
         raise SystemExit("test.py: give the frames with --frames or with --input (one of them)")
     if args.float_skip and args.skip_quant_scale is not None:
         raise SystemExit("test.py: --float-skip and --skip-quant-scale exclude each other")
@@ -109,7 +118,7 @@ def main(argv=None):
     print("skip_quant_scale:", skip_s if skip_s is not None else "none (float long skip)")
     model = splice_calibration(fmodel)
     model.__dict__["sesrq_skip_quant_scale"] = skip_s         # read by sesrq.lowering.lower_calibration
-    if args.input is not None or args.gt is not None:
+    if args.input is not None or args.gt is not None or args.hr is not None:
         return dataset_pass(args, model)
     frames = torch.load(args.frames, weights_only=True, map_location="cpu") if args.frames.endswith(".pt") else torch.from_numpy(np.load(args.frames))
     if not torch.cuda.is_available():
@@ -197,17 +206,28 @@ def dataset_pass(args, model):
     if args.method != "minmax":
         raise SystemExit("test.py: --input / --gt run the device-resident pass, which computes the reference's min/max ranges only; "
                          "use --frames for --method entropy")
-    if args.frames is not None:
+    if args.hr is not None:
+        from sesrq import downscale
+        kind, frames = load_inputs(args.hr, args.image)
+        try:
+            if kind != "image":
+                raise ValueError("--hr takes 8-bit HR images (.png, or uint8 .npy with --image)")
+            kind, frames = "hr", [downscale.modcrop(f, 12) if args.modcrop else f for f in frames]
+            for f in frames:       # the size refusal, before any device work
+                downscale.hr_images(torch.from_numpy(np.ascontiguousarray(f)), downscale.factor_of(args.mflag), who="--hr")
+        except ValueError as e:
+            raise SystemExit(f"test.py: {e}") from None
+    elif args.frames is not None:
         kind, frames = "f32", [f.astype(np.float32) for f in _frames_of(sim.load_frames(args.frames), False)]
     else:
         kind, frames = load_inputs(args.input, args.image, args.fmt)
     cin = next(m for m in model.modules() if isinstance(m, torch.nn.Conv2d)).in_channels
     try:       # the refusals of forward_raw / forward_image, before any device work
         quality.check_calibration_input(types.SimpleNamespace(in_channels=cin, method=args.method), args.mflag, kind,
-                                        scored=args.gt is not None)
+                                        scored=args.gt is not None or args.hr is not None)
     except ValueError as e:
         raise SystemExit(f"test.py: {e}") from None
-    gts = load_gts(args.gt, kind, args.image) if args.gt else None
+    gts = frames if kind == "hr" else load_gts(args.gt, kind, args.image) if args.gt else None
     if gts is not None and len(gts) != len(frames):
         raise SystemExit(f"test.py: {len(frames)} input frames, {len(gts)} ground truths")
     if not torch.cuda.is_available():
