@@ -258,7 +258,11 @@ class Engine:
         and the stream entered; then `decode(src, inp, stream)` fills a kept (N, C, H, W) input buffer of dtype `dt` from `src`
         (a front end's launch; without it `src` is the input), and sesrq_forward runs on that input."""
         with torch.cuda.device(self.device):
-            src = src.contiguous()
+            if isinstance(src, torch.Tensor):
+                src = src.contiguous()
+                planes = (src,)
+            else:                            # a video surface: planes with pitches, read where they lie
+                planes = tuple(src.tensors())
             if decode is None:
                 inp, (N, _, H, W) = src, src.shape
             else:
@@ -275,7 +279,7 @@ class Engine:
             if want_f and out_f is None:
                 out_f = torch.empty(shp, dtype=torch.float32, device=self.device)
             ws = self.workspace(N, H, W, slot)
-            st = _lib.enter_stream(self.device, stream, src, inp, out_q, out_f, ws)
+            st = _lib.enter_stream(self.device, stream, *planes, inp, out_q, out_f, ws)
             if decode is not None:
                 decode(src, inp, st)
             rc = _lib.lib().sesrq_forward(self._h, inp.data_ptr(), dt, out_q.data_ptr() if out_q is not None else None,
@@ -475,6 +479,43 @@ class Engine:
             st = _lib.enter_stream(self.device, stream, img, q, out)
             colour.launch(q, b.scale[b.L], b.zero[b.L], img, order, r, out, st)
         return out
+
+    def forward_video(self, src, out=None, want_q: bool = False, stream=None, slot: int = 0):
+        """src: a sesrq.video.Surface of N YUV 4:2:0 frames (NV12 or I420) on self.device -> the super-resolved frames as a Surface of
+        r H x r W, r the net's PixelShuffle factor; with want_q also the net's luma: (surface, luma).
+
+        For luma nets (1 channel in, 1 channel out: SESR-x4, MFLAG 5): the Y plane is decoded through its pitch into this net's kept
+        q0 buffer (libsesrq_video.so, sesrq.video) and run through the same forward as an int8 q0 input; the fused export then writes
+        the net's luma as bytes and the surface's chroma planes, upscaled bicubically, as a 4:2:0 surface -- no RGB on the way.  The
+        luma is the net's int8 output; an anchor_add engine and a net narrower than 8 bits take the fp32 frame and give the fp32
+        output, as forward_image does.  out: a Surface of the output size on this device to write into (its pixel format decides;
+        without it the output has src's).  All launches go to `stream` (default: current), ordered as forward() orders them; give
+        concurrent in-flight frames different slots."""
+        from . import video
+        b = self.bundle
+        if b.in_channels != 1 or b.out_channels != 1:
+            raise ValueError(f"forward_video: a video surface feeds a luma net (1 channel in, 1 out); this net takes {b.in_channels} "
+                             f"and gives {b.out_channels}")
+        r = video._factor(b.pixel_shuffle)
+        if self.i8_in_scale != 0.0:
+            raise ValueError("forward_video: this engine takes an upstream net's int8 output as input (upstream=...), not a surface")
+        s = video._on_device(src, self.device, "forward_video")
+        N, H, W = s.N, s.H, s.W
+        if out is not None:
+            video.check_out(out, None, N, r * H, r * W, self.device, "forward_video")
+        # the buffer holds q0, or the fp32 frame an anchored forward adds back / a narrow net quantises itself
+        fp = self.anchor_add or self.quan_bits != 8
+
+        def decode(surf, buf, st):
+            video.launch_decode(self.device, b.scale[0], b.zero[0], self.exact_div, surf, None if fp else buf, buf if fp else None, st)
+        with torch.cuda.device(self.device):
+            q, f = self._run(s, _lib.F32 if fp else _lib.I8, not fp, fp, None, None, stream, slot, (N, 1, H, W), decode)
+            luma = f if fp else q
+            if out is None:
+                out = video.Surface.alloc(s.fmt, N, r * H, r * W, self.device)
+            st = _lib.enter_stream(self.device, stream, luma, *s.planes()[1:], *out.planes())
+            video.launch_export(luma, b.scale[b.L], b.zero[b.L], s, r, out, st)
+        return (out, luma) if want_q else out
 
     def submission(self, frames, outs_q, streams, outs_f=None, group: int = 1):
         """A prepared batch of independent forwards for sesrq_forward_many: frame k = frames[k] -> outs_q[k] (/ outs_f[k]; either may be None) on

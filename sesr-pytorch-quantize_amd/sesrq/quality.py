@@ -376,6 +376,24 @@ def evaluate_image(engine, lr_imgs, hr_imgs, mflag: int, order: str = "rgb"):
     return _evaluate(engine, mflag, zip(lr_imgs, hr_imgs), step)
 
 
+def evaluate_video(engine, lr_surfaces, hr_surfaces, mflag: int = 5):
+    """evaluate_image for YUV 4:2:0 video (sesrq.video): per LR Surface (a frame or a batch, host or device) its Y plane is uploaded
+    with the surface at 1.5 B/px, decoded on the device into the net's q0 and run forward from int8; the ground truth is the HR
+    Surface's Y plane decoded to fp32 by the same per-code table, and the int8 output is scored as evaluate() scores it.  The luma
+    net only (MFLAG 5).  One synchronisation at the end; returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
+    from . import video
+    if mflag != 5:
+        raise ValueError(f"MFLAG {mflag}: video surfaces feed the luma net (MFLAG 5: SESR-x4, Y in, Y out)")
+    dev = engine.device
+
+    def step(lr, hr, fp32):
+        q0, _ = video.decode(engine, video.to_device(lr, dev))
+        _, g = video.decode(None, video.to_device(hr, dev), want_q=False, want_f=True)
+        q, _ = engine.forward(q0, want_q=True, want_f=False)
+        return q, g
+    return _evaluate(engine, mflag, zip(lr_surfaces, hr_surfaces), step)
+
+
 def evaluate_hr(engine, hr_imgs, mflag: int, order: str = "rgb"):
     """evaluate_image without the LR files: per frame ONE upload, the uint8 HR image, which is both the ground truth
     (sesrq.image.load_gt) and, downscaled bicubically by the net's factor and decoded in one kernel, the input

@@ -12,6 +12,7 @@ test.py produced (an ``output_pt`` directory) or from a bundle/fixture file.
     python sim.py --mflag 6 --params ... --input LR.png --gt HR.png --save-png SR.png      # 8-bit images (MFLAG 5 / 6)
     python sim.py --mflag 5 --params ... --input LR.png --colour --save-png SR.png         # the x4 luma net's output in colour
     python sim.py --mflag 6 --params ... --hr HR.png --save-lr LR.png                      # the HR image alone: input and ground truth
+    python sim.py --mflag 5 --params ... --yuv LR.yuv --size 960x540 --pix-fmt nv12 --save-yuv SR.yuv     # YUV 4:2:0 video in and out
     python sim.py --mflag 1 --ckpt nr_G.pth --calib output_pt --input a_132_128.raw --gt gt16.npy     # nr: scored on the Bayer mosaic
 """
 import argparse
@@ -170,8 +171,13 @@ def main(argv=None):
                          "dot4 kernels; mfma-q runs the width-aware MFMA kernels and the fused trio (same bits, several times the rate)")
     add_sensor_flags(ap)
     add_noise_flags(ap)
+    add_video_flags(ap)
     args = ap.parse_args(argv)
-    if args.hr is None:
+    yuv = video_args(args)
+    if yuv is not None:                     # --yuv stands in place of --input / --hr (video_args has refused them beside it)
+        if args.save_lr:
+            raise SystemExit("sim.py: --save-lr writes the LR image made from --hr")
+    elif args.hr is None:
         if args.input is None:
             ap.error("the following arguments are required: --input")
         if args.save_lr:
@@ -201,6 +207,10 @@ def main(argv=None):
     model = splice(float_model(args.mflag, args.ckpt, args.params))
     from sesrq import _lib
     model.__dict__["sesrq_engine_option"] = _lib.ENGINE_NAMES[args.engine]
+    if yuv is not None:                     # a raw .yuv sequence: decoded, run and exported batch by batch
+        if not torch.cuda.is_available():
+            raise SystemExit("sim.py: the integer path needs a HIP device (no CPU fallback)")
+        return run_yuv(args, yuv, model, keep=argv is not None)
     as_image = args.hr is not None or is_image(args.input, args.image)
     if args.colour and not (args.mflag == 5 and as_image and args.save_png):
         raise SystemExit("sim.py: --colour rebuilds colour around the luma net: it needs --mflag 5, an 8-bit LR image as --input "
@@ -271,6 +281,93 @@ def add_sensor_flags(ap):
     ap.add_argument("--packing", choices=("u16", "raw10", "raw12"), default=None,
                     help="how *.raw inputs hold their pixels: uint16 containers (default), MIPI RAW10 (4 px in 5 bytes) or RAW12 "
                          "(2 px in 3 bytes); a file is <rows> x the unpadded row bytes")
+
+
+YUV_BATCH = 8          # frames of a .yuv sequence that go through as one batch
+
+
+def add_video_flags(ap):
+    """--yuv / --size / --pix-fmt / --frames / --save-yuv / --out-pix-fmt / --gt-yuv: YUV 4:2:0 video through the luma net (sesrq.video)."""
+    ap.add_argument("--yuv", help="MFLAG 5, in place of --input: a raw .yuv file of unpadded 8-bit 4:2:0 frames (with --size and --pix-fmt); "
+                                  "the Y plane is the net's input, decoded on the device")
+    ap.add_argument("--size", metavar="WxH", help="frame size of --yuv (luma; odd sizes are legal)")
+    ap.add_argument("--pix-fmt", choices=("nv12", "i420"), default=None, help="pixel format of --yuv and --gt-yuv")
+    ap.add_argument("--frames", metavar="A:B", help="with --yuv: run frames A .. B-1 of the file only (default: all)")
+    ap.add_argument("--save-yuv", help="with --yuv: write the super-resolved sequence here as a raw .yuv file -- the net's luma as bytes, "
+                                       "the input's chroma upscaled bicubically (sesrq.video.export)")
+    ap.add_argument("--out-pix-fmt", choices=("nv12", "i420"), default=None, help="pixel format of --save-yuv (default: --pix-fmt)")
+    ap.add_argument("--gt-yuv", help="with --yuv: the HR sequence (same frames, r times the size, --pix-fmt); its Y plane is the ground "
+                                     "truth the output is scored against")
+
+
+def video_args(args):
+    """(W, H, (first, end) | None) of a --yuv run, or None without --yuv; a flag error ends the program."""
+    rest = [k for k in ("size", "pix_fmt", "frames", "save_yuv", "out_pix_fmt", "gt_yuv") if getattr(args, k) is not None]
+    if args.yuv is None:
+        if rest:
+            raise SystemExit("sim.py: --size, --pix-fmt, --frames, --save-yuv, --out-pix-fmt and --gt-yuv belong to --yuv")
+        return None
+    if args.mflag != 5 or args.input is not None or args.hr is not None or args.gt is not None or args.save_png or args.colour:
+        raise SystemExit("sim.py: --yuv feeds the luma net (--mflag 5) in place of --input / --hr; its ground truth is --gt-yuv, its "
+                         "output --save-yuv")
+    if args.size is None or args.pix_fmt is None:
+        raise SystemExit("sim.py: --yuv needs --size WxH and --pix-fmt")
+    try:
+        W, H = (int(v) for v in args.size.lower().split("x"))
+        span = None
+        if args.frames is not None:
+            a, b = args.frames.split(":")
+            span = (int(a or 0), int(b) if b else None)
+    except ValueError:
+        raise SystemExit("sim.py: --size is WxH, --frames is A:B") from None
+    return W, H, span
+
+
+def run_yuv(args, yuv, model, keep=False):
+    """The --yuv run: the sequence goes through in batches of YUV_BATCH frames -- Y plane decoded on the device -> model(inps) ->
+    scored against --gt-yuv's Y plane, exported with the input's chroma to --save-yuv.  Prints what the image path prints.
+    A batch's fp32 output (33 MB a 4K frame) is dropped once it is scored and saved, so device memory does not grow with the
+    sequence: only a caller from Python (keep: main(argv) returns the whole output, on the device) and --save (host copies) hold it."""
+    from sesrq import quality, video
+    W, H, span = yuv
+    dev = torch.device("cuda", torch.cuda.current_device())
+    try:
+        lr = video.load_yuv(args.yuv, W, H, args.pix_fmt, span)
+        r = model._sesrq_engine(dev).bundle.pixel_shuffle
+        gt = video.load_yuv(args.gt_yuv, r * W, r * H, args.pix_fmt, span) if args.gt_yuv else None
+        if gt is not None and gt.N != lr.N:
+            raise ValueError(f"{args.gt_yuv}: {gt.N} frames, {args.yuv} has {lr.N}")
+        outs, rows, shape = [], [], None
+        for a in range(0, lr.N, YUV_BATCH):
+            part = video.to_device(lr[a:a + YUV_BATCH], dev)
+            _, inps = video.decode(None, part, want_q=False, want_f=True)
+            gfake = model(inps)
+            shape = (a + gfake.shape[0],) + tuple(gfake.shape[1:])
+            if keep:
+                outs.append(gfake)
+            elif args.save:
+                outs.append(gfake.cpu())
+            if gt is not None:
+                _, g = video.decode(None, video.to_device(gt[a:a + YUV_BATCH], dev), want_q=False, want_f=True)
+                rows.append(quality.score(gfake, g, args.mflag))
+            if args.save_yuv:
+                video.save_yuv(args.save_yuv, video.export(gfake, part, r, fmt=args.out_pix_fmt or args.pix_fmt), append=a > 0)
+    except ValueError as e:
+        raise SystemExit(f"sim.py: {e}") from None
+    gfake = torch.cat(outs) if outs else None
+    torch.cuda.synchronize()
+    banner(args.mflag)
+    print("output:", shape, "engines:", model._sesrq_engine(dev).layer_engines())
+    if args.save:
+        np.save(args.save, gfake.cpu().numpy())
+    if rows:
+        res = torch.cat(rows).cpu().numpy()
+        for _, psnr, _ in res:
+            print(float(psnr))
+        print(quality.TASKS[args.mflag] + ' mean psnr is: ', float(res[:, 1].sum()) / len(res), ' ssim is: ', float(res[:, 2].sum()) / len(res))
+    if args.save_yuv:
+        print("yuv:", args.save_yuv, (shape[0], shape[2], shape[3]), args.out_pix_fmt or args.pix_fmt)
+    return gfake if keep else None
 
 
 def add_noise_flags(ap):
