@@ -141,16 +141,25 @@ class Expect:
     """The expected output of a case on the device: the small oracle output and the index vectors of both axes; pieces are gathered
     on demand.  tiled=False: the gather map of the convolution nets (out_map).  tiled=True: a pointwise operation on a frame tiled from
     a (PY, PX) block -- output pixel (y, x) is pixel (y mod PY, x mod PX) of the small output, whose own size is the period (the row
-    indices are formed band by band: the frame may have 2^31 rows)."""
+    indices are formed band by band: the frame may have 2^31 rows).  my, mx: the index vectors of the output's rows and columns into
+    the small output, given outright (an operation whose output axes are not H r and W r long: a plane cropped from the upscaled one);
+    H, W and r are then not looked at."""
 
-    def __init__(self, small, H, W, r, dev, words=True, tiled=False):
+    def __init__(self, small, H, W, r, dev, words=True, tiled=False, my=None, mx=None):
         import torch
         self.small = torch.from_numpy(np.array(small, copy=True)).to(dev)
         self.words = words
         if self.small.dtype == torch.float32 and words:
             self.small = self.small.view(torch.int32)            # fp32 is compared as words (words=False: as values, -0.0 == 0.0)
         self.Hr, self.Wr = H * r, W * r
-        if tiled:
+        if my is not None or mx is not None:
+            assert my is not None and mx is not None and not tiled
+            assert int(np.max(my)) < self.small.shape[2] and int(np.max(mx)) < self.small.shape[3]
+            self.Hr, self.Wr = len(my), len(mx)
+            ty = torch.from_numpy(np.asarray(my, np.int64)).to(dev)
+            self.rows = lambda r0, r1: ty[r0:r1]
+            self.mx = torch.from_numpy(np.asarray(mx, np.int64)).to(dev)
+        elif tiled:
             PY, PX = self.small.shape[2], self.small.shape[3]
             self.rows = lambda r0, r1: torch.arange(r0, r1, device=dev) % PY
             self.mx = torch.arange(self.Wr, device=dev) % PX

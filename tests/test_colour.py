@@ -9,6 +9,8 @@ comparison is exact and covers every byte; frames are small.
   luma extremes    every int8 code under three output domains; fp32 specials and values on rounding ties of step 4
   caller buffers   every buffer at odd addresses in a canary-filled arena: the same bytes, no canary touched
   large output     one batch whose output crosses 2^32 bytes
+  sweeps           (tests/test_resampler_sweep_device.py) every 4-tuple of the cube corners and mid-grey as the taps of each pass
+  strips           (tests/test_resampler_limits.py) one LR row and one LR column, one and two wide, of 2^22 + 5 pixels, r = 2 and 4
   forward_colour   on the golden LR frames, a side stream, a caller's out, the refusals; sim.py --colour --save-png
   instances        LAST: every instantiation was launched by a checked case"""
 import json

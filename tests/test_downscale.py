@@ -13,6 +13,8 @@ byte and every fp32 word; frames are small.
   engine           forward_hr == forward_image of the oracle's LR image; evaluate_hr == evaluate_image(oracle LR, HR);
                    Calibrator.enqueue_hr == enqueue_image on the oracle LR; sim.py --hr and --save-lr
   refusals         the C ABI's, on pointers that are never dereferenced
+  sweeps           (tests/test_resampler_sweep_device.py) every reachable sum of the vertical and of the horizontal pass, r = 2 and 4
+  strips           (tests/test_resampler_limits.py) one LR row and one LR column, one and two wide, of 2^22 + 5 pixels, r = 2 and 4
   instances        LAST: every instantiation was launched by a checked case"""
 import json
 import os

@@ -14,6 +14,9 @@ comparison is exact and covers every byte; frames are small.
                    byte of a row or between frames written, inputs unchanged
   sibling          the exported Y plane equals sesrq.image.export at C = 1 of the same luma
   large output     one batch whose output surface crosses 2^32 bytes
+  sweeps           (tests/test_resampler_sweep_device.py) both edges of every reachable Q6 value of each pass at every phase
+  loop, strips     (tests/test_resampler_limits.py) the decode's loop into its third trip; one LR row and one LR column, one and two
+                   wide, of 2^22 + 5 pixels through the export, r = 2 and 4
   forward_video    on the golden LR frames, a side stream, a caller's out, the fp32 branch on an anchored engine, the refusals;
                    evaluate_video; sim.py --yuv --save-yuv
   instances        LAST: every instantiation was launched by a checked case"""
