@@ -1,5 +1,8 @@
 // libsesrq_colour.so: colour out of the luma super-resolution nets (include/sesrq_colour.h, which fixes the arithmetic).  A library of
-// its own: it links nothing of libsesrq.so or libsesrq_image.so and registers nothing in their instance tables.
+// its own: it links nothing of libsesrq.so or libsesrq_image.so and registers nothing in their instance tables.  The weight
+// table and the row padding are sesrq_chroma_upscale.h's, which the video library uses too; the Q6 chroma of
+// RGB bytes, the wave-uniform phases, the luma load and the two passes (twins of the video export's: see that header), the colour
+// matrix and the 48-byte store are this file's.
 //
 // The net super-resolves Y; Cb and Cr of the LR image are upscaled bicubically (Keys a = -1/2, exact integers) and YCbCr goes back to
 // RGB bytes, in ONE kernel on the HR side: per output pixel 1 (int8) or 4 (fp32) bytes of Y and 3 / r^2 bytes of the LR image are
@@ -22,23 +25,21 @@
 
 #include "sesrq_colour.h"
 #include "sesrq_side.h"
+#include "sesrq_chroma_upscale.h"
 
 namespace sesrq_colk {
 
+using sesrq_chroma::HALO;
+using sesrq_chroma::SEG;                                    // output pixels per lane
+using sesrq_chroma::first_tap;
+using sesrq_chroma::half_of;
+using sesrq_chroma::weight;
+using sesrq_chroma::weight_of;
+
 constexpr int OUT_W = SESRQ_COLOUR_TILE_OUT_W, OUT_H = SESRQ_COLOUR_TILE_OUT_H;      // a workgroup's output tile, at r = 2 and 4
-constexpr int HALO = 2;
-constexpr int SEG = 16;                                     // output pixels per lane
 constexpr int CODES = 256;
 constexpr int CHROMA_THREADS = 256;
 constexpr int CHROMA_BLOCKS = 2048;
-
-// The Keys a = -1/2 weights x 1024 of phase phi (rows) and the offset of tap 0 from j; r = 4: rows 0 .. 3, r = 2: rows 4, 5.
-__host__ __device__ constexpr int weight(int r, int phi, int k) {
-    constexpr int W4[4][4] = {{-45, 399, 745, -75}, {-7, 93, 987, -49}, {-49, 987, 93, -7}, {-75, 745, 399, -45}};
-    constexpr int W2[2][4] = {{-24, 232, 888, -72}, {-72, 888, 232, -24}};
-    return r == 4 ? W4[phi][k] : W2[phi][k];
-}
-__host__ __device__ constexpr int first_tap(int r, int phi) { return 2 * phi < r ? -2 : -1; }
 
 struct ExportArgs {
     const void *y;
@@ -92,17 +93,6 @@ __global__ __launch_bounds__(CHROMA_THREADS) void colour_chroma(ChromaArgs a) {
     }
 }
 
-// the weight of tap k of a lane's own phase
-template <int R>
-__device__ inline int weight_of(int phi, int k) {
-    int w = weight(R, 0, k);
-#pragma unroll
-    for (int q = 1; q < R; ++q) w = phi == q ? weight(R, q, k) : w;
-    return w;
-}
-
-__device__ inline int half_of(unsigned w, int hi) { return hi ? (int)w >> 16 : (int)(short)(w & 0xffffu); }
-
 // steps 3 and 4 up to a: a = 1.16438356 (clip(p, 0, 1) * 255 - 16), every operation rounded; a NaN p gives a(0)
 __device__ inline float luma_term(float p) {
     const float yy = __fmul_rn(fminf(fmaxf(p, 0.f), 1.f), 255.f);
@@ -115,7 +105,7 @@ struct Shape {
     static constexpr int SW = TW + 2 * HALO, SH = TH + 2 * HALO;   // the staged tile
     static constexpr int RUNS = OUT_W / SEG;
     static constexpr int THREADS = RUNS * OUT_H;                   // a lane a run: 256
-    static constexpr int HWORDS = OUT_W / 2 + 2;                   // words per row of the horizontal pass, padded: a half wave's 4 rows x 8 runs of 8-byte reads fill the 64 banks
+    static constexpr int HWORDS = sesrq_chroma::hwords(OUT_W);     // words per row of the horizontal pass
     static constexpr int STAGE = (SW * SH + THREADS - 1) / THREADS;
 };
 static_assert(Shape<4>::TW == SESRQ_COLOUR_TILE_W && Shape<4>::TH == SESRQ_COLOUR_TILE_H, "the header's r = 4 tile");
@@ -235,7 +225,7 @@ __global__ __launch_bounds__(Shape<R>::THREADS, 8) void colour_export(ExportArgs
     if (!live) return;
 
     // the vertical pass over four rows of the horizontal pass and the colour matrix, four pixels at a time
-    const int r0 = li + HALO + (2 * phi < R ? -2 : -1);
+    const int r0 = li + HALO + first_tap(R, phi);
     int wy[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) wy[k] = weight_of<R>(phi, k);
@@ -293,6 +283,8 @@ __global__ __launch_bounds__(Shape<R>::THREADS, 8) void colour_export(ExportArgs
 
 using namespace sesrq_colk;
 
+static_assert(SESRQ_COLOUR_F32 == LUMA_F32 && SESRQ_COLOUR_I8 == LUMA_I8, "check_luma_export's y_dtype");
+
 enum { K_Q2 = 0, K_Q4, K_F2, K_F4, K_CHROMA, K_COUNT };
 static const char *const kNames[K_COUNT] = {"colour_export<i8,r2>", "colour_export<i8,r4>", "colour_export<f32,r2>",
                                             "colour_export<f32,r4>", "colour_chroma"};
@@ -331,44 +323,28 @@ extern "C" int sesrq_colour_chroma(const uint8_t *img, int order, int16_t *cbcr,
     const size_t want = (a.HW + CHROMA_THREADS - 1) / CHROMA_THREADS;
     const int grid = (int)(want < (size_t)CHROMA_BLOCKS ? want : (size_t)CHROMA_BLOCKS);
     colour_chroma<<<grid, CHROMA_THREADS, 0, static_cast<hipStream_t>(stream)>>>(a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("sesrq_colour_chroma: kernel launch: %s", hipGetErrorString(e));
-    ++g_count.launches[K_CHROMA];
-    return 0;
+    return launched("sesrq_colour_chroma", g_count, K_CHROMA);
 }
 
 extern "C" int sesrq_colour_export(const void *y, int y_dtype, float scale, int zero, const uint8_t *img, int order, int r,
                                    uint8_t *out, int N, int H, int W, void *stream) {
     g_err[0] = 0;
     const char *who = "sesrq_colour_export";
-    if (!y) return fail("%s: y is NULL", who);
+    ExportArgs a;
+    if (check_luma_export(who, y, y_dtype, scale, zero, r, N, H, W, OUT_W, OUT_H, &a.tiles_x, &a.tiles_y)) return 1;
     if (!img) return fail("%s: img is NULL", who);
     if (!out) return fail("%s: out is NULL", who);
-    if (y_dtype != SESRQ_COLOUR_F32 && y_dtype != SESRQ_COLOUR_I8) return fail("%s: y_dtype %d (0 = fp32, 1 = int8)", who, y_dtype);
-    if (y_dtype == SESRQ_COLOUR_I8 && (!(scale > 0.f) || !std::isfinite(scale)))
-        return fail("%s: an int8 luma needs a positive, finite output scale", who);
-    if (y_dtype == SESRQ_COLOUR_I8 && (zero < -128 || zero > 127)) return fail("%s: zero %d outside the int8 range", who, zero);
-    if (y_dtype == SESRQ_COLOUR_F32 && (reinterpret_cast<uintptr_t>(y) & 3)) return fail("%s: an fp32 y is not 4-byte aligned", who);
     if (check_order(who, order)) return 1;
-    if (r != 2 && r != 4) return fail("%s: r = %d (2 or 4)", who, r);
-    if (N < 1 || H < 1 || W < 1) return fail("%s: empty frame (N = %d, H = %d, W = %d)", who, N, H, W);
-    const int tw = OUT_W / r, th = OUT_H / r;
-    const long long tx = ((long long)W + tw - 1) / tw, ty = ((long long)H + th - 1) / th, tiles = (long long)N * tx * ty;
-    if ((long long)r * H > 0x7fffffffLL || (long long)r * W > 0x7fffffffLL || tiles > 0x7fffffffLL)
-        return fail("%s: frame of %d x %d x %d at r = %d is too large", who, N, H, W, r);
 
-    ExportArgs a;
     a.y = y;
     a.img = img;
     a.out = out;
     a.H = H;
     a.W = W;
-    a.tiles_x = (int)tx;
-    a.tiles_y = (int)ty;
     a.bgr = order == SESRQ_COLOUR_ORDER_BGR;
     a.scale = scale;
     a.zero = zero;
-    const unsigned grid = (unsigned)tiles;
+    const unsigned grid = (unsigned)N * a.tiles_x * a.tiles_y;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int k;
 #define SESRQ_COLOUR_EXPORT(D, R, K)                                                   \
@@ -382,10 +358,7 @@ extern "C" int sesrq_colour_export(const void *y, int y_dtype, float scale, int 
     else SESRQ_COLOUR_EXPORT(SESRQ_COLOUR_F32, 4, K_F4)
     else return fail("%s: unreachable instantiation", who);
 #undef SESRQ_COLOUR_EXPORT
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("%s: kernel launch: %s", who, hipGetErrorString(e));
-    ++g_count.launches[k];
-    return 0;
+    return launched(who, g_count, k);
 }
 
 extern "C" int sesrq_colour_instance_count(void) { return g_count.count(); }

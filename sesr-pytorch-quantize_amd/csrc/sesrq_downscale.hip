@@ -293,10 +293,7 @@ extern "C" int sesrq_downscale_run(sesrq_downscale_ctx c, const uint8_t *img, in
     else SESRQ_DOWNSCALE_RUN(4, SESRQ_IMAGE_RGB, K_4R)
     else return fail("%s: unreachable instantiation", who);
 #undef SESRQ_DOWNSCALE_RUN
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("%s: kernel launch: %s", who, hipGetErrorString(e));
-    ++g_count.launches[k];
-    return 0;
+    return launched(who, g_count, k);
 }
 
 extern "C" int sesrq_downscale_instance_count(void) { return g_count.count(); }

@@ -333,10 +333,7 @@ extern "C" int sesrq_image_decode(sesrq_image_ctx c, const uint8_t *img, int for
     else SESRQ_IMAGE_DECODE(SESRQ_IMAGE_RGB, OUT_Q | OUT_F, K_RQF)
     else return fail("sesrq_image_decode: unreachable output set %d", out);
 #undef SESRQ_IMAGE_DECODE
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("sesrq_image_decode: kernel launch: %s", hipGetErrorString(e));
-    ++g_count.launches[k];
-    return 0;
+    return launched("sesrq_image_decode", g_count, k);
 }
 
 extern "C" int sesrq_image_export(const void *pred, int pred_dtype, float scale, int zero, int C, int order, uint8_t *out, int N, int H,
@@ -381,10 +378,7 @@ extern "C" int sesrq_image_export(const void *pred, int pred_dtype, float scale,
         if (C == 1) image_export<SESRQ_IMAGE_I8, 1><<<grid, THREADS, 0, st>>>(a);
         else image_export<SESRQ_IMAGE_I8, 3><<<grid, THREADS, 0, st>>>(a);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("sesrq_image_export: kernel launch: %s", hipGetErrorString(e));
-    ++g_count.launches[k];
-    return 0;
+    return launched("sesrq_image_export", g_count, k);
 }
 
 extern "C" int sesrq_image_instance_count(void) { return g_count.count(); }

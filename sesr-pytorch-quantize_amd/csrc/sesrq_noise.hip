@@ -298,10 +298,7 @@ extern "C" int sesrq_noise_unpack(sesrq_noise_ctx c, const void *raw, size_t row
         launch<PACK_RAW12>(outs, grid, st, a);
     else
         launch<PACK_U16>(outs, grid, st, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("%s: kernel launch: %s", who, hipGetErrorString(e));
-    ++g_count.launches[pack * 3 + outs - 1];
-    return 0;
+    return launched(who, g_count, pack * 3 + outs - 1);
 }
 
 extern "C" int sesrq_noise_deviates(float *z, int N, int H, int W, uint64_t seed, uint64_t frame0, void *stream) {
@@ -315,10 +312,7 @@ extern "C" int sesrq_noise_deviates(float *z, int N, int H, int W, uint64_t seed
     const long long want = (items + THREADS - 1) / THREADS;
     noise_deviates<<<(int)(want < Z_BLOCKS ? want : Z_BLOCKS), THREADS, 0, static_cast<hipStream_t>(stream)>>>(
         z, H, W, (size_t)items, (uint32_t)seed, (uint32_t)(seed >> 32), frame0);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("%s: kernel launch: %s", who, hipGetErrorString(e));
-    ++g_count.launches[K_DEVIATES];
-    return 0;
+    return launched(who, g_count, K_DEVIATES);
 }
 
 extern "C" int sesrq_noise_instance_count(void) { return g_count.count(); }

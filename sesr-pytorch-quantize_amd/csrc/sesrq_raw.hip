@@ -95,10 +95,7 @@ extern "C" int sesrq_raw_unpack(sesrq_raw_ctx c, const uint16_t *raw, int8_t *q0
         k = K_F;
         raw_unpack<OUT_F><<<grid, THREADS, 0, st>>>(a);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("sesrq_raw_unpack: kernel launch: %s", hipGetErrorString(e));
-    ++g_count.launches[k];
-    return 0;
+    return launched("sesrq_raw_unpack", g_count, k);
 }
 
 extern "C" int sesrq_raw_instance_count(void) { return g_count.count(); }

@@ -175,10 +175,7 @@ extern "C" int sesrq_sensor_unpack(sesrq_sensor_ctx c, const void *raw, size_t r
         family = F_U16_STEPS;
         launch<MAP_STEPS, PACK_U16>(outs, grid, st, a);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("sesrq_sensor_unpack: kernel launch: %s", hipGetErrorString(e));
-    ++g_count.launches[family * 3 + outs - 1];
-    return 0;
+    return launched("sesrq_sensor_unpack", g_count, family * 3 + outs - 1);
 }
 
 extern "C" int sesrq_sensor_instance_count(void) { return g_count.count(); }

@@ -1,7 +1,9 @@
 // Host scaffold of the side libraries (libsesrq_eval.so, libsesrq_raw.so, libsesrq_image.so): the error buffer, the launch counters
-// behind their exported instance lists, the input-domain check and host q0 quantiser, and a context that keeps one host table on a
-// device.  For the two Bayer unpack libraries (raw, sensor; their device body is sesrq_bayer_unpack.h) also the q0 table of a level
-// count, the shared argument checks of their unpack entries and a context's publish / destroy.
+// behind their exported instance lists and the end of an entry that launched one of them, the input-domain check and host q0
+// quantiser, and a context that keeps one host table on a device.  For the two Bayer unpack libraries (raw, sensor; their device
+// body is sesrq_bayer_unpack.h) also the q0 table of a level count, the shared argument checks of their unpack entries and a
+// context's publish / destroy; for the colour and the video export (their chroma upscale is sesrq_chroma_upscale.h) the check of
+// the luma arguments and the frame size.
 // Each library stays a library of its own; only this host code is shared.  Everything here has internal
 // linkage (static, or the anonymous namespace), so a library exports exactly what its own header declares.  No device code.
 #pragma once
@@ -94,6 +96,36 @@ struct DeviceTable {
     if (n > 0x7fffffffLL - round) return fail("%s: frame of %d x %d x %d is too large", who, N, H, W);
     *segs = (int)s;
     *items = (int)n;
+    return 0;
+}
+
+// What the colour and the video export refuse of the net's luma (y_dtype: LUMA_F32 or LUMA_I8 with its output domain), of r and
+// of the LR frame; then the tiles of out_w x out_h output pixels that cover the r H x r W frame, N frames of which must fit a grid.
+enum { LUMA_F32 = 0, LUMA_I8 = 1 };
+[[maybe_unused]] static int check_luma_export(const char *who, const void *y, int y_dtype, float scale, int zero, int r, int N, int H, int W,
+                                              int out_w, int out_h, int *tiles_x, int *tiles_y) {
+    if (!y) return fail("%s: y is NULL", who);
+    if (y_dtype != LUMA_F32 && y_dtype != LUMA_I8) return fail("%s: y_dtype %d (0 = fp32, 1 = int8)", who, y_dtype);
+    if (y_dtype == LUMA_I8 && (!(scale > 0.f) || !std::isfinite(scale)))
+        return fail("%s: an int8 luma needs a positive, finite output scale", who);
+    if (y_dtype == LUMA_I8 && (zero < -128 || zero > 127)) return fail("%s: zero %d outside the int8 range", who, zero);
+    if (y_dtype == LUMA_F32 && (reinterpret_cast<uintptr_t>(y) & 3)) return fail("%s: an fp32 y is not 4-byte aligned", who);
+    if (r != 2 && r != 4) return fail("%s: r = %d (2 or 4)", who, r);
+    if (N < 1 || H < 1 || W < 1) return fail("%s: empty frame (N = %d, H = %d, W = %d)", who, N, H, W);
+    const long long rW = (long long)r * W, rH = (long long)r * H, tx = (rW + out_w - 1) / out_w, ty = (rH + out_h - 1) / out_h;
+    if (rH > 0x7fffffffLL || rW > 0x7fffffffLL || (long long)N * tx * ty > 0x7fffffffLL)
+        return fail("%s: frame of %d x %d x %d at r = %d is too large", who, N, H, W, r);
+    *tiles_x = (int)tx;
+    *tiles_y = (int)ty;
+    return 0;
+}
+
+// The end of an entry that launched kernel k of its library's list: the launch's error, or one more launch counted.
+template <int N>
+[[maybe_unused]] static int launched(const char *who, Counters<N> &count, int k) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail("%s: kernel launch: %s", who, hipGetErrorString(e));
+    ++count.launches[k];
     return 0;
 }
 

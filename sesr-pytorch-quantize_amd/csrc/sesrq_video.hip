@@ -1,6 +1,9 @@
 // libsesrq_video.so: YUV 4:2:0 video frames (NV12 / I420) into and out of the luma super-resolution nets (include/sesrq_video.h, which
 // fixes the arithmetic).  A library of its own: it links nothing of libsesrq.so, libsesrq_image.so or libsesrq_colour.so and registers
-// nothing in their instance tables; the per-code table of the decode is the image library's (sesrq_image_decode.h), built once.
+// nothing in their instance tables; the per-code table of the decode is the image library's (sesrq_image_decode.h), built once, and
+// the weight table and the row padding of the export the colour library's too (sesrq_chroma_upscale.h); the
+// staging through pitch and step, the luma load and the two passes (twins of the colour export's: see that header), the luma and
+// chroma bytes and the NV12 / I420 stores are this file's.
 //
 // Decode: a stream over the Y plane, 1 B/px read through the surface's pitch; 1 B/px of q0 and 4 B/px of fp32 written.  A lane owns a
 // run of 16 pixels of one row and looks each byte up in the 256-code table, staged in LDS after the lane's first run was requested.
@@ -22,13 +25,18 @@
 #include "sesrq_video.h"
 #include "sesrq_side.h"
 #include "sesrq_image_decode.h"
+#include "sesrq_chroma_upscale.h"
 
 namespace sesrq_vidk {
 
 constexpr int OUT_W = SESRQ_VIDEO_TILE_OUT_W, OUT_H = SESRQ_VIDEO_TILE_OUT_H;        // a workgroup's output luma tile, at r = 2 and 4
 constexpr int CW = OUT_W / 2, CH = OUT_H / 2;               // ... and its output chroma tile, samples a plane
-constexpr int HALO = 2;
-constexpr int SEG = 16;                                     // output bytes per lane and run
+using sesrq_chroma::HALO;
+using sesrq_chroma::SEG;                                    // output bytes per lane and run
+using sesrq_chroma::first_tap;
+using sesrq_chroma::half_of;
+using sesrq_chroma::weight;
+using sesrq_chroma::weight_of;
 constexpr int CODES = SESRQ_VIDEO_CODES;
 constexpr int DEC_THREADS = 128;
 constexpr int BLOCKS_PER_CU = 16;                           // 128-thread blocks: a full CU (32 waves)
@@ -37,14 +45,6 @@ enum { OUT_Q = 1, OUT_F = 2 };
 using sesrq_imgdec::Tables;
 using sesrq_imgdec::RGB_WORDS;
 static_assert(CODES == sesrq_imgdec::CODES, "one table for both libraries");
-
-// The Keys a = -1/2 weights x 1024 of phase phi and the offset of tap 0 from j: sesrq_colour.h's table.
-__host__ __device__ constexpr int weight(int r, int phi, int k) {
-    constexpr int W4[4][4] = {{-45, 399, 745, -75}, {-7, 93, 987, -49}, {-49, 987, 93, -7}, {-75, 745, 399, -45}};
-    constexpr int W2[2][4] = {{-24, 232, 888, -72}, {-72, 888, 232, -24}};
-    return r == 4 ? W4[phi][k] : W2[phi][k];
-}
-__host__ __device__ constexpr int first_tap(int r, int phi) { return 2 * phi < r ? -2 : -1; }
 
 struct DecodeArgs {
     const uint8_t *y;
@@ -132,17 +132,6 @@ __global__ __launch_bounds__(DEC_THREADS) void video_decode(DecodeArgs a) {
 // step 2 of the header: u = trunc(fl32(clip(p, 0, 1) * 255)); a NaN gives 0
 __device__ inline unsigned to_byte(float p) { return (unsigned)__fmul_rn(fminf(fmaxf(p, 0.f), 1.f), 255.f); }
 
-// the weight of tap k of a lane's own phase
-template <int R>
-__device__ inline int weight_of(int phi, int k) {
-    int w = weight(R, 0, k);
-#pragma unroll
-    for (int q = 1; q < R; ++q) w = phi == q ? weight(R, q, k) : w;
-    return w;
-}
-
-__device__ inline int half_of(unsigned w, int hi) { return hi ? (int)w >> 16 : (int)(short)(w & 0xffffu); }
-
 // step 3's last line: the byte of an upscaled Q6 sample
 __device__ inline unsigned chroma_byte(int c) { return (unsigned)min(max((c + 32) >> 6, 0), 255); }
 
@@ -153,7 +142,7 @@ struct Shape {
     static constexpr int RUNS = OUT_W / SEG;                       // luma runs of a row: 8
     static constexpr int THREADS = RUNS * OUT_H;                   // a lane a luma run: 256
     static constexpr int CRUNS = 2 * CW * CH / SEG;                // chroma runs of a tile, both planes: 128
-    static constexpr int HWORDS = CW / 2 + 2;                      // words per row of the horizontal pass, padded
+    static constexpr int HWORDS = sesrq_chroma::hwords(CW);        // words per row of the horizontal pass
     static constexpr int STAGE = (2 * SW * SH + THREADS - 1) / THREADS;
     static constexpr int HPASS = (2 * SH * TW + THREADS - 1) / THREADS;
 };
@@ -296,7 +285,7 @@ __global__ __launch_bounds__(Shape<R>::THREADS, 8) void video_export(ExportArgs 
 
     // the vertical pass over four rows of the horizontal pass, four samples at a time
     const int li = crow / R, phi = crow % R;
-    const int r0 = li + HALO + (2 * phi < R ? -2 : -1);
+    const int r0 = li + HALO + first_tap(R, phi);
     int wy[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) wy[k] = weight_of<R>(phi, k);
@@ -349,6 +338,8 @@ struct sesrq_video_ctx_s {
     DeviceTable t;     // Tables
     InQuant q;
 };
+
+static_assert(SESRQ_VIDEO_F32 == LUMA_F32 && SESRQ_VIDEO_I8 == LUMA_I8, "check_luma_export's y_dtype");
 
 enum { K_DQ = 0, K_DF, K_DQF, K_Q2N, K_Q2I, K_Q4N, K_Q4I, K_F2N, K_F2I, K_F4N, K_F4I, K_COUNT };
 static const char *const kNames[K_COUNT] = {"video_decode<q0>",           "video_decode<x>",           "video_decode<q0,x>",
@@ -443,33 +434,21 @@ extern "C" int sesrq_video_decode(sesrq_video_ctx c, const sesrq_video_surface *
         k = K_DF;
         video_decode<OUT_F><<<grid, DEC_THREADS, 0, st>>>(a);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("%s: kernel launch: %s", who, hipGetErrorString(e));
-    ++g_count.launches[k];
-    return 0;
+    return launched(who, g_count, k);
 }
 
 extern "C" int sesrq_video_export(const void *y, int y_dtype, float scale, int zero, const sesrq_video_surface *lr, int r,
                                   const sesrq_video_surface *out, int N, int H, int W, void *stream) {
     g_err[0] = 0;
     const char *who = "sesrq_video_export";
-    if (!y) return fail("%s: y is NULL", who);
+    ExportArgs a;
+    if (check_luma_export(who, y, y_dtype, scale, zero, r, N, H, W, OUT_W, OUT_H, &a.tiles_x, &a.tiles_y)) return 1;
     if (!lr) return fail("%s: lr is NULL", who);
     if (!out) return fail("%s: out is NULL", who);
-    if (y_dtype != SESRQ_VIDEO_F32 && y_dtype != SESRQ_VIDEO_I8) return fail("%s: y_dtype %d (0 = fp32, 1 = int8)", who, y_dtype);
-    if (y_dtype == SESRQ_VIDEO_I8 && (!(scale > 0.f) || !std::isfinite(scale)))
-        return fail("%s: an int8 luma needs a positive, finite output scale", who);
-    if (y_dtype == SESRQ_VIDEO_I8 && (zero < -128 || zero > 127)) return fail("%s: zero %d outside the int8 range", who, zero);
-    if (y_dtype == SESRQ_VIDEO_F32 && (reinterpret_cast<uintptr_t>(y) & 3)) return fail("%s: an fp32 y is not 4-byte aligned", who);
     if (check_format(who, "lr", lr->format) || check_format(who, "out", out->format)) return 1;
-    if (r != 2 && r != 4) return fail("%s: r = %d (2 or 4)", who, r);
-    if (N < 1 || H < 1 || W < 1) return fail("%s: empty frame (N = %d, H = %d, W = %d)", who, N, H, W);
     if (!lr->c0 || (lr->format == SESRQ_VIDEO_I420 && !lr->c1)) return fail("%s: a chroma plane of lr is NULL", who);
     if (!out->y) return fail("%s: the Y plane of out is NULL", who);
     if (!out->c0 || (out->format == SESRQ_VIDEO_I420 && !out->c1)) return fail("%s: a chroma plane of out is NULL", who);
-    const long long tx = ((long long)r * W + OUT_W - 1) / OUT_W, ty = ((long long)r * H + OUT_H - 1) / OUT_H, tiles = (long long)N * tx * ty;
-    if ((long long)r * H > 0x7fffffffLL || (long long)r * W > 0x7fffffffLL || tiles > 0x7fffffffLL)
-        return fail("%s: frame of %d x %d x %d at r = %d is too large", who, N, H, W, r);
     const long long rW = (long long)r * W, rH = (long long)r * H;
     const long long lrow = chroma_row_bytes(lr->format, ((long long)W + 1) / 2), orow = chroma_row_bytes(out->format, rW / 2);
     if (lr->pitch_c < lrow) return fail("%s: pitch_c %lld of lr is below the row's %lld bytes", who, (long long)lr->pitch_c, lrow);
@@ -480,7 +459,6 @@ extern "C" int sesrq_video_export(const void *y, int y_dtype, float scale, int z
         return fail("%s: a frame stride of out (%lld, %lld) is below its plane's extent", who, (long long)out->frame_y,
                     (long long)out->frame_c);
 
-    ExportArgs a;
     a.y = y;
     const bool lnv = lr->format == SESRQ_VIDEO_NV12;
     a.cb = static_cast<const uint8_t *>(lr->c0);
@@ -497,11 +475,9 @@ extern "C" int sesrq_video_export(const void *y, int y_dtype, float scale, int z
     a.frame_c = out->frame_c;
     a.H = H;
     a.W = W;
-    a.tiles_x = (int)tx;
-    a.tiles_y = (int)ty;
     a.scale = scale;
     a.zero = zero;
-    const unsigned grid = (unsigned)tiles;
+    const unsigned grid = (unsigned)N * a.tiles_x * a.tiles_y;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int of = out->format;
     int k;
@@ -520,10 +496,7 @@ extern "C" int sesrq_video_export(const void *y, int y_dtype, float scale, int z
     else SESRQ_VIDEO_EXPORT(SESRQ_VIDEO_F32, 4, SESRQ_VIDEO_I420, K_F4I)
     else return fail("%s: unreachable instantiation", who);
 #undef SESRQ_VIDEO_EXPORT
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail("%s: kernel launch: %s", who, hipGetErrorString(e));
-    ++g_count.launches[k];
-    return 0;
+    return launched(who, g_count, k);
 }
 
 extern "C" int sesrq_video_instance_count(void) { return g_count.count(); }

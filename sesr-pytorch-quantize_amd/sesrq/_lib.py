@@ -1,5 +1,6 @@
 """ctypes binding of libsesrq.so (C ABI declared in include/sesrq.h), and the host plumbing every binding in the package shares:
-the loader (bind, Library), the stream entry of a launch, the host-array conversion and the input domain of the front ends.
+the loader (bind, Library), the stream entry of a launch, the host-array conversion, the input domain of the front ends and the
+luma arguments of the colour and the video export.
 
 The library is the product: if it is missing or a symbol cannot be resolved this module
 raises immediately -- there is no CPU or PyTorch fallback anywhere in the package.
@@ -239,6 +240,35 @@ def host_tensor(a):
     import numpy as np
     import torch
     return torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+
+
+FACTORS = (2, 4)                    # what the chroma upscale of the colour and the video export takes
+Y_F32, Y_I8 = 0, 1                  # SESRQ_COLOUR_F32 / _I8 = SESRQ_VIDEO_F32 / _I8: the luma dtype of both exports
+
+
+def chroma_factor(r, what: str) -> int:
+    """r of the `what` ("colour" / "video") export."""
+    if r not in FACTORS:
+        raise ValueError(f"scale factor {r!r}: the {what} export upscales chroma by 2 or 4")
+    return int(r)
+
+
+def luma_domain(y, shape, device, scale, zero, noun: str):
+    """(scale, zero) an export passes on with the net's luma `y`: a tensor of `shape` = (N, 1, r H, r W) on the device of the LR `noun`
+    ("image" / "surface"), fp32 -- (0.0, 0) -- or int8 with the net's output domain."""
+    import torch
+    if not isinstance(y, torch.Tensor) or tuple(y.shape) != tuple(shape):
+        raise ValueError(f"export: the luma is a (N, 1, r H, r W) = {tuple(shape)} tensor, got "
+                         f"{tuple(y.shape) if isinstance(y, torch.Tensor) else type(y).__name__}")
+    if y.device != device:
+        raise ValueError(f"export: the luma is on {y.device}, the {noun} on {device}")
+    if y.dtype == torch.float32:
+        return 0.0, 0
+    if y.dtype != torch.int8:
+        raise ValueError("export: the luma must be float32 or int8")
+    if scale is None or zero is None:
+        raise ValueError("export: an int8 luma needs the output domain: scale and zero")
+    return scale, zero
 
 
 def input_domain(engine_or_bundle, want_q: bool, who: str):

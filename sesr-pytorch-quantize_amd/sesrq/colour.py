@@ -16,13 +16,12 @@ import os
 import numpy as np
 
 from . import _lib
+from ._lib import FACTORS, Y_F32, Y_I8
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "lib", "libsesrq_colour.so"))
 
 ORDERS = {"rgb": 0, "bgr": 1}
-Y_F32, Y_I8 = 0, 1                  # SESRQ_COLOUR_F32 / SESRQ_COLOUR_I8
-FACTORS = (2, 4)
 TILE_W, TILE_H = 32, 8              # SESRQ_COLOUR_TILE_W / _H: the export's LR tile at r = 4 (twice that each way at r = 2)
 
 # every symbol include/sesrq_colour.h declares: name -> (restype, argtypes)
@@ -49,9 +48,7 @@ def _order(order) -> int:
 
 
 def _factor(r) -> int:
-    if r not in FACTORS:
-        raise ValueError(f"scale factor {r!r}: the colour export upscales chroma by 2 or 4")
-    return int(r)
+    return _lib.chroma_factor(r, "colour")
 
 
 def weights(r: int):
@@ -117,19 +114,7 @@ def export(y, img_u8, r: int, order: str = "rgb", scale=None, zero=None, out=Non
     img = _images(img_u8)
     dev = img.device
     N, H, W, _ = img.shape
-    if not isinstance(y, torch.Tensor) or tuple(y.shape) != (N, 1, r * H, r * W):
-        raise ValueError(f"export: the luma is a (N, 1, r H, r W) = {(N, 1, r * H, r * W)} tensor, got "
-                         f"{tuple(y.shape) if isinstance(y, torch.Tensor) else type(y).__name__}")
-    if y.device != dev:
-        raise ValueError(f"export: the luma is on {y.device}, the image on {dev}")
-    if y.dtype == torch.float32:
-        s, z = 0.0, 0
-    elif y.dtype == torch.int8:
-        if scale is None or zero is None:
-            raise ValueError("export: an int8 luma needs the output domain: scale and zero")
-        s, z = scale, zero
-    else:
-        raise ValueError("export: the luma must be float32 or int8")
+    s, z = _lib.luma_domain(y, (N, 1, r * H, r * W), dev, scale, zero, "image")
     shape = (N, r * H, r * W, 3)
     if out is not None:
         check_out(out, shape, dev)

@@ -19,6 +19,7 @@ import os
 import numpy as np
 
 from . import _lib
+from ._lib import FACTORS, Y_F32, Y_I8  # noqa: F401  (FACTORS: a public name of this module)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "lib", "libsesrq_video.so"))
@@ -26,8 +27,6 @@ LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "lib", "libsesrq_video.so"
 CODES = 256
 NV12, I420 = 0, 1                   # SESRQ_VIDEO_NV12 / SESRQ_VIDEO_I420
 FORMATS = {"nv12": NV12, "i420": I420}
-Y_F32, Y_I8 = 0, 1                  # SESRQ_VIDEO_F32 / SESRQ_VIDEO_I8
-FACTORS = (2, 4)
 TILE_OUT_W, TILE_OUT_H = 128, 32    # SESRQ_VIDEO_TILE_OUT_W / _H: the output-luma tile of an export workgroup
 
 
@@ -63,9 +62,7 @@ def _format(fmt) -> int:
 
 
 def _factor(r) -> int:
-    if r not in FACTORS:
-        raise ValueError(f"scale factor {r!r}: the video export upscales chroma by 2 or 4")
-    return int(r)
+    return _lib.chroma_factor(r, "video")
 
 
 def _size(H, W):
@@ -338,19 +335,7 @@ def export(y, lr: Surface, r: int, fmt=None, scale=None, zero=None, out=None, st
     lr = _on_device(lr, None, "export")
     dev = lr.device
     N, H, W = lr.N, lr.H, lr.W
-    if not isinstance(y, torch.Tensor) or tuple(y.shape) != (N, 1, r * H, r * W):
-        raise ValueError(f"export: the luma is a (N, 1, r H, r W) = {(N, 1, r * H, r * W)} tensor, got "
-                         f"{tuple(y.shape) if isinstance(y, torch.Tensor) else type(y).__name__}")
-    if y.device != dev:
-        raise ValueError(f"export: the luma is on {y.device}, the surface on {dev}")
-    if y.dtype == torch.float32:
-        s, z = 0.0, 0
-    elif y.dtype == torch.int8:
-        if scale is None or zero is None:
-            raise ValueError("export: an int8 luma needs the output domain: scale and zero")
-        s, z = scale, zero
-    else:
-        raise ValueError("export: the luma must be float32 or int8")
+    s, z = _lib.luma_domain(y, (N, 1, r * H, r * W), dev, scale, zero, "surface")
     f = _format(fmt) if fmt is not None else (out.fmt if isinstance(out, Surface) else lr.fmt)
     if out is not None:
         check_out(out, f, N, r * H, r * W, dev)
