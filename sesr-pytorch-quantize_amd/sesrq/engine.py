@@ -495,7 +495,7 @@ class Engine:
         b = self.bundle
         if b.in_channels != 1 or b.out_channels != 1:
             raise ValueError(f"forward_video: a video surface feeds a luma net (1 channel in, 1 out); this net takes {b.in_channels} "
-                             f"and gives {b.out_channels}")
+                             f"and gives {b.out_channels}: RGB nets take a surface through forward_video_rgb")
         r = video._factor(b.pixel_shuffle)
         if self.i8_in_scale != 0.0:
             raise ValueError("forward_video: this engine takes an upstream net's int8 output as input (upstream=...), not a surface")
@@ -516,6 +516,44 @@ class Engine:
             st = _lib.enter_stream(self.device, stream, luma, *s.planes()[1:], *out.planes())
             video.launch_export(luma, b.scale[b.L], b.zero[b.L], s, r, out, st)
         return (out, luma) if want_q else out
+
+    def forward_video_rgb(self, src, out=None, want_q: bool = False, stream=None, slot: int = 0):
+        """src: a sesrq.video.Surface of N YUV 4:2:0 frames (NV12 or I420) on self.device -> the super-resolved frames as a Surface of
+        r H x r W, r the net's PixelShuffle factor; with want_q also the net's prediction: (surface, prediction).
+
+        For RGB nets (3 channels in, 3 out: SESR-x2, MFLAG 6): one kernel (libsesrq_video_rgb.so, sesrq.video_rgb) upscales the
+        surface's chroma to 4:4:4, converts YCbCr to RGB bytes and decodes them into this net's kept q0 buffer -- forward_image on
+        the RGB image those bytes are, without that image; the same forward runs from int8, and one kernel exports the int8 output
+        to a 4:2:0 surface again (RGB bytes as image.export forms them, BT.601 luma, chroma averaged over 2 x 2 blocks).  An
+        anchor_add engine and a net narrower than 8 bits decode into the fp32 frame instead and export the fp32 output, exactly as
+        forward_image decides.  out: a Surface of the output size on this device to write into (its pixel format decides; without
+        it the output has src's).  All launches go to `stream` (default: current), ordered as forward() orders them; give concurrent
+        in-flight frames different slots."""
+        from . import video_rgb
+        b = self.bundle
+        if b.in_channels != 3 or b.out_channels != 3:
+            raise ValueError(f"forward_video_rgb: the RGB route feeds an RGB net (3 channels in, 3 out); this net takes {b.in_channels} "
+                             f"and gives {b.out_channels}: a luma net takes a surface through forward_video")
+        r = b.pixel_shuffle
+        if self.i8_in_scale != 0.0:
+            raise ValueError("forward_video_rgb: this engine takes an upstream net's int8 output as input (upstream=...), not a surface")
+        s = video_rgb._on_device(src, self.device, "forward_video_rgb")
+        N, H, W = s.N, s.H, s.W
+        if out is not None:
+            video_rgb.check_out(out, None, N, r * H, r * W, self.device, "forward_video_rgb")
+        # the buffer holds q0, or the fp32 frame an anchored forward adds back / a narrow net quantises itself
+        fp = self.anchor_add or self.quan_bits != 8
+
+        def decode(surf, buf, st):
+            video_rgb.launch_decode(self.device, b.scale[0], b.zero[0], self.exact_div, surf, None if fp else buf, buf if fp else None, st)
+        with torch.cuda.device(self.device):
+            q, f = self._run(s, _lib.F32 if fp else _lib.I8, not fp, fp, None, None, stream, slot, (N, 3, H, W), decode)
+            pred = f if fp else q
+            if out is None:
+                out = video_rgb.Surface.alloc(s.fmt, N, r * H, r * W, self.device)
+            st = _lib.enter_stream(self.device, stream, pred, *out.planes())
+            video_rgb.launch_export(pred, b.scale[b.L], b.zero[b.L], out, st)
+        return (out, pred) if want_q else out
 
     def submission(self, frames, outs_q, streams, outs_f=None, group: int = 1):
         """A prepared batch of independent forwards for sesrq_forward_many: frame k = frames[k] -> outs_q[k] (/ outs_f[k]; either may be None) on

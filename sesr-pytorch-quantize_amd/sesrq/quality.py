@@ -383,7 +383,8 @@ def evaluate_video(engine, lr_surfaces, hr_surfaces, mflag: int = 5):
     net only (MFLAG 5).  One synchronisation at the end; returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
     from . import video
     if mflag != 5:
-        raise ValueError(f"MFLAG {mflag}: video surfaces feed the luma net (MFLAG 5: SESR-x4, Y in, Y out)")
+        raise ValueError(f"MFLAG {mflag}: video surfaces feed the luma net (MFLAG 5: SESR-x4, Y in, Y out); MFLAG 6 is "
+                         "evaluate_video_rgb's")
     dev = engine.device
 
     def step(lr, hr, fp32):
@@ -391,6 +392,27 @@ def evaluate_video(engine, lr_surfaces, hr_surfaces, mflag: int = 5):
         _, g = video.decode(None, video.to_device(hr, dev), want_q=False, want_f=True)
         q, _ = engine.forward(q0, want_q=True, want_f=False)
         return q, g
+    return _evaluate(engine, mflag, zip(lr_surfaces, hr_surfaces), step)
+
+
+def evaluate_video_rgb(engine, lr_surfaces, hr_surfaces, mflag: int = 6):
+    """evaluate_image for YUV 4:2:0 video into the RGB net (sesrq.video_rgb): per LR Surface (a frame or a batch, host or device)
+    the surface is uploaded at 1.5 B/px, decoded on the device into the net's input and run forward (the fp32 frame and the anchored
+    fp32 output: the engine must have been created with anchor_add=True); the ground truth is the HR Surface decoded to fp32 RGB by
+    the same decode, and the output is scored as evaluate_image scores MFLAG 6.  One synchronisation at the end; returns a host
+    float64 array (frames, 3) of (mse, psnr, ssim)."""
+    from . import video_rgb
+    if mflag != 6:
+        raise ValueError(f"MFLAG {mflag}: the RGB video route feeds the RGB net (MFLAG 6: SESR-x2); MFLAG 5 is evaluate_video's")
+    if engine.bundle.in_channels != 3:
+        raise ValueError(f"MFLAG 6 takes an RGB net (3 channels in); this net takes {engine.bundle.in_channels}")
+    dev = engine.device
+
+    def step(lr, hr, fp32):
+        _, x = video_rgb.decode(None, video_rgb.to_device(lr, dev), want_q=False, want_f=True)
+        _, g = video_rgb.decode(None, video_rgb.to_device(hr, dev), want_q=False, want_f=True)
+        _, y = engine.forward(x, want_q=False, want_f=True)
+        return y, g
     return _evaluate(engine, mflag, zip(lr_surfaces, hr_surfaces), step)
 
 

@@ -304,7 +304,8 @@ def decode(engine_or_bundle, surface: Surface, want_q: bool = True, want_f: bool
         raise ValueError("decode: ask for q0, x or both")
     b, scale_in, zero_in, exact_div, dev = _lib.input_domain(engine_or_bundle, want_q, "decode")
     if b is not None and b.in_channels != 1:
-        raise ValueError(f"decode: a video surface feeds luma nets (1 channel in); this net takes {b.in_channels}")
+        raise ValueError(f"decode: a video surface feeds luma nets (1 channel in); this net takes {b.in_channels}: RGB nets decode a "
+                         "surface through sesrq.video_rgb")
     s = _on_device(surface, dev, "decode")
     dev = s.device
     with torch.cuda.device(dev):

@@ -13,6 +13,7 @@ test.py produced (an ``output_pt`` directory) or from a bundle/fixture file.
     python sim.py --mflag 5 --params ... --input LR.png --colour --save-png SR.png         # the x4 luma net's output in colour
     python sim.py --mflag 6 --params ... --hr HR.png --save-lr LR.png                      # the HR image alone: input and ground truth
     python sim.py --mflag 5 --params ... --yuv LR.yuv --size 960x540 --pix-fmt nv12 --save-yuv SR.yuv     # YUV 4:2:0 video in and out
+    python sim.py --mflag 6 --params ... --yuv LR.yuv --size 1920x1080 --pix-fmt nv12 --save-yuv SR.yuv   # ... of the RGB net (YCbCr <-> RGB)
     python sim.py --mflag 1 --ckpt nr_G.pth --calib output_pt --input a_132_128.raw --gt gt16.npy     # nr: scored on the Bayer mosaic
 """
 import argparse
@@ -287,17 +288,20 @@ YUV_BATCH = 8          # frames of a .yuv sequence that go through as one batch
 
 
 def add_video_flags(ap):
-    """--yuv / --size / --pix-fmt / --frames / --save-yuv / --out-pix-fmt / --gt-yuv: YUV 4:2:0 video through the luma net (sesrq.video)."""
-    ap.add_argument("--yuv", help="MFLAG 5, in place of --input: a raw .yuv file of unpadded 8-bit 4:2:0 frames (with --size and --pix-fmt); "
-                                  "the Y plane is the net's input, decoded on the device")
+    """--yuv / --size / --pix-fmt / --frames / --save-yuv / --out-pix-fmt / --gt-yuv: YUV 4:2:0 video through the luma net (sesrq.video)
+    or the RGB net (sesrq.video_rgb)."""
+    ap.add_argument("--yuv", help="MFLAG 5 / 6, in place of --input: a raw .yuv file of unpadded 8-bit 4:2:0 frames (with --size and "
+                                  "--pix-fmt), decoded on the device; MFLAG 5: the Y plane is the net's input, MFLAG 6: the frame "
+                                  "converted to RGB")
     ap.add_argument("--size", metavar="WxH", help="frame size of --yuv (luma; odd sizes are legal)")
     ap.add_argument("--pix-fmt", choices=("nv12", "i420"), default=None, help="pixel format of --yuv and --gt-yuv")
     ap.add_argument("--frames", metavar="A:B", help="with --yuv: run frames A .. B-1 of the file only (default: all)")
-    ap.add_argument("--save-yuv", help="with --yuv: write the super-resolved sequence here as a raw .yuv file -- the net's luma as bytes, "
-                                       "the input's chroma upscaled bicubically (sesrq.video.export)")
+    ap.add_argument("--save-yuv", help="with --yuv: write the super-resolved sequence here as a raw .yuv file -- MFLAG 5: the net's luma "
+                                       "as bytes, the input's chroma upscaled bicubically (sesrq.video.export); MFLAG 6: the anchored RGB "
+                                       "output converted to YCbCr 4:2:0 (sesrq.video_rgb.export)")
     ap.add_argument("--out-pix-fmt", choices=("nv12", "i420"), default=None, help="pixel format of --save-yuv (default: --pix-fmt)")
-    ap.add_argument("--gt-yuv", help="with --yuv: the HR sequence (same frames, r times the size, --pix-fmt); its Y plane is the ground "
-                                     "truth the output is scored against")
+    ap.add_argument("--gt-yuv", help="with --yuv: the HR sequence (same frames, r times the size, --pix-fmt); its Y plane (MFLAG 6: the frame "
+                                     "converted to RGB) is the ground truth the output is scored against")
 
 
 def video_args(args):
@@ -307,9 +311,9 @@ def video_args(args):
         if rest:
             raise SystemExit("sim.py: --size, --pix-fmt, --frames, --save-yuv, --out-pix-fmt and --gt-yuv belong to --yuv")
         return None
-    if args.mflag != 5 or args.input is not None or args.hr is not None or args.gt is not None or args.save_png or args.colour:
-        raise SystemExit("sim.py: --yuv feeds the luma net (--mflag 5) in place of --input / --hr; its ground truth is --gt-yuv, its "
-                         "output --save-yuv")
+    if args.mflag not in (5, 6) or args.input is not None or args.hr is not None or args.gt is not None or args.save_png or args.colour:
+        raise SystemExit("sim.py: --yuv feeds the luma net (--mflag 5) or the RGB net (--mflag 6) in place of --input / --hr; its ground "
+                         "truth is --gt-yuv, its output --save-yuv")
     if args.size is None or args.pix_fmt is None:
         raise SystemExit("sim.py: --yuv needs --size WxH and --pix-fmt")
     try:
@@ -326,9 +330,15 @@ def video_args(args):
 def run_yuv(args, yuv, model, keep=False):
     """The --yuv run: the sequence goes through in batches of YUV_BATCH frames -- Y plane decoded on the device -> model(inps) ->
     scored against --gt-yuv's Y plane, exported with the input's chroma to --save-yuv.  Prints what the image path prints.
+    MFLAG 6 goes through sesrq.video_rgb instead: the frames decoded to RGB -> model(inps) -> the anchored output scored against
+    --gt-yuv decoded to RGB and exported to --save-yuv as YCbCr 4:2:0.
     A batch's fp32 output (33 MB a 4K frame) is dropped once it is scored and saved, so device memory does not grow with the
     sequence: only a caller from Python (keep: main(argv) returns the whole output, on the device) and --save (host copies) hold it."""
     from sesrq import quality, video
+    rgb = args.mflag == 6
+    if rgb:
+        from sesrq import video_rgb
+    route = video_rgb if rgb else video
     W, H, span = yuv
     dev = torch.device("cuda", torch.cuda.current_device())
     try:
@@ -340,18 +350,21 @@ def run_yuv(args, yuv, model, keep=False):
         outs, rows, shape = [], [], None
         for a in range(0, lr.N, YUV_BATCH):
             part = video.to_device(lr[a:a + YUV_BATCH], dev)
-            _, inps = video.decode(None, part, want_q=False, want_f=True)
+            _, inps = route.decode(None, part, want_q=False, want_f=True)
             gfake = model(inps)
+            pred = anchored(gfake, inps, args.mflag)        # test.py:149-155: MFLAG 6 + the nearest-upsampled input
             shape = (a + gfake.shape[0],) + tuple(gfake.shape[1:])
             if keep:
                 outs.append(gfake)
             elif args.save:
                 outs.append(gfake.cpu())
             if gt is not None:
-                _, g = video.decode(None, video.to_device(gt[a:a + YUV_BATCH], dev), want_q=False, want_f=True)
-                rows.append(quality.score(gfake, g, args.mflag))
+                _, g = route.decode(None, video.to_device(gt[a:a + YUV_BATCH], dev), want_q=False, want_f=True)
+                rows.append(quality.score(pred, g, args.mflag))
             if args.save_yuv:
-                video.save_yuv(args.save_yuv, video.export(gfake, part, r, fmt=args.out_pix_fmt or args.pix_fmt), append=a > 0)
+                fmt = args.out_pix_fmt or args.pix_fmt
+                sr = video_rgb.export(pred, fmt=fmt) if rgb else video.export(gfake, part, r, fmt=fmt)
+                video.save_yuv(args.save_yuv, sr, append=a > 0)
     except ValueError as e:
         raise SystemExit(f"sim.py: {e}") from None
     gfake = torch.cat(outs) if outs else None
