@@ -380,6 +380,39 @@ class Engine:
         return self._run(raw, _lib.F32 if narrow else _lib.I8, want_q, want_f, out_q if want_q else None, out_f if want_f else None,
                          stream, slot, (N, 3, H, W), unpack)
 
+    def forward_develop(self, raw: torch.Tensor, profile, order: str = "rgb", out=None, stream=None, slot: int = 0, fmt=None, stride=None,
+                        width=None, noise=None):
+        """raw: sensor frames as forward_raw takes them (with its fmt, stride, width and noise) -> the developed display images
+        (N, H, W, 3) torch.uint8 in `order`.
+
+        For the raw nets whose output is a linear camera-RGB image (3 channels out, no PixelShuffle: dm, nrdm_3, nrdm_6): forward_raw
+        with the int8 output only, followed by the fused develop export (libsesrq_develop.so, sesrq.develop) from that int8 output with
+        the net's output domain -- white-balance gains, colour-correction matrix and tone curve of `profile` (a
+        sesrq.develop.Profile), bytes out.  out: a contiguous uint8 tensor of the output shape to write into.  All launches go to
+        `stream` (default: current), ordered as forward() orders them; give concurrent in-flight frames different slots.  Everything
+        forward_raw refuses is refused by forward_raw.  An nr net (MFLAG 1) has the shape of a dm net but returns a mosaic; a bundle
+        does not record its task, so that misuse is the caller's to avoid (sim.py --develop refuses MFLAG 1)."""
+        from . import develop, sensor
+        b = self.bundle
+        if b.out_channels != 3 or b.pixel_shuffle != 1:
+            raise ValueError(f"forward_develop: a developed image comes from a net that returns the 3 planes R, G, B at the frame's size; "
+                             f"this net gives {b.out_channels} channel(s) at PixelShuffle factor {b.pixel_shuffle} (the SR nets export "
+                             "through image.export, forward_colour and forward_video)")
+        develop._order(order)
+        profile = develop._profile(profile)
+        if out is not None:                  # the frame size as forward_raw will read it (what it refuses of `raw`, it refuses here too)
+            frames, W, _ = sensor.frames(raw, fmt, self.device, stride, width, "forward_raw: ")
+            develop.check_out(out, (frames.shape[0], frames.shape[1], W, 3), self.device, "forward_develop")
+        with torch.cuda.device(self.device):
+            q, _ = self.forward_raw(raw, want_q=True, want_f=False, stream=stream, slot=slot, fmt=fmt, stride=stride, width=width,
+                                    noise=noise)
+            N, _, H, W = q.shape
+            if out is None:
+                out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=self.device)
+            st = _lib.enter_stream(self.device, stream, q, out)
+            develop.launch(profile, q, b.scale[b.L], b.zero[b.L], order, out, st)
+        return out
+
     def forward_image(self, img_u8: torch.Tensor, form=None, order: str = "rgb", want_q: bool = True, want_f: bool = True, out_q=None,
                       out_f=None, stream=None, slot: int = 0):
         """img_u8: (N, H, W, 3) or (H, W, 3) torch.uint8 images on self.device, interleaved in `order` ("rgb" or "bgr") ->

@@ -15,6 +15,7 @@ test.py produced (an ``output_pt`` directory) or from a bundle/fixture file.
     python sim.py --mflag 5 --params ... --yuv LR.yuv --size 960x540 --pix-fmt nv12 --save-yuv SR.yuv     # YUV 4:2:0 video in and out
     python sim.py --mflag 6 --params ... --yuv LR.yuv --size 1920x1080 --pix-fmt nv12 --save-yuv SR.yuv   # ... of the RGB net (YCbCr <-> RGB)
     python sim.py --mflag 1 --ckpt nr_G.pth --calib output_pt --input a_132_128.raw --gt gt16.npy     # nr: scored on the Bayer mosaic
+    python sim.py --mflag 3 --params ... --input a_132_128.raw --develop --colormatrix ... --red-gain 2.1 --blue-gain 1.6 --save-png OUT.png
 """
 import argparse
 import json
@@ -173,7 +174,9 @@ def main(argv=None):
     add_sensor_flags(ap)
     add_noise_flags(ap)
     add_video_flags(ap)
+    add_develop_flags(ap)
     args = ap.parse_args(argv)
+    profile = develop_profile(ap, args)
     yuv = video_args(args)
     if yuv is not None:                     # --yuv stands in place of --input / --hr (video_args has refused them beside it)
         if args.save_lr:
@@ -268,6 +271,8 @@ def main(argv=None):
         score_against(args.gt, gfake, inps, args.mflag, gts=gts, fmt=fmt)
     if args.save_png and args.colour:
         save_colour_png(args.save_png, gfake, lr_u8, args.order)
+    elif args.save_png and profile is not None:
+        save_develop_png(args.save_png, gfake, profile, args.order)
     elif args.save_png:
         save_png(args.save_png, gfake, inps, args.mflag)
     return gfake
@@ -282,6 +287,72 @@ def add_sensor_flags(ap):
     ap.add_argument("--packing", choices=("u16", "raw10", "raw12"), default=None,
                     help="how *.raw inputs hold their pixels: uint16 containers (default), MIPI RAW10 (4 px in 5 bytes) or RAW12 "
                          "(2 px in 3 bytes); a file is <rows> x the unpadded row bytes")
+
+
+def add_develop_flags(ap):
+    """--develop / --wb / --ccm / --colormatrix / --red-gain / --blue-gain / --rgb-gain / --curve: the display image of a raw net's
+    linear camera-RGB output (sesrq.develop)."""
+    nine = lambda s: [float(v) for v in s.replace(",", " ").split()]
+    ap.add_argument("--develop", action="store_true", help="MFLAG 2 / 3 / 4 with a *.raw input and --save-png: write the DEVELOPED image -- "
+                                                           "white-balance gains, colour-correction matrix, tone curve (sesrq.develop); "
+                                                           "without the flag the PNG is the linear camera RGB, as the reference's")
+    ap.add_argument("--wb", metavar="R,G,B", type=nine, default=None, help="with --develop: the three gains (default 1,1,1)")
+    ap.add_argument("--ccm", metavar="M", type=float, nargs=9, default=None,
+                    help="with --develop: the colour-correction matrix (camera RGB -> display RGB), nine numbers row by row (default: "
+                         "the identity)")
+    ap.add_argument("--colormatrix", metavar="M", type=float, nargs=9, default=None,
+                    help="with --develop, in place of --ccm and --wb: the camera's xyz2cam matrix, nine numbers row by row, turned into "
+                         "cam2rgb as the reference's metadata2tensor does; gains from --red-gain, --blue-gain and --rgb-gain")
+    ap.add_argument("--red-gain", type=float, default=None, help="with --colormatrix: the red white-balance gain (default 1)")
+    ap.add_argument("--blue-gain", type=float, default=None, help="with --colormatrix: the blue white-balance gain (default 1)")
+    ap.add_argument("--rgb-gain", type=float, default=None, help="with --colormatrix: the exposure gain on all three channels (default 1)")
+    ap.add_argument("--curve", choices=("gamma", "srgb", "trunc255"), default=None,
+                    help="with --develop: the tone curve -- gamma (o^(1/2.2), the default), srgb, or trunc255 (no curve: * 255, truncated)")
+
+
+def develop_profile(ap, args):
+    """The sesrq.develop.Profile the develop flags describe, or None without --develop; a flag error is an argparse error."""
+    rest = [k for k in ("wb", "ccm", "colormatrix", "red_gain", "blue_gain", "rgb_gain", "curve") if getattr(args, k) is not None]
+    if not args.develop:
+        if rest:
+            ap.error("--wb, --ccm, --colormatrix, --red-gain, --blue-gain, --rgb-gain and --curve belong to --develop")
+        return None
+    if args.mflag not in (2, 3, 4):
+        ap.error(f"--develop: MFLAG {args.mflag} does not return a linear camera-RGB image (2: dm, 3: nrdm_3 and 4: nrdm_6 do; the "
+                 "output of 1, nr, is a mosaic; 5 and 6 are developed images already)")
+    if args.input is None or not args.input.endswith(".raw"):
+        ap.error("--develop: the developed image comes from a raw frame: it needs a *.raw file as --input")
+    if not args.save_png:
+        ap.error("--develop: the developed image is written as a PNG: it needs --save-png")
+    if args.colour:
+        ap.error("--develop: --colour rebuilds colour around the luma net (--mflag 5)")
+    gains = [k for k in ("red_gain", "blue_gain", "rgb_gain") if getattr(args, k) is not None]
+    if args.colormatrix is not None and (args.ccm is not None or args.wb is not None):
+        ap.error("--develop: either --ccm (with --wb), or --colormatrix (with --red-gain, --blue-gain, --rgb-gain)")
+    if args.colormatrix is None and gains:
+        ap.error("--develop: --red-gain, --blue-gain and --rgb-gain belong to --colormatrix; with --ccm the gains are --wb R,G,B")
+    if args.wb is not None and len(args.wb) != 3:
+        ap.error("--develop: --wb takes three gains R,G,B")
+    from sesrq import develop
+    try:
+        if args.colormatrix is not None:
+            one = lambda v: 1.0 if v is None else v
+            return develop.from_colormatrix(args.colormatrix, one(args.red_gain), one(args.blue_gain), one(args.rgb_gain),
+                                            curve=args.curve or "gamma")
+        return develop.Profile(args.wb or (1.0, 1.0, 1.0), args.ccm or (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), args.curve or "gamma")
+    except ValueError as e:
+        ap.error(f"--develop: {e}")
+
+
+def save_develop_png(path, gfake, profile, order):
+    """--develop: the raw net's linear camera RGB with gains, colour matrix and tone curve applied, as an RGB PNG (sesrq.develop.export;
+    the fp32 output is the dequantised int8 output, so the bytes are Engine.forward_develop's)."""
+    from sesrq import develop, image
+    u8 = develop.export(gfake, profile, order="rgb").cpu().numpy()          # PIL takes RGB bytes
+    stem, ext = os.path.splitext(path)
+    for k in range(u8.shape[0]):
+        image.save_png(path if u8.shape[0] == 1 else f"{stem}_{k}{ext or '.png'}", u8[k])
+    print("png:", path, tuple(u8.shape))
 
 
 YUV_BATCH = 8          # frames of a .yuv sequence that go through as one batch
