@@ -26,6 +26,7 @@
 #include "sesrq_colour.h"
 #include "sesrq_side.h"
 #include "sesrq_chroma_upscale.h"
+#include "sesrq_pred_byte.h"
 
 namespace sesrq_colk {
 
@@ -185,7 +186,7 @@ __global__ __launch_bounds__(Shape<R>::THREADS, 8) void colour_export(ExportArgs
     stage_codes<THREADS>(s_d);
     if (YD == SESRQ_COLOUR_I8) {                                     // an int8 luma has 256 codes: a(q) of steps 3 and 4, one code a lane
         static_assert(THREADS == CODES, "one int8 code a lane");
-        s_a[tid] = luma_term(__fmul_rn((float)(tid - 128 - a.zero), a.scale));
+        s_a[tid] = luma_term(sesrq_pred::dequant(tid - 128, a.zero, a.scale));
     }
     __syncthreads();
 #pragma unroll
@@ -283,7 +284,7 @@ __global__ __launch_bounds__(Shape<R>::THREADS, 8) void colour_export(ExportArgs
 
 using namespace sesrq_colk;
 
-static_assert(SESRQ_COLOUR_F32 == LUMA_F32 && SESRQ_COLOUR_I8 == LUMA_I8, "check_luma_export's y_dtype");
+static_assert(SESRQ_COLOUR_F32 == PRED_F32 && SESRQ_COLOUR_I8 == PRED_I8, "check_pred's dtype");
 
 enum { K_Q2 = 0, K_Q4, K_F2, K_F4, K_CHROMA, K_COUNT };
 static const char *const kNames[K_COUNT] = {"colour_export<i8,r2>", "colour_export<i8,r4>", "colour_export<f32,r2>",

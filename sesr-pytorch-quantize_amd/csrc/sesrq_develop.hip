@@ -25,6 +25,7 @@
 
 #include "sesrq_develop.h"
 #include "sesrq_side.h"
+#include "sesrq_pred_byte.h"
 
 namespace sesrq_devk {
 
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(THREADS) void develop_export(Args a) {
     const size_t HW = (size_t)a.HW;
     const float *pf = static_cast<const float *>(a.pred);
     const int8_t *pq = static_cast<const int8_t *>(a.pred);
-    auto val = [&](int8_t q) { return __fmul_rn((float)((int)q - a.zero), a.scale); };
+    auto val = [&](int8_t q) { return sesrq_pred::dequant(q, a.zero, a.scale); };
     const int ir = a.bgr ? 2 : 0;                         // byte position of R in a pixel (B sits at 2 - ir)
 
     for (int i = blockIdx.x * THREADS + threadIdx.x; i < a.items; i += gridDim.x * THREADS) {
@@ -156,6 +157,8 @@ struct sesrq_develop_ctx_s {
     float g[3], m[9];
     int depth;
 };
+
+static_assert(SESRQ_DEVELOP_F32 == PRED_F32 && SESRQ_DEVELOP_I8 == PRED_I8, "check_pred's dtype");
 
 enum { K_F32 = 0, K_I8, K_COUNT };
 static const char *const kNames[K_COUNT] = {"develop_export<f32>", "develop_export<i8>"};
@@ -256,29 +259,24 @@ extern "C" int sesrq_develop_export(sesrq_develop_ctx c, const void *pred, int p
     if (!c) return fail("%s: ctx is NULL", who);
     if (!pred) return fail("%s: pred is NULL", who);
     if (!out) return fail("%s: out is NULL", who);
-    if (pred_dtype != SESRQ_DEVELOP_F32 && pred_dtype != SESRQ_DEVELOP_I8) return fail("%s: pred_dtype %d (0 = fp32, 1 = int8)", who, pred_dtype);
-    if (pred_dtype == SESRQ_DEVELOP_I8 && (!(scale > 0.f) || !std::isfinite(scale)))
-        return fail("%s: an int8 prediction needs a positive, finite output scale", who);
-    if (pred_dtype == SESRQ_DEVELOP_I8 && (zero < -128 || zero > 127)) return fail("%s: zero %d outside the int8 range", who, zero);
-    if (pred_dtype == SESRQ_DEVELOP_F32 && (reinterpret_cast<uintptr_t>(pred) & 3)) return fail("%s: an fp32 pred is not 4-byte aligned", who);
+    if (check_pred(who, "pred", pred, pred_dtype, scale, zero, true)) return 1;
     if (order != SESRQ_DEVELOP_ORDER_RGB && order != SESRQ_DEVELOP_ORDER_BGR) return fail("%s: order %d (0 = RGB, 1 = BGR)", who, order);
     if (N < 1 || H < 1 || W < 1) return fail("%s: empty frame (N = %d, H = %d, W = %d)", who, N, H, W);
     // the 16-pixel runs must fit an int together with one round of the grid; a generous bound on the grid (1024 CUs) keeps the check
     // independent of the device
-    const long long HW = (long long)H * W, segs = (HW + SEG - 1) / SEG, items = (long long)N * segs;
-    if (HW > 0x7fffffffLL || items > 0x7fffffffLL - (long long)THREADS * 1024 * BLOCKS_PER_CU)
-        return fail("%s: frame of %d x %d x %d is too large", who, N, H, W);
+    int segs, items;
+    if (pixel_runs(who, N, H, W, SEG, (long long)THREADS * 1024 * BLOCKS_PER_CU, &segs, &items)) return 1;
     if (table_on_current(who, c->t)) return 1;
 
     Args a;
     a.pred = pred;
     a.out = out;
     a.tab = static_cast<const Table *>(c->t.ptr);
-    a.HW = (int)HW;
-    a.segs = (int)segs;
-    a.items = (int)items;
+    a.HW = H * W;
+    a.segs = segs;
+    a.items = items;
     a.bgr = order == SESRQ_DEVELOP_ORDER_BGR;
-    a.planes16 = HW % SEG == 0;
+    a.planes16 = a.HW % SEG == 0;
     a.depth = c->depth;
     a.scale = scale;
     a.zero = zero;

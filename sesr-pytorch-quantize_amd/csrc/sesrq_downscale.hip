@@ -210,10 +210,7 @@ __global__ __launch_bounds__(THREADS) void downscale(Args a) {
 
 using namespace sesrq_dsk;
 
-struct sesrq_downscale_ctx_s {
-    DeviceTable t;     // Tables
-    InQuant q;
-};
+struct sesrq_downscale_ctx_s : sesrq_imgdec::CodeCtx {};
 
 enum { K_2L = 0, K_2Y, K_2R, K_4L, K_4Y, K_4R, K_COUNT };
 static const char *const kNames[K_COUNT] = {"downscale<r2,lr>", "downscale<r2,Y>", "downscale<r2,RGB>",
@@ -230,17 +227,7 @@ extern "C" int sesrq_downscale_weights(int r, int16_t *w, int *D) {
 }
 
 extern "C" int sesrq_downscale_create(float scale_in, int zero_in, int exact_div, sesrq_downscale_ctx *out) {
-    g_err[0] = 0;
-    if (!out) return fail("sesrq_downscale_create: ctx is NULL");
-    *out = nullptr;
-    if (check_domain("sesrq_downscale_create", scale_in, zero_in, exact_div)) return 1;
-    auto *c = new sesrq_downscale_ctx_s();
-    c->q = in_quant(scale_in, zero_in, exact_div);
-    Tables *host = new Tables();
-    sesrq_imgdec::build(c->q, *host);
-    const int rc = ctx_publish("sesrq_downscale_create", c, host, sizeof(Tables), out);
-    delete host;
-    return rc;
+    return sesrq_imgdec::code_create("sesrq_downscale_create", scale_in, zero_in, exact_div, out);
 }
 
 extern "C" void sesrq_downscale_destroy(sesrq_downscale_ctx c) { ctx_destroy(c); }

@@ -24,6 +24,7 @@
 #include "sesrq_image.h"
 #include "sesrq_side.h"
 #include "sesrq_image_decode.h"
+#include "sesrq_pred_byte.h"
 
 namespace sesrq_imgk {
 
@@ -39,6 +40,8 @@ using sesrq_imgdec::RGB_WORDS;
 using sesrq_imgdec::Quant;
 using sesrq_imgdec::quant;
 using sesrq_imgdec::luma;
+using sesrq_pred::dequant;
+using sesrq_pred::to_byte;
 static_assert(Y_WORDS % THREADS == 0 && RGB_WORDS <= THREADS, "staging: whole words per thread");
 
 struct DecodeArgs {
@@ -169,9 +172,6 @@ __global__ __launch_bounds__(THREADS) void image_decode(DecodeArgs a) {
     }
 }
 
-// u = trunc(fl32(clip(p, 0, 1) * 255)); an int8 prediction is first dequantised as sesrq_forward forms out_f
-__device__ inline unsigned to_byte(float p) { return (unsigned)__fmul_rn(fminf(fmaxf(p, 0.f), 1.f), 255.f); }
-
 template <int PRED, int C>
 __global__ __launch_bounds__(THREADS) void image_export(ExportArgs a) {
     const size_t HW = (size_t)a.HW;
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(THREADS) void image_export(ExportArgs a) {
         for (int c = 0; c < C; ++c) pl[c] = in0 + (size_t)(C == 3 && a.bgr ? 2 - c : c) * HW;
         const float *pf = static_cast<const float *>(a.pred);
         const int8_t *pq = static_cast<const int8_t *>(a.pred);
-        auto val = [&](int8_t q) { return __fmul_rn((float)((int)q - a.zero), a.scale); };
+        auto val = [&](int8_t q) { return dequant(q, a.zero, a.scale); };
         const bool vec = npx == SEG && (reinterpret_cast<uintptr_t>(dst) & 15) == 0 && (C == 1 || a.planes16) &&
                          (reinterpret_cast<uintptr_t>(PRED == SESRQ_IMAGE_F32 ? (const void *)(pf + in0) : (const void *)(pq + in0)) & 15) == 0;
         if (vec) {
@@ -230,10 +230,8 @@ __global__ __launch_bounds__(THREADS) void image_export(ExportArgs a) {
 
 using namespace sesrq_imgk;
 
-struct sesrq_image_ctx_s {
-    DeviceTable t;     // Tables
-    InQuant q;
-};
+struct sesrq_image_ctx_s : sesrq_imgdec::CodeCtx {};
+static_assert(SESRQ_IMAGE_F32 == PRED_F32 && SESRQ_IMAGE_I8 == PRED_I8, "check_pred's dtype");
 
 enum { K_YQ = 0, K_YF, K_YQF, K_RQ, K_RF, K_RQF, K_EF1, K_EF3, K_EQ1, K_EQ3, K_COUNT };
 static const char *const kNames[K_COUNT] = {
@@ -241,56 +239,20 @@ static const char *const kNames[K_COUNT] = {
     "image_decode<RGB,q0,x>", "image_export<f32,C1>", "image_export<f32,C3>", "image_export<i8,C1>", "image_export<i8,C3>"};
 static Counters<K_COUNT> g_count{kNames};
 
-using sesrq_imgdec::build;
-
 extern "C" int sesrq_image_table(float scale_in, int zero_in, int exact_div, int8_t q[SESRQ_IMAGE_CODES], float x[SESRQ_IMAGE_CODES]) {
-    g_err[0] = 0;
-    if (!q || !x) return fail("sesrq_image_table: q or x is NULL");
-    if (check_domain("sesrq_image_table", scale_in, zero_in, exact_div)) return 1;
-    static thread_local Tables t;
-    build(in_quant(scale_in, zero_in, exact_div), t);
-    for (int v = 0; v < CODES; ++v) {
-        q[v] = t.q[v];
-        x[v] = t.x[v];
-    }
-    return 0;
+    return sesrq_imgdec::code_table("sesrq_image_table", scale_in, zero_in, exact_div, q, x);
 }
 
 extern "C" int sesrq_image_create(float scale_in, int zero_in, int exact_div, sesrq_image_ctx *out) {
-    g_err[0] = 0;
-    if (!out) return fail("sesrq_image_create: ctx is NULL");
-    *out = nullptr;
-    if (check_domain("sesrq_image_create", scale_in, zero_in, exact_div)) return 1;
-    auto *c = new sesrq_image_ctx_s();
-    c->q = in_quant(scale_in, zero_in, exact_div);
-    Tables *host = new Tables();
-    build(c->q, *host);
-    const hipError_t e = table_create(c->t, host, sizeof(Tables));
-    delete host;
-    if (e != hipSuccess) {
-        delete c;
-        return fail("sesrq_image_create: %s", hipGetErrorString(e));
-    }
-    *out = c;
-    return 0;
+    return sesrq_imgdec::code_create("sesrq_image_create", scale_in, zero_in, exact_div, out);
 }
 
-extern "C" void sesrq_image_destroy(sesrq_image_ctx c) {
-    if (!c) return;
-    table_destroy(c->t);
-    delete c;
-}
+extern "C" void sesrq_image_destroy(sesrq_image_ctx c) { ctx_destroy(c); }
 
 // items of 16-pixel runs, checked to fit an int together with the grid stride
 static int runs(const char *who, int N, int H, int W, int num_cu, int &segs, int &items) {
     if (N < 1 || H < 1 || W < 1) return fail("%s: empty frame (N = %d, H = %d, W = %d)", who, N, H, W);
-    const long long HW = (long long)H * W;
-    const long long sg = (HW + SEG - 1) / SEG, it = (long long)N * sg;
-    if (HW > 0x7fffffffLL || it > 0x7fffffffLL - (long long)THREADS * num_cu * BLOCKS_PER_CU)
-        return fail("%s: frame of %d x %d x %d is too large", who, N, H, W);
-    segs = (int)sg;
-    items = (int)it;
-    return 0;
+    return pixel_runs(who, N, H, W, SEG, (long long)THREADS * num_cu * BLOCKS_PER_CU, &segs, &items);
 }
 
 extern "C" int sesrq_image_decode(sesrq_image_ctx c, const uint8_t *img, int form, int order, int8_t *q0, float *x, int N, int H, int W,
@@ -341,11 +303,7 @@ extern "C" int sesrq_image_export(const void *pred, int pred_dtype, float scale,
     g_err[0] = 0;
     if (!pred) return fail("sesrq_image_export: pred is NULL");
     if (!out) return fail("sesrq_image_export: out is NULL");
-    if (pred_dtype != SESRQ_IMAGE_F32 && pred_dtype != SESRQ_IMAGE_I8)
-        return fail("sesrq_image_export: pred_dtype %d (0 = fp32, 1 = int8)", pred_dtype);
-    if (pred_dtype == SESRQ_IMAGE_I8 && (!(scale > 0.f) || !std::isfinite(scale)))
-        return fail("sesrq_image_export: an int8 prediction needs a positive, finite output scale");
-    if (pred_dtype == SESRQ_IMAGE_I8 && (zero < -128 || zero > 127)) return fail("sesrq_image_export: zero %d outside the int8 range", zero);
+    if (check_pred("sesrq_image_export", "pred", pred, pred_dtype, scale, zero, false)) return 1;
     if (C != 1 && C != 3) return fail("sesrq_image_export: %d channels (1 or 3)", C);
     if (order != SESRQ_IMAGE_ORDER_RGB && order != SESRQ_IMAGE_ORDER_BGR) return fail("sesrq_image_export: order %d (0 = RGB, 1 = BGR)", order);
     int dev = -1, num_cu = 0;

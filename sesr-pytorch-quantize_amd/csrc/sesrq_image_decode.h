@@ -1,8 +1,10 @@
 // The decode of 8-bit image bytes into the super-resolution nets' input (include/sesrq_image.h, which fixes the arithmetic): the tables
 // of a context, how the host builds them, and the per-pixel device body -- the float64 luma of the Y form, the table lookup of the RGB
 // form, the input quantiser.  libsesrq_image.so (image_decode: bytes from memory) and libsesrq_downscale.so (bytes from its own bicubic
-// pass) both instantiate it, so the arithmetic stands once.  Each library stays a library of its own; everything here has internal
-// linkage.  Include after sesrq_side.h (InQuant, host_quant).
+// pass) both instantiate it, so the arithmetic stands once; the two video libraries look their bytes up in the same tables.  Also the
+// host code around the tables that these four libraries share: the context that holds them and the bodies of their <library>_table
+// and <library>_create entries.  Each library stays a library of its own; everything here has internal linkage.  Include after
+// sesrq_side.h (InQuant, host_quant, ctx_publish).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -74,6 +76,42 @@ static inline void build(const InQuant &q, Tables &t) {
         t.x[v] = x;
         t.q[v] = host_quant(x, q);
     }
+}
+
+// the context of every library that decodes through these tables; a library's <library>_ctx_s derives from it and adds nothing
+struct CodeCtx {
+    DeviceTable t;     // Tables
+    InQuant q;
+};
+
+// a <library>_table entry: the RGB form of every byte code in the input domain, built on the host
+[[maybe_unused]] static int code_table(const char *who, float scale_in, int zero_in, int exact_div, int8_t *q, float *x) {
+    g_err[0] = 0;
+    if (!q || !x) return fail("%s: q or x is NULL", who);
+    if (check_domain(who, scale_in, zero_in, exact_div)) return 1;
+    static thread_local Tables t;
+    build(in_quant(scale_in, zero_in, exact_div), t);
+    for (int v = 0; v < CODES; ++v) {
+        q[v] = t.q[v];
+        x[v] = t.x[v];
+    }
+    return 0;
+}
+
+// a <library>_create entry: the tables of an input domain on the current device
+template <class Ctx>
+static int code_create(const char *who, float scale_in, int zero_in, int exact_div, Ctx **out) {
+    g_err[0] = 0;
+    if (!out) return fail("%s: ctx is NULL", who);
+    *out = nullptr;
+    if (check_domain(who, scale_in, zero_in, exact_div)) return 1;
+    auto *c = new Ctx();
+    c->q = in_quant(scale_in, zero_in, exact_div);
+    Tables *host = new Tables();
+    build(c->q, *host);
+    const int rc = ctx_publish(who, c, host, sizeof(Tables), out);
+    delete host;
+    return rc;
 }
 
 }  // namespace sesrq_imgdec

@@ -1,9 +1,10 @@
-// Host scaffold of the side libraries (libsesrq_eval.so, libsesrq_raw.so, libsesrq_image.so): the error buffer, the launch counters
-// behind their exported instance lists and the end of an entry that launched one of them, the input-domain check and host q0
-// quantiser, and a context that keeps one host table on a device.  For the two Bayer unpack libraries (raw, sensor; their device
-// body is sesrq_bayer_unpack.h) also the q0 table of a level count, the shared argument checks of their unpack entries and a
-// context's publish / destroy; for the colour and the video export (their chroma upscale is sesrq_chroma_upscale.h) the check of
-// the luma arguments and the frame size.
+// Host scaffold of the side libraries (eval, raw, image, mosaic, sensor, noise, colour, downscale, video, video_rgb, develop): the
+// error buffer, the launch counters behind their exported instance lists and the end of an entry that launched one of them, the
+// input-domain check and host q0 quantiser, and a context that keeps one host table on a device.  For the two Bayer unpack libraries
+// (raw, sensor; their device body is sesrq_bayer_unpack.h) also the q0 table of a level count, the shared argument checks of their
+// unpack entries and a context's publish / destroy; for the exports (image, colour, video, video_rgb, develop) the check of a
+// prediction's dtype and output domain, the run count of a planar frame and, for the colour and the video export (their chroma
+// upscale is sesrq_chroma_upscale.h), the check of r and the frame size.
 // Each library stays a library of its own; only this host code is shared.  Everything here has internal
 // linkage (static, or the anonymous namespace), so a library exports exactly what its own header declares.  No device code.
 #pragma once
@@ -99,17 +100,35 @@ struct DeviceTable {
     return 0;
 }
 
-// What the colour and the video export refuse of the net's luma (y_dtype: LUMA_F32 or LUMA_I8 with its output domain), of r and
-// of the LR frame; then the tiles of out_w x out_h output pixels that cover the r H x r W frame, N frames of which must fit a grid.
-enum { LUMA_F32 = 0, LUMA_I8 = 1 };
+// The H W pixels of a planar frame as runs of `seg`: N ceil(H W / seg) items of a grid-stride launch, which must fit an int together
+// with one grid round, as H W itself must.
+[[maybe_unused]] static int pixel_runs(const char *who, int N, int H, int W, int seg, long long round, int *segs, int *items) {
+    const long long HW = (long long)H * W, s = (HW + seg - 1) / seg, n = (long long)N * s;
+    if (HW > 0x7fffffffLL || n > 0x7fffffffLL - round) return fail("%s: frame of %d x %d x %d is too large", who, N, H, W);
+    *segs = (int)s;
+    *items = (int)n;
+    return 0;
+}
+
+// What every export refuses of the net's prediction `p`, which its entry calls `name` (its dtype: <name>_dtype): a dtype that is
+// neither PRED_F32 nor PRED_I8, an int8 one without a usable output domain, an fp32 one that is not 4-byte aligned.
+// aligned = false skips the last: sesrq_image_export has always accepted such a pointer (its kernel then takes the per-pixel path).
+enum { PRED_F32 = 0, PRED_I8 = 1 };
+[[maybe_unused]] static int check_pred(const char *who, const char *name, const void *p, int dtype, float scale, int zero, bool aligned) {
+    if (dtype != PRED_F32 && dtype != PRED_I8) return fail("%s: %s_dtype %d (0 = fp32, 1 = int8)", who, name, dtype);
+    if (dtype == PRED_I8 && (!(scale > 0.f) || !std::isfinite(scale)))
+        return fail("%s: an int8 %s needs a positive, finite output scale", who, name);
+    if (dtype == PRED_I8 && (zero < -128 || zero > 127)) return fail("%s: zero %d outside the int8 range", who, zero);
+    if (aligned && dtype == PRED_F32 && (reinterpret_cast<uintptr_t>(p) & 3)) return fail("%s: an fp32 %s is not 4-byte aligned", who, name);
+    return 0;
+}
+
+// What the colour and the video export refuse of the net's luma, of r and of the LR frame; then the tiles of out_w x out_h output
+// pixels that cover the r H x r W frame, N frames of which must fit a grid.
 [[maybe_unused]] static int check_luma_export(const char *who, const void *y, int y_dtype, float scale, int zero, int r, int N, int H, int W,
                                               int out_w, int out_h, int *tiles_x, int *tiles_y) {
     if (!y) return fail("%s: y is NULL", who);
-    if (y_dtype != LUMA_F32 && y_dtype != LUMA_I8) return fail("%s: y_dtype %d (0 = fp32, 1 = int8)", who, y_dtype);
-    if (y_dtype == LUMA_I8 && (!(scale > 0.f) || !std::isfinite(scale)))
-        return fail("%s: an int8 luma needs a positive, finite output scale", who);
-    if (y_dtype == LUMA_I8 && (zero < -128 || zero > 127)) return fail("%s: zero %d outside the int8 range", who, zero);
-    if (y_dtype == LUMA_F32 && (reinterpret_cast<uintptr_t>(y) & 3)) return fail("%s: an fp32 y is not 4-byte aligned", who);
+    if (check_pred(who, "y", y, y_dtype, scale, zero, true)) return 1;
     if (r != 2 && r != 4) return fail("%s: r = %d (2 or 4)", who, r);
     if (N < 1 || H < 1 || W < 1) return fail("%s: empty frame (N = %d, H = %d, W = %d)", who, N, H, W);
     const long long rW = (long long)r * W, rH = (long long)r * H, tx = (rW + out_w - 1) / out_w, ty = (rH + out_h - 1) / out_h;

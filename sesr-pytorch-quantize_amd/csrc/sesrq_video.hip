@@ -26,6 +26,8 @@
 #include "sesrq_side.h"
 #include "sesrq_image_decode.h"
 #include "sesrq_chroma_upscale.h"
+#include "sesrq_pred_byte.h"
+#include "sesrq_video_surface.h"
 
 namespace sesrq_vidk {
 
@@ -44,6 +46,8 @@ enum { OUT_Q = 1, OUT_F = 2 };
 
 using sesrq_imgdec::Tables;
 using sesrq_imgdec::RGB_WORDS;
+using sesrq_pred::dequant;
+using sesrq_pred::to_byte;
 static_assert(CODES == sesrq_imgdec::CODES, "one table for both libraries");
 
 struct DecodeArgs {
@@ -128,9 +132,6 @@ __global__ __launch_bounds__(DEC_THREADS) void video_decode(DecodeArgs a) {
         }
     }
 }
-
-// step 2 of the header: u = trunc(fl32(clip(p, 0, 1) * 255)); a NaN gives 0
-__device__ inline unsigned to_byte(float p) { return (unsigned)__fmul_rn(fminf(fmaxf(p, 0.f), 1.f), 255.f); }
 
 // step 3's last line: the byte of an upscaled Q6 sample
 __device__ inline unsigned chroma_byte(int c) { return (unsigned)min(max((c + 32) >> 6, 0), 255); }
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(Shape<R>::THREADS, 8) void video_export(ExportArgs 
         }
     }
     if (YD == SESRQ_VIDEO_I8)                                        // an int8 luma has 256 codes: the byte of each, one code a lane
-        s_u[tid] = (uint8_t)to_byte(__fmul_rn((float)(tid - 128 - a.zero), a.scale));
+        s_u[tid] = (uint8_t)to_byte(dequant(tid - 128, a.zero, a.scale));
 #pragma unroll
     for (int i = 0; i < S::STAGE; ++i) {
         const int p = tid + i * THREADS;
@@ -334,12 +335,8 @@ __global__ __launch_bounds__(Shape<R>::THREADS, 8) void video_export(ExportArgs 
 
 using namespace sesrq_vidk;
 
-struct sesrq_video_ctx_s {
-    DeviceTable t;     // Tables
-    InQuant q;
-};
-
-static_assert(SESRQ_VIDEO_F32 == LUMA_F32 && SESRQ_VIDEO_I8 == LUMA_I8, "check_luma_export's y_dtype");
+struct sesrq_video_ctx_s : sesrq_imgdec::CodeCtx {};
+static_assert(SESRQ_VIDEO_F32 == PRED_F32 && SESRQ_VIDEO_I8 == PRED_I8, "check_pred's dtype");
 
 enum { K_DQ = 0, K_DF, K_DQF, K_Q2N, K_Q2I, K_Q4N, K_Q4I, K_F2N, K_F2I, K_F4N, K_F4I, K_COUNT };
 static const char *const kNames[K_COUNT] = {"video_decode<q0>",           "video_decode<x>",           "video_decode<q0,x>",
@@ -348,49 +345,15 @@ static const char *const kNames[K_COUNT] = {"video_decode<q0>",           "video
                                             "video_export<f32,r4,nv12>",  "video_export<f32,r4,i420>"};
 static Counters<K_COUNT> g_count{kNames};
 
-using sesrq_imgdec::build;
-
 extern "C" int sesrq_video_table(float scale_in, int zero_in, int exact_div, int8_t q[SESRQ_VIDEO_CODES], float x[SESRQ_VIDEO_CODES]) {
-    g_err[0] = 0;
-    if (!q || !x) return fail("sesrq_video_table: q or x is NULL");
-    if (check_domain("sesrq_video_table", scale_in, zero_in, exact_div)) return 1;
-    static thread_local Tables t;
-    build(in_quant(scale_in, zero_in, exact_div), t);
-    for (int v = 0; v < CODES; ++v) {
-        q[v] = t.q[v];
-        x[v] = t.x[v];
-    }
-    return 0;
+    return sesrq_imgdec::code_table("sesrq_video_table", scale_in, zero_in, exact_div, q, x);
 }
 
 extern "C" int sesrq_video_create(float scale_in, int zero_in, int exact_div, sesrq_video_ctx *out) {
-    g_err[0] = 0;
-    if (!out) return fail("sesrq_video_create: ctx is NULL");
-    *out = nullptr;
-    if (check_domain("sesrq_video_create", scale_in, zero_in, exact_div)) return 1;
-    auto *c = new sesrq_video_ctx_s();
-    c->q = in_quant(scale_in, zero_in, exact_div);
-    Tables *host = new Tables();
-    build(c->q, *host);
-    const hipError_t e = table_create(c->t, host, sizeof(Tables));
-    delete host;
-    if (e != hipSuccess) {
-        delete c;
-        return fail("sesrq_video_create: %s", hipGetErrorString(e));
-    }
-    *out = c;
-    return 0;
+    return sesrq_imgdec::code_create("sesrq_video_create", scale_in, zero_in, exact_div, out);
 }
 
 extern "C" void sesrq_video_destroy(sesrq_video_ctx c) { ctx_destroy(c); }
-
-static int check_format(const char *who, const char *what, int format) {
-    if (format != SESRQ_VIDEO_NV12 && format != SESRQ_VIDEO_I420) return fail("%s: %s format %d (0 = NV12, 1 = I420)", who, what, format);
-    return 0;
-}
-
-// the bytes of a chroma row of a surface whose chroma planes are cw samples wide
-static long long chroma_row_bytes(int format, long long cw) { return format == SESRQ_VIDEO_NV12 ? 2 * cw : cw; }
 
 extern "C" int sesrq_video_decode(sesrq_video_ctx c, const sesrq_video_surface *src, int8_t *q0, float *x, int N, int H, int W,
                                   void *stream) {
@@ -398,12 +361,11 @@ extern "C" int sesrq_video_decode(sesrq_video_ctx c, const sesrq_video_surface *
     const char *who = "sesrq_video_decode";
     if (!c) return fail("%s: ctx is NULL", who);
     if (!src) return fail("%s: src is NULL", who);
-    if (!src->y) return fail("%s: the Y plane of src is NULL", who);
+    if (check_planes(who, "src", src, PLANE_Y)) return 1;
     if (!q0 && !x) return fail("%s: neither q0 nor x requested", who);
     if (reinterpret_cast<uintptr_t>(x) & 3) return fail("%s: x is not 4-byte aligned", who);
     if (N < 1 || H < 1 || W < 1) return fail("%s: empty frame (N = %d, H = %d, W = %d)", who, N, H, W);
-    if (src->pitch_y < W) return fail("%s: pitch_y %lld is below the row's %d bytes", who, (long long)src->pitch_y, W);
-    if (src->frame_y < 0) return fail("%s: frame_y %lld is negative", who, (long long)src->frame_y);
+    if (check_pitches(who, "", src, PLANE_Y, W) || check_frames_in(who, "", src, PLANE_Y)) return 1;
     // the generous grid round (1024 CUs) keeps the size check before any HIP call
     if ((long long)N * H > 0x7fffffffLL) return fail("%s: frame of %d x %d x %d is too large", who, N, H, W);
     int segs, items;
@@ -446,24 +408,13 @@ extern "C" int sesrq_video_export(const void *y, int y_dtype, float scale, int z
     if (!lr) return fail("%s: lr is NULL", who);
     if (!out) return fail("%s: out is NULL", who);
     if (check_format(who, "lr", lr->format) || check_format(who, "out", out->format)) return 1;
-    if (!lr->c0 || (lr->format == SESRQ_VIDEO_I420 && !lr->c1)) return fail("%s: a chroma plane of lr is NULL", who);
-    if (!out->y) return fail("%s: the Y plane of out is NULL", who);
-    if (!out->c0 || (out->format == SESRQ_VIDEO_I420 && !out->c1)) return fail("%s: a chroma plane of out is NULL", who);
     const long long rW = (long long)r * W, rH = (long long)r * H;
-    const long long lrow = chroma_row_bytes(lr->format, ((long long)W + 1) / 2), orow = chroma_row_bytes(out->format, rW / 2);
-    if (lr->pitch_c < lrow) return fail("%s: pitch_c %lld of lr is below the row's %lld bytes", who, (long long)lr->pitch_c, lrow);
-    if (out->pitch_y < rW) return fail("%s: pitch_y %lld of out is below the row's %lld bytes", who, (long long)out->pitch_y, rW);
-    if (out->pitch_c < orow) return fail("%s: pitch_c %lld of out is below the row's %lld bytes", who, (long long)out->pitch_c, orow);
-    if (lr->frame_c < 0) return fail("%s: frame_c %lld of lr is negative", who, (long long)lr->frame_c);
-    if (N > 1 && (out->frame_y < (rH - 1) * out->pitch_y + rW || out->frame_c < (rH / 2 - 1) * out->pitch_c + orow))
-        return fail("%s: a frame stride of out (%lld, %lld) is below its plane's extent", who, (long long)out->frame_y,
-                    (long long)out->frame_c);
+    if (check_planes(who, "lr", lr, PLANE_C) || check_planes(who, "out", out, PLANE_Y | PLANE_C)) return 1;
+    if (check_pitches(who, " of lr", lr, PLANE_C, W) || check_pitches(who, " of out", out, PLANE_Y | PLANE_C, rW)) return 1;
+    if (check_frames_in(who, " of lr", lr, PLANE_C) || check_frames_out(who, "out", out, N, rH, rW, false)) return 1;
 
     a.y = y;
-    const bool lnv = lr->format == SESRQ_VIDEO_NV12;
-    a.cb = static_cast<const uint8_t *>(lr->c0);
-    a.cr = lnv ? a.cb + 1 : static_cast<const uint8_t *>(lr->c1);
-    a.lr_step = lnv ? 2 : 1;
+    a.lr_step = chroma_in(lr, &a.cb, &a.cr);
     a.lr_pitch = lr->pitch_c;
     a.lr_frame = lr->frame_c;
     a.oy = static_cast<uint8_t *>(out->y);

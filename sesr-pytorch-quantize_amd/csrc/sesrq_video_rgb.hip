@@ -26,6 +26,8 @@
 #include "sesrq_side.h"
 #include "sesrq_image_decode.h"
 #include "sesrq_chroma_upscale.h"
+#include "sesrq_pred_byte.h"
+#include "sesrq_video_surface.h"
 
 namespace sesrq_vrgb {
 
@@ -51,6 +53,8 @@ static_assert(EXP_THREADS == CODES, "one int8 code a lane");
 
 using sesrq_imgdec::Tables;
 using sesrq_imgdec::RGB_WORDS;
+using sesrq_pred::dequant;
+using sesrq_pred::to_byte;
 static_assert(CODES == sesrq_imgdec::CODES, "one table for both libraries");
 
 struct DecodeArgs {
@@ -235,9 +239,6 @@ __global__ __launch_bounds__(THREADS) void vrgb_decode(DecodeArgs a) {
     }
 }
 
-// E1 of the header: u = trunc(fl32(clip(p, 0, 1) * 255)); a NaN gives 0
-__device__ inline unsigned to_byte(float p) { return (unsigned)__fmul_rn(fminf(fmaxf(p, 0.f), 1.f), 255.f); }
-
 // four waves a workgroup; no occupancy is asked for: the block's 24 words of bytes and the loads in flight of the per-element path
 // want more than the 128 VGPRs of 4 waves a SIMD, and a cap would spill them
 template <int DT, int FMT>
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(EXP_THREADS) void vrgb_export(ExportArgs a) {
     __shared__ uint8_t s_u[DT == SESRQ_VIDEO_I8 ? CODES : 4];         // the byte of int8 code q at [q + 128]
     const int tid = threadIdx.x;
     if (DT == SESRQ_VIDEO_I8) {
-        s_u[tid] = (uint8_t)to_byte(__fmul_rn((float)(tid - 128 - a.zero), a.scale));
+        s_u[tid] = (uint8_t)to_byte(dequant(tid - 128, a.zero, a.scale));
         __syncthreads();
     }
     const int64_t it = (int64_t)blockIdx.x * EXP_THREADS + tid;
@@ -384,10 +385,8 @@ __global__ __launch_bounds__(EXP_THREADS) void vrgb_export(ExportArgs a) {
 
 using namespace sesrq_vrgb;
 
-struct sesrq_video_rgb_ctx_s {
-    DeviceTable t;     // Tables
-    InQuant q;
-};
+struct sesrq_video_rgb_ctx_s : sesrq_imgdec::CodeCtx {};
+static_assert(SESRQ_VIDEO_F32 == PRED_F32 && SESRQ_VIDEO_I8 == PRED_I8, "check_pred's dtype");
 
 enum { K_NQ = 0, K_NF, K_NQF, K_IQ, K_IF, K_IQF, K_EFN, K_EFI, K_EQN, K_EQI, K_COUNT };
 static const char *const kNames[K_COUNT] = {"vrgb_decode<nv12,q0>", "vrgb_decode<nv12,x>",   "vrgb_decode<nv12,q0,x>", "vrgb_decode<i420,q0>",
@@ -395,46 +394,16 @@ static const char *const kNames[K_COUNT] = {"vrgb_decode<nv12,q0>", "vrgb_decode
                                             "vrgb_export<i8,nv12>", "vrgb_export<i8,i420>"};
 static Counters<K_COUNT> g_count{kNames};
 
-using sesrq_imgdec::build;
-
 extern "C" int sesrq_video_rgb_table(float scale_in, int zero_in, int exact_div, int8_t q[SESRQ_VIDEO_RGB_CODES],
                                      float x[SESRQ_VIDEO_RGB_CODES]) {
-    g_err[0] = 0;
-    if (!q || !x) return fail("sesrq_video_rgb_table: q or x is NULL");
-    if (check_domain("sesrq_video_rgb_table", scale_in, zero_in, exact_div)) return 1;
-    static thread_local Tables t;
-    build(in_quant(scale_in, zero_in, exact_div), t);
-    for (int v = 0; v < CODES; ++v) {
-        q[v] = t.q[v];
-        x[v] = t.x[v];
-    }
-    return 0;
+    return sesrq_imgdec::code_table("sesrq_video_rgb_table", scale_in, zero_in, exact_div, q, x);
 }
 
 extern "C" int sesrq_video_rgb_create(float scale_in, int zero_in, int exact_div, sesrq_video_rgb_ctx *out) {
-    g_err[0] = 0;
-    const char *who = "sesrq_video_rgb_create";
-    if (!out) return fail("%s: ctx is NULL", who);
-    *out = nullptr;
-    if (check_domain(who, scale_in, zero_in, exact_div)) return 1;
-    auto *c = new sesrq_video_rgb_ctx_s();
-    c->q = in_quant(scale_in, zero_in, exact_div);
-    Tables *host = new Tables();
-    build(c->q, *host);
-    const int rc = ctx_publish(who, c, host, sizeof(Tables), out);
-    delete host;
-    return rc;
+    return sesrq_imgdec::code_create("sesrq_video_rgb_create", scale_in, zero_in, exact_div, out);
 }
 
 extern "C" void sesrq_video_rgb_destroy(sesrq_video_rgb_ctx c) { ctx_destroy(c); }
-
-static int check_format(const char *who, const char *what, int format) {
-    if (format != SESRQ_VIDEO_NV12 && format != SESRQ_VIDEO_I420) return fail("%s: %s format %d (0 = NV12, 1 = I420)", who, what, format);
-    return 0;
-}
-
-// the bytes of a chroma row of a surface whose chroma planes are cw samples wide
-static long long chroma_row_bytes(int format, long long cw) { return format == SESRQ_VIDEO_NV12 ? 2 * cw : cw; }
 
 extern "C" int sesrq_video_rgb_decode(sesrq_video_rgb_ctx c, const sesrq_video_surface *src, int8_t *q0, float *x, int N, int H, int W,
                                       void *stream) {
@@ -443,25 +412,18 @@ extern "C" int sesrq_video_rgb_decode(sesrq_video_rgb_ctx c, const sesrq_video_s
     if (!c) return fail("%s: ctx is NULL", who);
     if (!src) return fail("%s: src is NULL", who);
     if (check_format(who, "src", src->format)) return 1;
-    if (!src->y) return fail("%s: the Y plane of src is NULL", who);
-    if (!src->c0 || (src->format == SESRQ_VIDEO_I420 && !src->c1)) return fail("%s: a chroma plane of src is NULL", who);
+    if (check_planes(who, "src", src, PLANE_Y | PLANE_C)) return 1;
     if (!q0 && !x) return fail("%s: neither q0 nor x requested", who);
     if (reinterpret_cast<uintptr_t>(x) & 3) return fail("%s: x is not 4-byte aligned", who);
     if (N < 1 || H < 1 || W < 1) return fail("%s: empty frame (N = %d, H = %d, W = %d)", who, N, H, W);
-    const long long crow = chroma_row_bytes(src->format, ((long long)W + 1) / 2);
-    if (src->pitch_y < W) return fail("%s: pitch_y %lld is below the row's %d bytes", who, (long long)src->pitch_y, W);
-    if (src->pitch_c < crow) return fail("%s: pitch_c %lld is below the row's %lld bytes", who, (long long)src->pitch_c, crow);
-    if (src->frame_y < 0) return fail("%s: frame_y %lld is negative", who, (long long)src->frame_y);
-    if (src->frame_c < 0) return fail("%s: frame_c %lld is negative", who, (long long)src->frame_c);
+    if (check_pitches(who, "", src, PLANE_Y | PLANE_C, W) || check_frames_in(who, "", src, PLANE_Y | PLANE_C)) return 1;
     const long long tx = ((long long)W + TW - 1) / TW, ty = ((long long)H + TH - 1) / TH;
     if ((long long)N * tx * ty > 0x7fffffffLL) return fail("%s: frame of %d x %d x %d is too large", who, N, H, W);
     if (table_on_current(who, c->t)) return 1;
 
     DecodeArgs a;
-    const bool nv = src->format == SESRQ_VIDEO_NV12;
     a.y = static_cast<const uint8_t *>(src->y);
-    a.cb = static_cast<const uint8_t *>(src->c0);
-    a.cr = nv ? a.cb + 1 : static_cast<const uint8_t *>(src->c1);
+    chroma_in(src, &a.cb, &a.cr);
     a.tab = static_cast<const Tables *>(c->t.ptr);
     a.q0 = q0;
     a.x = x;
@@ -498,25 +460,13 @@ extern "C" int sesrq_video_rgb_export(const void *pred, int dtype, float scale, 
     g_err[0] = 0;
     const char *who = "sesrq_video_rgb_export";
     if (!pred) return fail("%s: pred is NULL", who);
-    if (dtype != SESRQ_VIDEO_F32 && dtype != SESRQ_VIDEO_I8) return fail("%s: dtype %d (0 = fp32, 1 = int8)", who, dtype);
-    if (dtype == SESRQ_VIDEO_I8 && (!(scale > 0.f) || !std::isfinite(scale)))
-        return fail("%s: an int8 pred needs a positive, finite output scale", who);
-    if (dtype == SESRQ_VIDEO_I8 && (zero < -128 || zero > 127)) return fail("%s: zero %d outside the int8 range", who, zero);
-    if (dtype == SESRQ_VIDEO_F32 && (reinterpret_cast<uintptr_t>(pred) & 3)) return fail("%s: an fp32 pred is not 4-byte aligned", who);
+    if (check_pred(who, "pred", pred, dtype, scale, zero, true)) return 1;
     if (!out) return fail("%s: out is NULL", who);
     if (check_format(who, "out", out->format)) return 1;
-    if (!out->y) return fail("%s: the Y plane of out is NULL", who);
-    if (!out->c0 || (out->format == SESRQ_VIDEO_I420 && !out->c1)) return fail("%s: a chroma plane of out is NULL", who);
+    if (check_planes(who, "out", out, PLANE_Y | PLANE_C)) return 1;
     if (N < 1 || H < 1 || W < 1) return fail("%s: empty frame (N = %d, H = %d, W = %d)", who, N, H, W);
     const long long pairs = ((long long)H + 1) / 2, segs = ((long long)W + SEG - 1) / SEG;
-    const long long crow = chroma_row_bytes(out->format, ((long long)W + 1) / 2);
-    if (out->pitch_y < W) return fail("%s: pitch_y %lld of out is below the row's %d bytes", who, (long long)out->pitch_y, W);
-    if (out->pitch_c < crow) return fail("%s: pitch_c %lld of out is below the row's %lld bytes", who, (long long)out->pitch_c, crow);
-    if (out->frame_y < 0 || out->frame_c < 0)
-        return fail("%s: a frame stride of out (%lld, %lld) is negative", who, (long long)out->frame_y, (long long)out->frame_c);
-    if (N > 1 && (out->frame_y < (H - 1) * out->pitch_y + W || out->frame_c < (pairs - 1) * out->pitch_c + crow))
-        return fail("%s: a frame stride of out (%lld, %lld) is below its plane's extent", who, (long long)out->frame_y,
-                    (long long)out->frame_c);
+    if (check_pitches(who, " of out", out, PLANE_Y | PLANE_C, W) || check_frames_out(who, "out", out, N, H, W, true)) return 1;
     // N pairs segs cannot overflow 64 bits: each factor is below 2^31 and segs below 2^27
     if ((long long)N * pairs > 0x7fffffffLL || (long long)N * pairs * segs > 0x7fffffffLL - EXP_THREADS)
         return fail("%s: frame of %d x %d x %d is too large", who, N, H, W);

@@ -1,6 +1,7 @@
 """ctypes binding of libsesrq.so (C ABI declared in include/sesrq.h), and the host plumbing every binding in the package shares:
-the loader (bind, Library), the stream entry of a launch, the host-array conversion, the input domain of the front ends and the
-luma arguments of the colour and the video export.
+the loader (bind, Library), the stream entry of a launch, the host-array conversion, the input domain of the front ends, and of the
+byte libraries the byte order, the check of a caller's uint8 output, the output domain of a prediction and the luma arguments of
+the colour and the video export.
 
 The library is the product: if it is missing or a symbol cannot be resolved this module
 raises immediately -- there is no CPU or PyTorch fallback anywhere in the package.
@@ -158,9 +159,13 @@ def bind(path: str, symbols: dict, who: str = "sesrq") -> C.CDLL:
     return handle
 
 
+BYTE_CODES = 256                    # SESRQ_IMAGE_CODES = SESRQ_VIDEO_CODES = SESRQ_VIDEO_RGB_CODES
+
+
 class Library:
     """One native library, loaded and bound on first use.  `prefix` names its C entry points: <prefix>_last_error, the launch
-    counters <prefix>_<counters>_{count,name,launches} and, for the raw / image front ends, <prefix>_create of a device context."""
+    counters <prefix>_<counters>_{count,name,launches} and, for the front ends that have them, <prefix>_create of a device context
+    and <prefix>_table of the byte codes."""
 
     def __init__(self, path: str, symbols: dict, who: str, prefix: str, counters: str = "instance"):
         self.path, self.symbols, self.who, self.prefix, self.counters = path, symbols, who, prefix, counters
@@ -195,6 +200,15 @@ class Library:
                     raise ValueError(self.last_error())
             self._ctx[key] = h
         return h
+
+    def table(self, scale_in: float, zero_in: int, exact_div: int = 0):
+        """Every byte code in an input domain (<prefix>_table, host): (q0 int8 (256,), x fp32 (256,)), x = clip(fl32(v / 255.0), 0, 1)."""
+        import numpy as np
+        q, x = np.empty(BYTE_CODES, np.int8), np.empty(BYTE_CODES, np.float32)
+        fn = getattr(self.lib(), self.prefix + "_table")
+        if fn(float(np.float32(scale_in)), int(zero_in), int(exact_div), q.ctypes.data, x.ctypes.data) != 0:
+            raise ValueError(self.last_error())
+        return q, x
 
 
 _core = Library(LIB_PATH, SYMBOLS, "sesrq", "sesrq")
@@ -242,6 +256,38 @@ def host_tensor(a):
     return torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
 
 
+ORDERS = {"rgb": 0, "bgr": 1}       # the byte order of an interleaved image: *_ORDER_RGB / *_ORDER_BGR of every byte library
+
+
+def byte_order(order) -> int:
+    o = ORDERS.get(str(order).lower())
+    if o is None:
+        raise ValueError(f"byte order {order!r}: 'rgb' (PIL) or 'bgr' (cv2)")
+    return o
+
+
+def check_u8_out(out, shape, device, who: str = "export"):
+    """A caller-supplied output is written through its data_ptr(): anything but a contiguous uint8 tensor of the output shape on the
+    device is refused before any launch."""
+    import torch
+    if (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != torch.uint8 or out.device != device
+            or not out.is_contiguous()):
+        raise ValueError(f"{who}: out must be a contiguous uint8 tensor of the output shape {tuple(shape)} on {device}")
+
+
+def pred_domain(pred, scale, zero, noun: str):
+    """(scale, zero) an export passes on with the net's output tensor `pred`, the `noun` ("prediction" / "luma") of its messages:
+    fp32 -- (0.0, 0) -- or int8 with the net's output domain."""
+    import torch
+    if pred.dtype == torch.float32:
+        return 0.0, 0
+    if pred.dtype != torch.int8:
+        raise ValueError(f"export: the {noun} must be float32 or int8")
+    if scale is None or zero is None:
+        raise ValueError(f"export: an int8 {noun} needs the output domain: scale and zero")
+    return scale, zero
+
+
 FACTORS = (2, 4)                    # what the chroma upscale of the colour and the video export takes
 Y_F32, Y_I8 = 0, 1                  # SESRQ_COLOUR_F32 / _I8 = SESRQ_VIDEO_F32 / _I8: the luma dtype of both exports
 
@@ -262,13 +308,7 @@ def luma_domain(y, shape, device, scale, zero, noun: str):
                          f"{tuple(y.shape) if isinstance(y, torch.Tensor) else type(y).__name__}")
     if y.device != device:
         raise ValueError(f"export: the luma is on {y.device}, the {noun} on {device}")
-    if y.dtype == torch.float32:
-        return 0.0, 0
-    if y.dtype != torch.int8:
-        raise ValueError("export: the luma must be float32 or int8")
-    if scale is None or zero is None:
-        raise ValueError("export: an int8 luma needs the output domain: scale and zero")
-    return scale, zero
+    return pred_domain(y, scale, zero, "luma")
 
 
 def input_domain(engine_or_bundle, want_q: bool, who: str):

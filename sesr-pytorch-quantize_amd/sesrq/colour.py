@@ -21,7 +21,7 @@ from ._lib import FACTORS, Y_F32, Y_I8
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "lib", "libsesrq_colour.so"))
 
-ORDERS = {"rgb": 0, "bgr": 1}
+ORDERS = _lib.ORDERS
 TILE_W, TILE_H = 32, 8              # SESRQ_COLOUR_TILE_W / _H: the export's LR tile at r = 4 (twice that each way at r = 2)
 
 # every symbol include/sesrq_colour.h declares: name -> (restype, argtypes)
@@ -38,13 +38,7 @@ SYMBOLS = {
 
 _so = _lib.Library(LIB_PATH, SYMBOLS, "sesrq.colour", "sesrq_colour")
 lib, last_error, instances = _so.lib, _so.last_error, _so.instances
-
-
-def _order(order) -> int:
-    o = ORDERS.get(str(order).lower())
-    if o is None:
-        raise ValueError(f"byte order {order!r}: 'rgb' (PIL) or 'bgr' (cv2)")
-    return o
+_order, check_out = _lib.byte_order, _lib.check_u8_out
 
 
 def _factor(r) -> int:
@@ -81,15 +75,6 @@ def chroma(img_u8, order: str = "rgb", stream=None):
     if rc != 0:
         raise ValueError(last_error())
     return out
-
-
-def check_out(out, shape, device, who: str = "export"):
-    """A caller-supplied output is written through its data_ptr(): anything but a contiguous uint8 tensor of the output shape on the
-    device is refused before any launch."""
-    import torch
-    if (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != torch.uint8 or out.device != device
-            or not out.is_contiguous()):
-        raise ValueError(f"{who}: out must be a contiguous uint8 tensor of the output shape {tuple(shape)} on {device}")
 
 
 def launch(y, scale, zero, img, order, r, out, stream):

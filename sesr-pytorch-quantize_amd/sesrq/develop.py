@@ -26,7 +26,7 @@ LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "lib", "libsesrq_develop.s
 LEVELS = 255
 GAMMA22, SRGB, TRUNC255 = 0, 1, 2           # SESRQ_DEVELOP_GAMMA22 / _SRGB / _TRUNC255
 CURVES = {"gamma": GAMMA22, "srgb": SRGB, "trunc255": TRUNC255}
-ORDERS = {"rgb": 0, "bgr": 1}
+ORDERS = _lib.ORDERS
 PRED_F32, PRED_I8 = 0, 1
 MFLAGS = (2, 3, 4)                          # the nets whose output is a linear camera-RGB image
 RGB2XYZ = ((0.4124564, 0.3575761, 0.1804375), (0.2126729, 0.7151522, 0.0721750), (0.0193339, 0.1191920, 0.9503041))
@@ -46,14 +46,8 @@ SYMBOLS = {
 
 _so = _lib.Library(LIB_PATH, SYMBOLS, "sesrq.develop", "sesrq_develop")
 lib, last_error, instances = _so.lib, _so.last_error, _so.instances
+_order, check_out = _lib.byte_order, _lib.check_u8_out
 _ctx = {}           # (profile bytes, device index) -> context handle; lives as long as the process
-
-
-def _order(order) -> int:
-    o = ORDERS.get(str(order).lower())
-    if o is None:
-        raise ValueError(f"byte order {order!r}: 'rgb' (PIL) or 'bgr' (cv2)")
-    return o
 
 
 def check_mflag(mflag: int) -> int:
@@ -161,15 +155,6 @@ def context(profile: Profile, device):
     return h
 
 
-def check_out(out, shape, device, who: str = "export"):
-    """A caller-supplied output is written through its data_ptr(): anything but a contiguous uint8 tensor of the output shape on the
-    device is refused before any launch."""
-    import torch
-    if (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != torch.uint8 or out.device != device
-            or not out.is_contiguous()):
-        raise ValueError(f"{who}: out must be a contiguous uint8 tensor of the output shape {tuple(shape)} on {device}")
-
-
 def launch(profile, pred, scale, zero, order, out, stream):
     """Enqueue one export of the contiguous (N, 3, H, W) `pred` into caller-owned `out` on `stream`."""
     import torch
@@ -196,14 +181,7 @@ def export(pred, profile, scale=None, zero=None, order: str = "rgb", out=None, s
         raise ValueError(f"export: {Ch} channels; a developed image comes from the 3 planes R, G, B")
     if pred.device.type != "cuda":
         raise ValueError("export: the prediction must be on a HIP device")
-    if pred.dtype == torch.float32:
-        s, z = 0.0, 0
-    elif pred.dtype == torch.int8:
-        if scale is None or zero is None:
-            raise ValueError("export: an int8 prediction needs the output domain: scale and zero")
-        s, z = scale, zero
-    else:
-        raise ValueError("export: the prediction must be float32 or int8")
+    s, z = _lib.pred_domain(pred, scale, zero, "prediction")
     dev = pred.device
     shape = (N, H, W, 3)
     if out is not None:

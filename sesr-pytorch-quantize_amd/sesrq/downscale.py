@@ -28,7 +28,7 @@ LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "lib", "libsesrq_downscale
 Y, RGB = 0, 1                       # SESRQ_DOWNSCALE_Y / SESRQ_DOWNSCALE_RGB: sesrq.image's forms
 FORMS = {"y": Y, "rgb": RGB}
 CHANNELS = {Y: 1, RGB: 3}
-ORDERS = {"rgb": 0, "bgr": 1}
+ORDERS = _lib.ORDERS
 FACTORS = (2, 4)
 MFLAG_FACTORS = {5: 4, 6: 2}        # SESR-x4 (Y), SESR-x2 (RGB)
 TILE_W, TILE_H = 32, 8              # SESRQ_DOWNSCALE_TILE_W / _H: the kernel's LR tile at r = 4 (twice that each way at r = 2)
@@ -48,6 +48,7 @@ SYMBOLS = {
 
 _so = _lib.Library(LIB_PATH, SYMBOLS, "sesrq.downscale", "sesrq_downscale")
 lib, last_error, instances = _so.lib, _so.last_error, _so.instances
+_order = _lib.byte_order
 
 
 def factor_of(mflag: int) -> int:
@@ -68,13 +69,6 @@ def _form(form) -> int:
     if f is None:
         raise ValueError(f"image form {form!r}: 'y' (MFLAG 5) or 'rgb' (MFLAG 6)")
     return f
-
-
-def _order(order) -> int:
-    o = ORDERS.get(str(order).lower())
-    if o is None:
-        raise ValueError(f"byte order {order!r}: 'rgb' (PIL) or 'bgr' (cv2)")
-    return o
 
 
 def weights(r: int):
@@ -123,12 +117,7 @@ def _on_device(img, device, who):
 
 
 def check_out(out, shape, device, who: str = "downscale"):
-    """A caller-supplied output is written through its data_ptr(): anything but a contiguous uint8 tensor of the output shape on the
-    image's device is refused before any launch."""
-    import torch
-    if (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != torch.uint8 or out.device != device
-            or not out.is_contiguous()):
-        raise ValueError(f"{who}: out must be a contiguous uint8 tensor of the output shape {tuple(shape)} on {device}")
+    _lib.check_u8_out(out, shape, device, who)
 
 
 def launch(device, scale_in, zero_in, exact_div, img, order, r, form, lr, q0, x, stream):

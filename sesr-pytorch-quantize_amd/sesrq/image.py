@@ -25,7 +25,7 @@ CODES = 256
 Y, RGB = 0, 1                       # SESRQ_IMAGE_Y / SESRQ_IMAGE_RGB
 FORMS = {"y": Y, "rgb": RGB}
 CHANNELS = {Y: 1, RGB: 3}
-ORDERS = {"rgb": 0, "bgr": 1}
+ORDERS = _lib.ORDERS
 PRED_F32, PRED_I8 = 0, 1
 MFLAG_FORMS = {5: "y", 6: "rgb"}
 
@@ -45,7 +45,8 @@ SYMBOLS = {
 }
 
 _so = _lib.Library(LIB_PATH, SYMBOLS, "sesrq.image", "sesrq_image")
-lib, last_error, instances = _so.lib, _so.last_error, _so.instances
+lib, last_error, instances, table = _so.lib, _so.last_error, _so.instances, _so.table
+_order = _lib.byte_order
 
 
 def form_of(mflag: int) -> str:
@@ -60,21 +61,6 @@ def _form(form) -> int:
     if f is None:
         raise ValueError(f"image form {form!r}: 'y' (MFLAG 5) or 'rgb' (MFLAG 6)")
     return f
-
-
-def _order(order) -> int:
-    o = ORDERS.get(str(order).lower())
-    if o is None:
-        raise ValueError(f"byte order {order!r}: 'rgb' (PIL) or 'bgr' (cv2)")
-    return o
-
-
-def table(scale_in: float, zero_in: int, exact_div: int = 0):
-    """The RGB form of every byte code (host): (q0 int8 (256,), x fp32 (256,)) with x = clip(fl32(v / 255.0), 0, 1)."""
-    q, x = np.empty(CODES, np.int8), np.empty(CODES, np.float32)
-    if lib().sesrq_image_table(float(np.float32(scale_in)), int(zero_in), int(exact_div), q.ctypes.data, x.ctypes.data) != 0:
-        raise ValueError(last_error())
-    return q, x
 
 
 # ------------------------------------------------------------------------------------------------------------------ files
@@ -197,20 +183,14 @@ def export(pred, order: str = "rgb", scale=None, zero=None, stream=None):
         raise ValueError(f"export: {Ch} channels; an 8-bit image has 1 or 3")
     if pred.device.type != "cuda":
         raise ValueError("export: the prediction must be on a HIP device")
-    if pred.dtype == torch.float32:
-        dt, s, z = PRED_F32, 0.0, 0
-    elif pred.dtype == torch.int8:
-        if scale is None or zero is None:
-            raise ValueError("export: an int8 prediction needs the output domain: scale and zero")
-        dt, s, z = PRED_I8, float(np.float32(scale)), int(zero)
-    else:
-        raise ValueError("export: the prediction must be float32 or int8")
+    s, z = _lib.pred_domain(pred, scale, zero, "prediction")
+    dt = PRED_F32 if pred.dtype == torch.float32 else PRED_I8
     dev = pred.device
     with torch.cuda.device(dev):
         pred = pred.contiguous()
         out = torch.empty((N, H, W, Ch), dtype=torch.uint8, device=dev)
         st = _lib.enter_stream(dev, stream, pred, out)
-        rc = lib().sesrq_image_export(pred.data_ptr(), dt, s, z, Ch, o, out.data_ptr(), N, H, W, st.cuda_stream)
+        rc = lib().sesrq_image_export(pred.data_ptr(), dt, float(np.float32(s)), int(z), Ch, o, out.data_ptr(), N, H, W, st.cuda_stream)
     if rc != 0:
         raise ValueError(last_error())
     return out

@@ -51,7 +51,7 @@ SYMBOLS = {
 }
 
 _so = _lib.Library(LIB_PATH, SYMBOLS, "sesrq.video", "sesrq_video")
-lib, last_error, instances = _so.lib, _so.last_error, _so.instances
+lib, last_error, instances, table = _so.lib, _so.last_error, _so.instances, _so.table
 
 
 def _format(fmt) -> int:
@@ -86,14 +86,6 @@ def frame_bytes(fmt, H: int, W: int) -> int:
     """Bytes of one unpadded H x W frame of a raw .yuv file: H W + 2 ceil(H / 2) ceil(W / 2)."""
     H, W = _size(H, W)
     return sum(r * b for r, b in plane_shapes(fmt, H, W))
-
-
-def table(scale_in: float, zero_in: int, exact_div: int = 0):
-    """Every Y byte code (host): (q0 int8 (256,), x fp32 (256,)) with x = clip(fl32(v / 255.0), 0, 1) -- sesrq.image.table's."""
-    q, x = np.empty(CODES, np.int8), np.empty(CODES, np.float32)
-    if lib().sesrq_video_table(float(np.float32(scale_in)), int(zero_in), int(exact_div), q.ctypes.data, x.ctypes.data) != 0:
-        raise ValueError(last_error())
-    return q, x
 
 
 def weights(r: int):

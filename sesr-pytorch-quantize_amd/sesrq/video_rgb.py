@@ -42,15 +42,7 @@ SYMBOLS = {
 }
 
 _so = _lib.Library(LIB_PATH, SYMBOLS, "sesrq.video_rgb", "sesrq_video_rgb")
-lib, last_error, instances = _so.lib, _so.last_error, _so.instances
-
-
-def table(scale_in: float, zero_in: int, exact_div: int = 0):
-    """Every RGB byte code (host): (q0 int8 (256,), x fp32 (256,)) with x = clip(fl32(v / 255.0), 0, 1) -- sesrq.image.table's."""
-    q, x = np.empty(CODES, np.int8), np.empty(CODES, np.float32)
-    if lib().sesrq_video_rgb_table(float(np.float32(scale_in)), int(zero_in), int(exact_div), q.ctypes.data, x.ctypes.data) != 0:
-        raise ValueError(last_error())
-    return q, x
+lib, last_error, instances, table = _so.lib, _so.last_error, _so.instances, _so.table
 
 
 def launch_decode(device, scale_in, zero_in, exact_div, src: Surface, q0, x, stream) -> None:
@@ -105,13 +97,7 @@ def _pred_domain(pred, scale, zero):
                          f"{tuple(pred.shape) if isinstance(pred, torch.Tensor) else type(pred).__name__}")
     if pred.device.type != "cuda":
         raise ValueError("export: the prediction must be on a HIP device")
-    if pred.dtype == torch.float32:
-        return 0.0, 0
-    if pred.dtype != torch.int8:
-        raise ValueError("export: the prediction must be float32 or int8")
-    if scale is None or zero is None:
-        raise ValueError("export: an int8 prediction needs the output domain: scale and zero")
-    return scale, zero
+    return _lib.pred_domain(pred, scale, zero, "prediction")
 
 
 def export(pred, fmt=None, scale=None, zero=None, out=None, stream=None) -> Surface:
