@@ -362,6 +362,31 @@ class Calibrator:
         self.last_input = x
         return self._forward_device(x, out)
 
+    def enqueue_srgb(self, img_u8: torch.Tensor, profile, order: str = "rgb", out: Optional[torch.Tensor] = None, fmt=None,
+                     noise=None) -> torch.Tensor:
+        """8-bit display images (N, H, W, 3) / (H, W, 3) torch.uint8 on the device, in `order`, unprocessed on the device with
+        `profile` (a sesrq.unprocess.Profile) into the fp32 input frame enqueue_raw would form from the unprocessed sensor frame
+        (sesrq.unprocess, one kernel), and calibrated as enqueue() does.  fmt: the sesrq.sensor.Format of that frame (16-bit
+        containers; default the reference's 12-bit RGGB).  noise: a sesrq.noise.NoiseModel -- the kernel writes the clean sensor
+        frame instead and the call continues as enqueue_raw(raw, fmt=fmt, noise=noise)."""
+        from . import unprocess
+        self._check_device_pass("enqueue_srgb")
+        if self.in_channels != 3:
+            raise ValueError(f"Calibrator.enqueue_srgb: a raw RGGB frame feeds 3-channel nets; this one takes {self.in_channels}")
+        unprocess._order(order)
+        profile, f = unprocess._profile(profile), unprocess._format(fmt)
+        img = unprocess.images(img_u8, self.device).contiguous()
+        N, H, W, _ = img.shape
+        st = torch.cuda.current_stream(self.device)
+        if noise is not None:
+            raw = torch.empty((N, H, W), dtype=torch.uint16, device=self.device)
+            unprocess.launch(profile, f, 1.0, 0, 0, img, order, raw, None, None, None, st)
+            return self.enqueue_raw(raw, out, fmt=f, noise=noise)
+        x = self._acts(N, H, W)["input"]
+        unprocess.launch(profile, f, 1.0, 0, 0, img, order, None, None, None, x, st)
+        self.last_input = x
+        return self._forward_device(x, out)
+
     def enqueue_image(self, img_u8: torch.Tensor, order: str = "rgb", out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """8-bit images (N, H, W, 3) / (H, W, 3) torch.uint8 on the device, in `order`, decoded on the device into the reference's fp32
         input (sesrq.image: the float64 luma for a 1-channel net (MFLAG 5), RGB / 255 for a 3-channel one (MFLAG 6)) and calibrated

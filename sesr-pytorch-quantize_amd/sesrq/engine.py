@@ -380,6 +380,57 @@ class Engine:
         return self._run(raw, _lib.F32 if narrow else _lib.I8, want_q, want_f, out_q if want_q else None, out_f if want_f else None,
                          stream, slot, (N, 3, H, W), unpack)
 
+    def forward_srgb(self, img_u8: torch.Tensor, profile, order: str = "rgb", fmt=None, noise=None, want_gt: bool = False,
+                     want_q: bool = True, want_f: bool = True, out_q=None, out_f=None, stream=None, slot: int = 0):
+        """img_u8: (N, H, W, 3) or (H, W, 3) torch.uint8 display images on self.device, interleaved in `order` ->
+        (q int8 | None, y float32 | None), with want_gt (q, y, gt): gt the fp32 ground truth (N, 3, H, W) of the same frames.
+
+        forward_raw on the unprocessed image, without that frame: one kernel (libsesrq_unprocess.so, sesrq.unprocess) takes the
+        image through `profile` (a sesrq.unprocess.Profile: inverse tone curve, rgb2cam, inverse gains) to the Bayer frame of `fmt`
+        (a sesrq.sensor.Format in 16-bit containers; None: the reference's 12-bit RGGB) and writes this net's q0 -- the fp32 frame for
+        a net narrower than 8 bits -- into the kept input buffer, and the ground truth when asked; the same forward runs from there.
+        The results are those of forward_raw on unprocess.run(...)["raw"].  With `noise` (a sesrq.noise.NoiseModel) the kernel writes
+        the clean sensor frame instead and the call continues as forward_raw(raw, fmt=fmt, noise=noise).  Streams, slots and caller
+        outputs are forward_raw's, and everything forward_raw refuses is refused here too."""
+        from . import unprocess
+        if self.bundle.in_channels != 3:
+            raise ValueError(f"forward_srgb: a raw RGGB frame feeds 3-channel nets; this one takes {self.bundle.in_channels}")
+        if self.i8_in_scale != 0.0:
+            raise ValueError("forward_srgb: this engine takes an upstream net's int8 output as input (upstream=...), not q0")
+        if self.anchor_add:
+            raise ValueError("forward_srgb: anchor_add needs the fp32 input frame; use unprocess.run(..., want_spread=True) and forward()")
+        if not (want_q or want_f):
+            raise ValueError("forward_srgb: ask for the int8 output, the fp32 output or both")
+        unprocess._order(order)
+        profile, f = unprocess._profile(profile), unprocess._format(fmt)
+        img = unprocess.images(img_u8, self.device)
+        N, H, W, _ = img.shape
+        s0, z0 = self.bundle.scale[0], self.bundle.zero[0]
+        if noise is not None:
+            from . import noise as noisemod
+            noisemod._model(noise)
+        # what _run would refuse of the caller's outputs, before the first launch of either route
+        self._check_out(out_q if want_q else None, out_f if want_f else None, self.out_shape(N, H, W))
+        with torch.cuda.device(self.device):
+            gt = torch.empty((N, 3, H, W), dtype=torch.float32, device=self.device) if want_gt else None
+            if noise is not None:
+                img = img.contiguous()
+                raw = torch.empty((N, H, W), dtype=torch.uint16, device=self.device)
+                unprocess.launch(profile, f, s0, z0, self.exact_div, img, order, raw, gt, None, None,
+                                 _lib.enter_stream(self.device, stream, img, raw, gt))
+                res = self.forward_raw(raw, want_q, want_f, out_q, out_f, stream, slot, fmt=f, noise=noise)
+            else:
+                narrow = self.quan_bits != 8       # the buffer holds q0, or the fp32 frame of a narrow net
+
+                def decode(src, buf, st):
+                    if gt is not None and st != torch.cuda.current_stream(self.device):
+                        gt.record_stream(st)
+                    unprocess.launch(profile, f, s0, z0, self.exact_div, src, order, None, gt, None if narrow else buf,
+                                     buf if narrow else None, st)
+                res = self._run(img, _lib.F32 if narrow else _lib.I8, want_q, want_f, out_q if want_q else None,
+                                out_f if want_f else None, stream, slot, (N, 3, H, W), decode)
+        return (*res, gt) if want_gt else res
+
     def forward_develop(self, raw: torch.Tensor, profile, order: str = "rgb", out=None, stream=None, slot: int = 0, fmt=None, stride=None,
                         width=None, noise=None):
         """raw: sensor frames as forward_raw takes them (with its fmt, stride, width and noise) -> the developed display images

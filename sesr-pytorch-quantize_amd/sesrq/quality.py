@@ -179,7 +179,7 @@ def score_anchored(pred, lr, gt, stream=None):
     return _run(_so, anchored_lib().sesrq_eval_anchored, d, (pred, lr, gt), (N, Ch, H, W), stream)
 
 
-KINDS = ("f32", "raw", "image", "hr")
+KINDS = ("f32", "raw", "image", "hr", "srgb")
 
 
 def check_mosaic_format(mflag: int, fmt):
@@ -201,7 +201,7 @@ def check_calibration_input(calibrator, mflag: int, kind: str, scored: bool = Tr
     if kind not in KINDS:
         raise ValueError(f"kind {kind!r}: one of {KINDS}")
     cin = calibrator.in_channels
-    if kind == "raw":
+    if kind in ("raw", "srgb"):
         if mflag not in RAW_MFLAGS:
             raise ValueError(f"MFLAG {mflag}: raw RGGB frames feed the denoise / demosaic nets (MFLAG 1, 2, 3, 4)")
         if cin != 3:
@@ -221,7 +221,7 @@ def check_calibration_input(calibrator, mflag: int, kind: str, scored: bool = Tr
                          "method='entropy' runs on the host pass (Calibrator.observe)")
 
 
-def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32", order: str = "rgb", fmt=None, noise=None):
+def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32", order: str = "rgb", fmt=None, noise=None, profile=None):
     """The reference's calibration loop (test.py:141-183) on the device: per frame the mode-0 forward (Calibrator.enqueue /
     enqueue_raw / enqueue_image, which also accumulates the running ranges) and the metrics of its output in the form the MFLAG uses
     -- MFLAG 6 the anchored output fl32(gfake + up2(inps)), formed inside the scoring kernel (score_anchored).  One synchronisation at
@@ -232,16 +232,18 @@ def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32",
     frames of the output shape, uint16 RGB frames (3, H, W) / (1, 3, H, W) (sesrq.raw.load_gt), or uint8 HR images in `order`
     (sesrq.image.load_gt); "hr": (H, W, 3) / (1, H, W, 3) uint8 HR images in `order`, sizes multiples of the net's factor -- each is
     its own ground truth and the source of its input (Calibrator.enqueue_hr; the matching entry of gts is not read).
-    fmt: the sesrq.sensor.Format of "raw" frames and uint16 ground truths (default: 12-bit RGGB, sesrq.raw).
+    "srgb": (H, W, 3) / (1, H, W, 3) uint8 display images in `order`, unprocessed on the device with `profile` (a
+    sesrq.unprocess.Profile; Calibrator.enqueue_srgb) -- the ground truth is the same profile's (the matching entry of gts is not read).
+    fmt: the sesrq.sensor.Format of "raw" and "srgb" frames and uint16 ground truths (default: 12-bit RGGB, sesrq.raw).
     noise: a sesrq.noise.NoiseModel for "raw" frames -- shot and read noise added on the device, consecutive frames getting
     consecutive frame numbers from the model's frame0 (the reference's TEST_RAW_ADD_NOISE).
     Returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
     import torch
     check_calibration_input(calibrator, mflag, kind)
-    if fmt is not None and kind != "raw":
-        raise ValueError("a sensor format belongs to raw frames (kind='raw')")
-    if noise is not None and kind != "raw":
-        raise ValueError("noise belongs to raw frames (kind='raw')")
+    if fmt is not None and kind not in ("raw", "srgb"):
+        raise ValueError("a sensor format belongs to raw frames (kind='raw', 'srgb')")
+    if noise is not None and kind not in ("raw", "srgb"):
+        raise ValueError("noise belongs to raw frames (kind='raw', 'srgb')")
     done = 0             # raw frames so far
     dev = calibrator.device
     form = FORMS[mflag]
@@ -256,6 +258,11 @@ def evaluate_calibration(calibrator, frames, gts, mflag: int, kind: str = "f32",
             else:
                 y = calibrator.enqueue_raw(x, fmt=fmt, noise=noise.advance(done))
                 done += y.shape[0]
+        elif kind == "srgb":   # one upload: the image is unprocessed on the device, and its ground truth comes from the same profile
+            from . import unprocess
+            y = calibrator.enqueue_srgb(x, profile, order=order, fmt=fmt, noise=None if noise is None else noise.advance(done))
+            done += y.shape[0]
+            g = unprocess.run(x, profile, fmt, order=order, want_raw=False)["gt"]
         elif kind == "hr":     # one upload: the HR image is downscaled and decoded on the device, and is the ground truth
             y = calibrator.enqueue_hr(x, order=order)
             g = x
@@ -353,6 +360,30 @@ def evaluate_raw(engine, raws, gts_u16, mflag: int, fmt=None, noise=None):
             done[0] += q.shape[0]
         return q, sensor.load_gt(g, fmt, dev)
     return _evaluate(engine, mflag, zip(raws, gts_u16), step)
+
+
+def evaluate_srgb(engine, images, profile, mflag: int, order: str = "rgb", fmt=None, noise=None):
+    """evaluate_raw from ordinary images: per image (H, W, 3) / (1, H, W, 3) uint8 in `order` (numpy or torch; uploaded at 3 B/px) one
+    kernel unprocesses it with `profile` (a sesrq.unprocess.Profile) into the net's input and the ground truth of the same launch
+    (Engine.forward_srgb with want_gt), the forward runs, and the int8 output is scored as evaluate() scores it.  The scores are
+    those of evaluate_raw on the frames and ground truths sesrq.unprocess.run would have written.  fmt (16-bit containers) and noise
+    as evaluate_raw takes them; MFLAG 1 scores the RGGB mosaic and refuses every other CFA order."""
+    form_of(mflag)
+    if mflag not in RAW_MFLAGS:
+        raise ValueError(f"MFLAG {mflag}: unprocessed images feed the denoise / demosaic nets (MFLAG 1, 2, 3, 4)")
+    check_mosaic_format(mflag, fmt)
+    dev = engine.device
+    if noise is not None:
+        from . import noise as noisemod
+        noisemod._model(noise)
+    done = [0]           # frames so far
+
+    def step(img, _, fp32):
+        q, _, gt = engine.forward_srgb(_lib.host_tensor(img).to(dev, non_blocking=True), profile, order=order, fmt=fmt,
+                                       noise=None if noise is None else noise.advance(done[0]), want_gt=True, want_q=True, want_f=False)
+        done[0] += q.shape[0]
+        return q, gt
+    return _evaluate(engine, mflag, ((i, None) for i in images), step)
 
 
 def evaluate_image(engine, lr_imgs, hr_imgs, mflag: int, order: str = "rgb"):

@@ -175,14 +175,16 @@ def main(argv=None):
     add_noise_flags(ap)
     add_video_flags(ap)
     add_develop_flags(ap)
+    add_unprocess_flags(ap)
     args = ap.parse_args(argv)
+    uprofile = unprocess_profile(ap, args)
     profile = develop_profile(ap, args)
     yuv = video_args(args)
     if yuv is not None:                     # --yuv stands in place of --input / --hr (video_args has refused them beside it)
         if args.save_lr:
             raise SystemExit("sim.py: --save-lr writes the LR image made from --hr")
     elif args.hr is None:
-        if args.input is None:
+        if args.input is None and uprofile is None:
             ap.error("the following arguments are required: --input")
         if args.save_lr:
             raise SystemExit("sim.py: --save-lr writes the LR image made from --hr")
@@ -192,9 +194,10 @@ def main(argv=None):
         if args.mflag not in (5, 6) or not is_image(args.hr, args.image):
             raise SystemExit("sim.py: --hr takes an 8-bit HR image (.png, or a uint8 .npy with --image) for the super-resolution nets "
                              "(--mflag 5 or 6)")
-    fmt = sensor_format(args, "sim.py", [args.input] if args.input else [])
-    noise_m = noise_model(args, "sim.py", [args.input] if args.input else [])
-    if fmt is not None and args.gt:
+    raws = [args.input] if args.input else [UNPROCESSED] if uprofile is not None else []
+    fmt = sensor_format(args, "sim.py", raws)
+    noise_m = noise_model(args, "sim.py", raws)
+    if fmt is not None and (args.gt or uprofile is not None):
         from sesrq import quality
         try:
             quality.check_mosaic_format(args.mflag, fmt)
@@ -215,12 +218,12 @@ def main(argv=None):
         if not torch.cuda.is_available():
             raise SystemExit("sim.py: the integer path needs a HIP device (no CPU fallback)")
         return run_yuv(args, yuv, model, keep=argv is not None)
-    as_image = args.hr is not None or is_image(args.input, args.image)
+    as_image = uprofile is None and (args.hr is not None or is_image(args.input, args.image))
     if args.colour and not (args.mflag == 5 and as_image and args.save_png):
         raise SystemExit("sim.py: --colour rebuilds colour around the luma net: it needs --mflag 5, an 8-bit LR image as --input "
                          "(.png, or a uint8 .npy with --image) and --save-png")
     lr_u8 = hr_u8 = None
-    if not as_image and not args.input.endswith(".raw"):
+    if not as_image and uprofile is None and not args.input.endswith(".raw"):
         inps = torch.load(args.input, weights_only=True, map_location="cpu") if args.input.endswith(".pt") else \
             torch.from_numpy(np.load(args.input))
     if not torch.cuda.is_available():
@@ -236,6 +239,8 @@ def main(argv=None):
                 lr_u8 = downscale.downscale(hr_u8, r, order=args.order)
         except ValueError as e:
             raise SystemExit(f"sim.py: {e}") from None
+    elif uprofile is not None:              # an sRGB image, unprocessed on the device: the sensor's frame, the net's input, the ground truth
+        raw, inps, ugt = unprocess_image(args, uprofile, fmt, noise_m)
     elif args.input.endswith(".raw"):       # the reference's loop: raw frame -> sparse RGGB mosaic / 4095, clamped -> model(inps)
         from sesrq import sensor           # fmt: a sensor's format (CFA order, levels, MIPI packing), or None for the reference's
         raw = torch.from_numpy(sensor.load_raw(args.input, fmt)).cuda()
@@ -263,6 +268,8 @@ def main(argv=None):
         score_against(args.hr, gfake, inps, args.mflag, gts=image.load_gt(hr_u8, args.mflag, gfake.device, order=args.order))
         if args.save_lr:
             save_lr_png(args.save_lr, lr_u8, args.order)
+    if uprofile is not None:                # the ground truth of the same launch
+        score_against(args.srgb, gfake, inps, args.mflag, gts=ugt)
     if args.gt:
         gts = None
         if is_image(args.gt, args.image):   # the HR image: the reference's gt formed on the device
@@ -300,27 +307,39 @@ def add_develop_flags(ap):
     ap.add_argument("--ccm", metavar="M", type=float, nargs=9, default=None,
                     help="with --develop: the colour-correction matrix (camera RGB -> display RGB), nine numbers row by row (default: "
                          "the identity)")
+    add_camera_flags(ap)
+
+
+def add_camera_flags(ap):
+    """--colormatrix / --red-gain / --blue-gain / --rgb-gain / --curve: the camera metadata --develop and --unprocess share."""
     ap.add_argument("--colormatrix", metavar="M", type=float, nargs=9, default=None,
                     help="with --develop, in place of --ccm and --wb: the camera's xyz2cam matrix, nine numbers row by row, turned into "
                          "cam2rgb as the reference's metadata2tensor does; gains from --red-gain, --blue-gain and --rgb-gain")
     ap.add_argument("--red-gain", type=float, default=None, help="with --colormatrix: the red white-balance gain (default 1)")
     ap.add_argument("--blue-gain", type=float, default=None, help="with --colormatrix: the blue white-balance gain (default 1)")
     ap.add_argument("--rgb-gain", type=float, default=None, help="with --colormatrix: the exposure gain on all three channels (default 1)")
-    ap.add_argument("--curve", choices=("gamma", "srgb", "trunc255"), default=None,
-                    help="with --develop: the tone curve -- gamma (o^(1/2.2), the default), srgb, or trunc255 (no curve: * 255, truncated)")
+    ap.add_argument("--curve", choices=("gamma", "srgb", "trunc255", "paper", "linear"), default=None,
+                    help="with --develop: the tone curve -- gamma (o^(1/2.2), the default), srgb, or trunc255 (no curve: * 255, truncated); "
+                         "with --unprocess: the curve that is undone -- paper (the default: inverse smoothstep, then ^2.2), gamma, srgb or "
+                         "linear -- and --develop then applies its counterpart (gamma, gamma, srgb, trunc255)")
 
 
 def develop_profile(ap, args):
     """The sesrq.develop.Profile the develop flags describe, or None without --develop; a flag error is an argparse error."""
     rest = [k for k in ("wb", "ccm", "colormatrix", "red_gain", "blue_gain", "rgb_gain", "curve") if getattr(args, k) is not None]
+    unp = getattr(args, "unprocess", False)
     if not args.develop:
-        if rest:
+        if [k for k in rest if not (unp and k in UNPROCESS_SHARED)]:
             ap.error("--wb, --ccm, --colormatrix, --red-gain, --blue-gain, --rgb-gain and --curve belong to --develop")
         return None
+    if args.curve is not None and args.curve not in (UNPROCESS_CURVES if unp else ("gamma", "srgb", "trunc255")):
+        ap.error(f"argument --curve: invalid choice: {args.curve!r} (--develop alone: choose from 'gamma', 'srgb', 'trunc255'; 'paper', "
+                 "'gamma', 'srgb' and 'linear' are the curves --unprocess undoes)")
+    curve = UNPROCESS_CURVES[args.curve or "paper"] if unp else args.curve or "gamma"
     if args.mflag not in (2, 3, 4):
         ap.error(f"--develop: MFLAG {args.mflag} does not return a linear camera-RGB image (2: dm, 3: nrdm_3 and 4: nrdm_6 do; the "
                  "output of 1, nr, is a mosaic; 5 and 6 are developed images already)")
-    if args.input is None or not args.input.endswith(".raw"):
+    if not unp and (args.input is None or not args.input.endswith(".raw")):
         ap.error("--develop: the developed image comes from a raw frame: it needs a *.raw file as --input")
     if not args.save_png:
         ap.error("--develop: the developed image is written as a PNG: it needs --save-png")
@@ -338,10 +357,78 @@ def develop_profile(ap, args):
         if args.colormatrix is not None:
             one = lambda v: 1.0 if v is None else v
             return develop.from_colormatrix(args.colormatrix, one(args.red_gain), one(args.blue_gain), one(args.rgb_gain),
-                                            curve=args.curve or "gamma")
-        return develop.Profile(args.wb or (1.0, 1.0, 1.0), args.ccm or (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), args.curve or "gamma")
+                                            curve=curve)
+        return develop.Profile(args.wb or (1.0, 1.0, 1.0), args.ccm or (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), curve)
     except ValueError as e:
         ap.error(f"--develop: {e}")
+
+
+UNPROCESSED = "unprocessed.raw"             # what --unprocess makes of --srgb is a raw input to the sensor and noise flags
+UNPROCESS_SHARED = ("colormatrix", "red_gain", "blue_gain", "rgb_gain", "curve")
+UNPROCESS_CURVES = {"paper": "gamma", "gamma": "gamma", "srgb": "srgb", "linear": "trunc255"}       # -> its develop counterpart
+
+
+def add_unprocess_flags(ap, many=False):
+    """--srgb / --unprocess / --no-highlight / --save-raw / --save-gt: a raw net's input and ground truth from an 8-bit image
+    (sesrq.unprocess); the camera comes from --colormatrix / --red-gain / --blue-gain / --rgb-gain, the curve from --curve."""
+    ap.add_argument("--srgb", nargs="+" if many else None, help="MFLAG 1 ... 4, in place of --input and --gt, with --unprocess: an 8-bit display image (.png, or a uint8 "
+                                   ".npy with --image) that is unprocessed on the device into the raw frame and its ground truth")
+    ap.add_argument("--unprocess", action="store_true", help="unprocess --srgb: inverse tone curve (--curve), rgb2cam of --colormatrix, "
+                                                             "inverse gains, mosaic in the format of --cfa / --black / --white")
+    ap.add_argument("--no-highlight", action="store_true", help="with --unprocess: plain inverse gains, no highlight preservation")
+    ap.add_argument("--save-raw", help="with --unprocess: write the sensor frame here (little-endian uint16; name it "
+                                       "<name>_<rows>_<cols>.raw to read it back with --input)")
+    ap.add_argument("--save-gt", help="with --unprocess: write the ground truth codes here: a 16-bit RGB .png, or a uint16 (1, 3, H, W) .npy "
+                                      "that --gt takes")
+
+
+def unprocess_profile(ap, args):
+    """The sesrq.unprocess.Profile the flags describe, or None without --unprocess; a flag error is an argparse error."""
+    if not args.unprocess:
+        if args.srgb or args.no_highlight or args.save_raw or args.save_gt:
+            ap.error("--srgb, --no-highlight, --save-raw and --save-gt belong to --unprocess")
+        return None
+    if args.mflag not in (1, 2, 3, 4):
+        ap.error(f"--unprocess: MFLAG {args.mflag} is no raw net (1: nr, 2: dm, 3: nrdm_3, 4: nrdm_6 are)")
+    if not args.srgb or not all(is_image(p, args.image) for p in ([args.srgb] if isinstance(args.srgb, str) else args.srgb)):
+        ap.error("--unprocess: the image comes with --srgb (.png, or a uint8 .npy with --image)")
+    if args.input is not None or args.gt is not None or getattr(args, "hr", None) is not None or getattr(args, "frames", None) is not None:
+        ap.error("--unprocess: --srgb is the input's source and the ground truth; give none of --input, --gt and --hr with it")
+    if args.curve == "trunc255" or (args.colormatrix is None and any(getattr(args, k) is not None for k in ("red_gain", "blue_gain", "rgb_gain"))):
+        ap.error("--unprocess: --curve is paper, gamma, srgb or linear; --red-gain, --blue-gain and --rgb-gain belong to --colormatrix")
+    from sesrq import unprocess
+    try:
+        one = lambda v: 1.0 if v is None else v
+        if args.colormatrix is None:
+            return unprocess.Profile(curve=args.curve or "paper", highlight=not args.no_highlight)
+        return unprocess.from_colormatrix(args.colormatrix, one(args.red_gain), one(args.blue_gain), one(args.rgb_gain),
+                                          args.curve or "paper", not args.no_highlight)
+    except ValueError as e:
+        ap.error(f"--unprocess: {e}")
+
+
+def unprocess_image(args, uprofile, fmt, noise_m):
+    """--srgb --unprocess: (raw frame, the net's fp32 input, ground truth) on the device from one launch (sesrq.unprocess.run); with
+    --add-noise the input is the noisy unpack of the clean frame, as for a *.raw file.  --save-raw / --save-gt write the frame and the codes."""
+    from sesrq import image, sensor, unprocess
+    try:
+        out = unprocess.run(torch.from_numpy(image.load_image(args.srgb)).cuda(), uprofile, fmt, order=args.order, want_spread=True)
+    except ValueError as e:
+        raise SystemExit(f"sim.py: {e}") from None
+    raw, inps = out["raw"], out["spread"]
+    if noise_m is not None:
+        from sesrq import noise
+        _, inps = noise.apply(None, raw, fmt, noise_m, want_q=False, want_spread=True)
+    f = fmt or sensor.REFERENCE
+    if args.save_raw:
+        raw.cpu().numpy().astype("<u2").tofile(args.save_raw)
+    if args.save_gt:
+        codes = (np.rint(out["gt"].cpu().numpy().astype(np.float64) * (f.white - f.black)) + f.black).astype(np.uint16)
+        if args.save_gt.lower().endswith(".png"):
+            unprocess.save_png16(args.save_gt, codes[0].transpose(1, 2, 0))
+        else:
+            np.save(args.save_gt, codes)
+    return raw, inps, out["gt"]
 
 
 def save_develop_png(path, gfake, profile, order):

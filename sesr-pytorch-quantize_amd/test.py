@@ -90,15 +90,25 @@ def main(argv=None):
     ap.add_argument("--float-skip", action="store_true", help="add the long skip in float even for a QAT checkpoint")
     sim.add_sensor_flags(ap)
     sim.add_noise_flags(ap)
+    sim.add_camera_flags(ap)
+    sim.add_unprocess_flags(ap, many=True)
     args = ap.parse_args(argv)
-    args.fmt = sim.sensor_format(args, "test.py", args.input)
-    args.noise = sim.noise_model(args, "test.py", args.input)
+    args.uprofile = sim.unprocess_profile(ap, args)
+    if args.uprofile is None and any(getattr(args, k) is not None for k in sim.UNPROCESS_SHARED):
+        ap.error("--colormatrix, --red-gain, --blue-gain, --rgb-gain and --curve belong to --unprocess")
+    if args.save_raw or args.save_gt:
+        ap.error("--save-raw and --save-gt write one frame: use sim.py")
+    raws = [sim.UNPROCESSED] if args.uprofile is not None else args.input
+    args.fmt = sim.sensor_format(args, "test.py", raws)
+    args.noise = sim.noise_model(args, "test.py", raws)
     if args.quan_bit is not None:
         define.QUAN_BIT = args.quan_bit
     define.check()
     print("QUAN_BIT:", define.QUAN_BIT)
     STORE.clear()
-    if args.hr is not None:
+    if args.uprofile is not None:
+        pass                                # unprocess_profile has refused --frames, --input, --gt and --hr beside --srgb
+    elif args.hr is not None:
         if args.frames is not None or args.input is not None or args.gt is not None:
             raise SystemExit("test.py: --hr images are the inputs' source and the ground truths; give none of --frames, --input and --gt "
                              "with them")
@@ -118,7 +128,7 @@ def main(argv=None):
     print("skip_quant_scale:", skip_s if skip_s is not None else "none (float long skip)")
     model = splice_calibration(fmodel)
     model.__dict__["sesrq_skip_quant_scale"] = skip_s         # read by sesrq.lowering.lower_calibration
-    if args.input is not None or args.gt is not None or args.hr is not None:
+    if args.input is not None or args.gt is not None or args.hr is not None or args.uprofile is not None:
         return dataset_pass(args, model)
     frames = torch.load(args.frames, weights_only=True, map_location="cpu") if args.frames.endswith(".pt") else torch.from_numpy(np.load(args.frames))
     if not torch.cuda.is_available():
@@ -206,7 +216,14 @@ def dataset_pass(args, model):
     if args.method != "minmax":
         raise SystemExit("test.py: --input / --gt run the device-resident pass, which computes the reference's min/max ranges only; "
                          "use --frames for --method entropy")
-    if args.hr is not None:
+    if args.uprofile is not None:           # --srgb --unprocess: images, unprocessed on the device; each is its own ground truth
+        kind, frames = load_inputs(args.srgb, args.image)
+        kind = "srgb"
+        try:
+            quality.check_mosaic_format(args.mflag, args.fmt)
+        except ValueError as e:
+            raise SystemExit(f"test.py: {e}") from None
+    elif args.hr is not None:
         from sesrq import downscale
         kind, frames = load_inputs(args.hr, args.image)
         try:
@@ -224,10 +241,10 @@ def dataset_pass(args, model):
     cin = next(m for m in model.modules() if isinstance(m, torch.nn.Conv2d)).in_channels
     try:       # the refusals of forward_raw / forward_image, before any device work
         quality.check_calibration_input(types.SimpleNamespace(in_channels=cin, method=args.method), args.mflag, kind,
-                                        scored=args.gt is not None or args.hr is not None)
+                                        scored=args.gt is not None or kind in ("hr", "srgb"))
     except ValueError as e:
         raise SystemExit(f"test.py: {e}") from None
-    gts = frames if kind == "hr" else load_gts(args.gt, kind, args.image) if args.gt else None
+    gts = frames if kind in ("hr", "srgb") else load_gts(args.gt, kind, args.image) if args.gt else None
     if gts is not None and len(gts) != len(frames):
         raise SystemExit(f"test.py: {len(frames)} input frames, {len(gts)} ground truths")
     if not torch.cuda.is_available():
@@ -236,7 +253,8 @@ def dataset_pass(args, model):
     cal = lower_calibration(model, dev)
     model.__dict__["_sesrq_cal"] = cal
     if gts is not None:
-        res = quality.evaluate_calibration(cal, frames, gts, args.mflag, kind=kind, order=args.order, fmt=args.fmt, noise=args.noise)
+        res = quality.evaluate_calibration(cal, frames, gts, args.mflag, kind=kind, order=args.order, fmt=args.fmt, noise=args.noise,
+                                           profile=args.uprofile)
         totalpsnr = totalssim = 0.0
         for _, psnr, ssim in res:
             print(float(psnr))
