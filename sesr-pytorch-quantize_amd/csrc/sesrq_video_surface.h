@@ -1,4 +1,4 @@
-// What the entries of the two video libraries (libsesrq_video.so, libsesrq_video_rgb.so) refuse of a sesrq_video_surface
+// What the entries of the video libraries (libsesrq_video.so, libsesrq_video_rgb.so, libsesrq_video_hr.so) refuse of a sesrq_video_surface
 // (include/sesrq_video.h), and the chroma pointers of an input surface.  An entry calls the checks in the order of its own refusals:
 // formats, planes, pitches, frame strides.  Host code with internal linkage.  Include after sesrq_side.h (fail) and sesrq_video.h.
 #pragma once
@@ -51,7 +51,7 @@ static int check_frames_out(const char *who, const char *what, const sesrq_video
 }
 
 // the chroma of an input surface: sample (row, col) of plane p (*cb, *cr) at p[row * pitch_c + col * step]; returns step
-static int chroma_in(const sesrq_video_surface *s, const uint8_t **cb, const uint8_t **cr) {
+[[maybe_unused]] static int chroma_in(const sesrq_video_surface *s, const uint8_t **cb, const uint8_t **cr) {
     const bool nv = s->format == SESRQ_VIDEO_NV12;
     *cb = static_cast<const uint8_t *>(s->c0);
     *cr = nv ? *cb + 1 : static_cast<const uint8_t *>(s->c1);

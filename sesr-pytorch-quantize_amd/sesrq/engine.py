@@ -639,6 +639,70 @@ class Engine:
             video_rgb.launch_export(pred, b.scale[b.L], b.zero[b.L], out, st)
         return (out, pred) if want_q else out
 
+    def forward_video_hr(self, hr, out=None, want_q: bool = False, stream=None, slot: int = 0):
+        """hr: a sesrq.video.Surface of N HR YUV 4:2:0 frames (NV12 or I420) on self.device, its luma a multiple of 2 r each way, r the
+        net's PixelShuffle factor -> the super-resolved frames as a Surface of the HR size; with want_q also the net's luma.
+
+        forward_video on the bicubically downscaled surface, without a ready-made LR clip: for luma nets (SESR-x4, MFLAG 5) one kernel
+        (libsesrq_video_hr.so, sesrq.video_hr) downscales the three planes by r, writes the LR chroma planes and decodes the LR luma
+        into this net's kept input buffer -- q0, or the fp32 frame for an anchor_add engine and a net narrower than 8 bits, exactly as
+        forward_video decides; the LR luma plane is never written.  Then the same forward runs and the same fused export writes the
+        output surface.  out, launches, streams and slots are forward_video's."""
+        from . import video, video_hr
+        b = self.bundle
+        if b.in_channels != 1 or b.out_channels != 1:
+            raise ValueError(f"forward_video_hr: a video surface feeds a luma net (1 channel in, 1 out); this net takes {b.in_channels} "
+                             f"and gives {b.out_channels}: RGB nets take an HR surface through forward_video_rgb_hr")
+        r = video._factor(b.pixel_shuffle)
+        if self.i8_in_scale != 0.0:
+            raise ValueError("forward_video_hr: this engine takes an upstream net's int8 output as input (upstream=...), not a surface")
+        s = video._on_device(hr, self.device, "forward_video_hr")
+        H, W = video_hr.lr_size(s, r, "forward_video_hr")
+        N = s.N
+        if out is not None:
+            video.check_out(out, None, N, r * H, r * W, self.device, "forward_video_hr")
+        # the buffer holds q0, or the fp32 frame an anchored forward adds back / a narrow net quantises itself
+        fp = self.anchor_add or self.quan_bits != 8
+        with torch.cuda.device(self.device):
+            lr = video.Surface.alloc(s.fmt, N, H, W, self.device)      # its chroma planes are written; the luma never leaves the kernel
+
+            def decode(surf, buf, st):
+                video_hr.launch(self.device, b.scale[0], b.zero[0], self.exact_div, surf, r, lr, None if fp else buf, buf if fp else None,
+                                st, lr_luma=False)
+            q, f = self._run(s, _lib.F32 if fp else _lib.I8, not fp, fp, None, None, stream, slot, (N, 1, H, W), decode)
+            luma = f if fp else q
+            if out is None:
+                out = video.Surface.alloc(s.fmt, N, r * H, r * W, self.device)
+            st = _lib.enter_stream(self.device, stream, luma, *lr.planes(), *out.planes())
+            video.launch_export(luma, b.scale[b.L], b.zero[b.L], lr, r, out, st)
+        return (out, luma) if want_q else out
+
+    def forward_video_rgb_hr(self, hr, out=None, want_q: bool = False, stream=None, slot: int = 0):
+        """hr: a sesrq.video.Surface of N HR YUV 4:2:0 frames on self.device, its luma a multiple of 2 r each way -> the super-resolved
+        frames as a Surface of the HR size; with want_q also the net's prediction.
+
+        forward_video_rgb on the bicubically downscaled surface, without a ready-made LR clip: for RGB nets (SESR-x2, MFLAG 6) one
+        kernel (libsesrq_video_hr.so, sesrq.video_hr) writes the whole LR surface, on which forward_video_rgb's decode, forward and
+        export run.  (The YCbCr -> RGB decode is not fused into the downscale: it needs the 4:4:4 upscale of LR chroma samples that
+        other workgroups produce.)  out, launches, streams and slots are forward_video_rgb's."""
+        from . import video, video_hr
+        b = self.bundle
+        if b.in_channels != 3 or b.out_channels != 3:
+            raise ValueError(f"forward_video_rgb_hr: the RGB route feeds an RGB net (3 channels in, 3 out); this net takes "
+                             f"{b.in_channels} and gives {b.out_channels}: a luma net takes an HR surface through forward_video_hr")
+        r = video_hr._factor(b.pixel_shuffle)
+        if self.i8_in_scale != 0.0:
+            raise ValueError("forward_video_rgb_hr: this engine takes an upstream net's int8 output as input (upstream=...), not a surface")
+        s = video._on_device(hr, self.device, "forward_video_rgb_hr")
+        H, W = video_hr.lr_size(s, r, "forward_video_rgb_hr")
+        if out is not None:
+            video.check_out(out, None, s.N, r * H, r * W, self.device, "forward_video_rgb_hr")
+        with torch.cuda.device(self.device):
+            lr = video.Surface.alloc(s.fmt, s.N, H, W, self.device)
+            st = _lib.enter_stream(self.device, stream, *s.planes(), *lr.planes())
+            video_hr.launch(self.device, 1.0, 0, 0, s, r, lr, None, None, st)
+        return self.forward_video_rgb(lr, out=out, want_q=want_q, stream=stream, slot=slot)
+
     def submission(self, frames, outs_q, streams, outs_f=None, group: int = 1):
         """A prepared batch of independent forwards for sesrq_forward_many: frame k = frames[k] -> outs_q[k] (/ outs_f[k]; either may be None) on
         streams[k % len(streams)] with workspace slot k % len(streams).  Returns a Submission; .enqueue(count, first=0) issues frames

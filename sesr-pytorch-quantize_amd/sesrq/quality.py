@@ -468,3 +468,33 @@ def evaluate_hr(engine, hr_imgs, mflag: int, order: str = "rgb"):
         q, y = engine.forward_hr(hr, order=order, want_q=not fp32, want_f=fp32)
         return (y if fp32 else q), imgmod.load_gt(hr, mflag, dev, order=order)
     return _evaluate(engine, mflag, ((h, None) for h in hr_imgs), step)
+
+
+def evaluate_video_hr(engine, hr_surfaces, mflag: int):
+    """evaluate_video (MFLAG 5) / evaluate_video_rgb (MFLAG 6) without the LR clip: per HR Surface (a frame or a batch, host or
+    device) ONE upload, which is both the ground truth -- decoded as those two decode it -- and, downscaled bicubically by the net's
+    factor on the device (sesrq.video_hr), the input: MFLAG 5 the q0 of the LR luma straight out of the downscale kernel, MFLAG 6 the
+    LR surface decoded to the fp32 RGB frame.  The scores are those of the sibling on the pair (LR surface sesrq.video_hr.run writes,
+    HR surface).  The luma of every HR surface must be a multiple of 2 r each way (sesrq.video_hr.modcrop).  One synchronisation at
+    the end; returns a host float64 array (frames, 3) of (mse, psnr, ssim)."""
+    from . import video, video_hr, video_rgb
+    r = video_hr.factor_of(mflag)
+    if engine.bundle.pixel_shuffle != r:
+        raise ValueError(f"MFLAG {mflag} downscales the HR surface by {r}; this net upscales by {engine.bundle.pixel_shuffle}")
+    if engine.bundle.in_channels != (1 if mflag == 5 else 3):
+        raise ValueError(f"MFLAG {mflag} takes a net of {1 if mflag == 5 else 3} channel(s) in; this net takes {engine.bundle.in_channels}")
+    dev = engine.device
+
+    def step(hr, _, fp32):
+        hr = video.to_device(hr, dev)
+        if mflag == 5:
+            _, q0, _ = video_hr.run(engine, hr, r, want_lr=False, want_q=True)
+            _, g = video.decode(None, hr, want_q=False, want_f=True)
+            q, _ = engine.forward(q0, want_q=True, want_f=False)
+            return q, g
+        lr, _, _ = video_hr.run(None, hr, r)
+        _, x = video_rgb.decode(None, lr, want_q=False, want_f=True)
+        _, g = video_rgb.decode(None, hr, want_q=False, want_f=True)
+        _, y = engine.forward(x, want_q=False, want_f=True)
+        return y, g
+    return _evaluate(engine, mflag, ((h, None) for h in hr_surfaces), step)

@@ -14,6 +14,7 @@ test.py produced (an ``output_pt`` directory) or from a bundle/fixture file.
     python sim.py --mflag 6 --params ... --hr HR.png --save-lr LR.png                      # the HR image alone: input and ground truth
     python sim.py --mflag 5 --params ... --yuv LR.yuv --size 960x540 --pix-fmt nv12 --save-yuv SR.yuv     # YUV 4:2:0 video in and out
     python sim.py --mflag 6 --params ... --yuv LR.yuv --size 1920x1080 --pix-fmt nv12 --save-yuv SR.yuv   # ... of the RGB net (YCbCr <-> RGB)
+    python sim.py --mflag 5 --params ... --hr-yuv HR.yuv --size 3840x2160 --pix-fmt nv12 --save-lr-yuv LR.yuv   # the HR clip alone: input and ground truth
     python sim.py --mflag 1 --ckpt nr_G.pth --calib output_pt --input a_132_128.raw --gt gt16.npy     # nr: scored on the Bayer mosaic
     python sim.py --mflag 3 --params ... --input a_132_128.raw --develop --colormatrix ... --red-gain 2.1 --blue-gain 1.6 --save-png OUT.png
 """
@@ -447,7 +448,7 @@ YUV_BATCH = 8          # frames of a .yuv sequence that go through as one batch
 
 def add_video_flags(ap):
     """--yuv / --size / --pix-fmt / --frames / --save-yuv / --out-pix-fmt / --gt-yuv: YUV 4:2:0 video through the luma net (sesrq.video)
-    or the RGB net (sesrq.video_rgb)."""
+    or the RGB net (sesrq.video_rgb); --hr-yuv / --save-lr-yuv: the same from the HR sequence alone (sesrq.video_hr)."""
     ap.add_argument("--yuv", help="MFLAG 5 / 6, in place of --input: a raw .yuv file of unpadded 8-bit 4:2:0 frames (with --size and "
                                   "--pix-fmt), decoded on the device; MFLAG 5: the Y plane is the net's input, MFLAG 6: the frame "
                                   "converted to RGB")
@@ -460,14 +461,26 @@ def add_video_flags(ap):
     ap.add_argument("--out-pix-fmt", choices=("nv12", "i420"), default=None, help="pixel format of --save-yuv (default: --pix-fmt)")
     ap.add_argument("--gt-yuv", help="with --yuv: the HR sequence (same frames, r times the size, --pix-fmt); its Y plane (MFLAG 6: the frame "
                                      "converted to RGB) is the ground truth the output is scored against")
+    ap.add_argument("--hr-yuv", help="MFLAG 5 / 6, in place of --yuv and --gt-yuv: the HR sequence alone (--size is ITS size); it is the "
+                                     "ground truth and, every plane downscaled bicubically by the net's factor on the device "
+                                     "(sesrq.video_hr), the input.  Its size must be a multiple of twice the factor each way, or is "
+                                     "cropped to one (top left) with --modcrop, the default")
+    ap.add_argument("--save-lr-yuv", help="with --hr-yuv: write the device-made LR sequence here as a raw .yuv file (--pix-fmt)")
 
 
 def video_args(args):
     """(W, H, (first, end) | None) of a --yuv run, or None without --yuv; a flag error ends the program."""
     rest = [k for k in ("size", "pix_fmt", "frames", "save_yuv", "out_pix_fmt", "gt_yuv") if getattr(args, k) is not None]
+    if args.hr_yuv is not None:
+        if args.yuv is not None or args.gt_yuv is not None or args.input is not None or args.hr is not None:
+            raise SystemExit("sim.py: --hr-yuv is the input's source and the ground truth; give none of --yuv, --gt-yuv, --input and --hr "
+                             "with it")
+        args.yuv = args.hr_yuv              # the checks below are those of a --yuv run
+    elif args.save_lr_yuv is not None:
+        raise SystemExit("sim.py: --save-lr-yuv writes the LR sequence made from --hr-yuv")
     if args.yuv is None:
         if rest:
-            raise SystemExit("sim.py: --size, --pix-fmt, --frames, --save-yuv, --out-pix-fmt and --gt-yuv belong to --yuv")
+            raise SystemExit("sim.py: --size, --pix-fmt, --frames, --save-yuv, --out-pix-fmt and --gt-yuv belong to --yuv / --hr-yuv")
         return None
     if args.mflag not in (5, 6) or args.input is not None or args.hr is not None or args.gt is not None or args.save_png or args.colour:
         raise SystemExit("sim.py: --yuv feeds the luma net (--mflag 5) or the RGB net (--mflag 6) in place of --input / --hr; its ground "
@@ -490,6 +503,8 @@ def run_yuv(args, yuv, model, keep=False):
     scored against --gt-yuv's Y plane, exported with the input's chroma to --save-yuv.  Prints what the image path prints.
     MFLAG 6 goes through sesrq.video_rgb instead: the frames decoded to RGB -> model(inps) -> the anchored output scored against
     --gt-yuv decoded to RGB and exported to --save-yuv as YCbCr 4:2:0.
+    With --hr-yuv the file is the HR sequence: each batch is uploaded once, is its own ground truth, and its LR surface is made on the
+    device (sesrq.video_hr.run), written to --save-lr-yuv when asked for.
     A batch's fp32 output (33 MB a 4K frame) is dropped once it is scored and saved, so device memory does not grow with the
     sequence: only a caller from Python (keep: main(argv) returns the whole output, on the device) and --save (host copies) hold it."""
     from sesrq import quality, video
@@ -505,9 +520,18 @@ def run_yuv(args, yuv, model, keep=False):
         gt = video.load_yuv(args.gt_yuv, r * W, r * H, args.pix_fmt, span) if args.gt_yuv else None
         if gt is not None and gt.N != lr.N:
             raise ValueError(f"{args.gt_yuv}: {gt.N} frames, {args.yuv} has {lr.N}")
+        if args.hr_yuv is not None:         # the HR clip alone: one upload a batch, the LR surface made on the device
+            from sesrq import video_hr
+            gt, lr = (video_hr.modcrop(lr, r) if args.modcrop else lr), None
         outs, rows, shape = [], [], None
-        for a in range(0, lr.N, YUV_BATCH):
-            part = video.to_device(lr[a:a + YUV_BATCH], dev)
+        for a in range(0, gt.N if lr is None else lr.N, YUV_BATCH):
+            if lr is None:
+                hr_part = video.to_device(gt[a:a + YUV_BATCH], dev)
+                part, _, _ = video_hr.run(None, hr_part, r)
+                if args.save_lr_yuv:
+                    video.save_yuv(args.save_lr_yuv, part, append=a > 0)
+            else:
+                part = video.to_device(lr[a:a + YUV_BATCH], dev)
             _, inps = route.decode(None, part, want_q=False, want_f=True)
             gfake = model(inps)
             pred = anchored(gfake, inps, args.mflag)        # test.py:149-155: MFLAG 6 + the nearest-upsampled input
@@ -517,7 +541,7 @@ def run_yuv(args, yuv, model, keep=False):
             elif args.save:
                 outs.append(gfake.cpu())
             if gt is not None:
-                _, g = route.decode(None, video.to_device(gt[a:a + YUV_BATCH], dev), want_q=False, want_f=True)
+                _, g = route.decode(None, hr_part if lr is None else video.to_device(gt[a:a + YUV_BATCH], dev), want_q=False, want_f=True)
                 rows.append(quality.score(pred, g, args.mflag))
             if args.save_yuv:
                 fmt = args.out_pix_fmt or args.pix_fmt
@@ -536,6 +560,8 @@ def run_yuv(args, yuv, model, keep=False):
         for _, psnr, _ in res:
             print(float(psnr))
         print(quality.TASKS[args.mflag] + ' mean psnr is: ', float(res[:, 1].sum()) / len(res), ' ssim is: ', float(res[:, 2].sum()) / len(res))
+    if args.save_lr_yuv:
+        print("lr yuv:", args.save_lr_yuv, (shape[0], shape[2] // r, shape[3] // r), args.pix_fmt)
     if args.save_yuv:
         print("yuv:", args.save_yuv, (shape[0], shape[2], shape[3]), args.out_pix_fmt or args.pix_fmt)
     return gfake if keep else None
