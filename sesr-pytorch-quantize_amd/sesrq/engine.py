@@ -564,6 +564,31 @@ class Engine:
             colour.launch(q, b.scale[b.L], b.zero[b.L], img, order, r, out, st)
         return out
 
+    def forward_resized(self, img_u8: torch.Tensor, size, order: str = "rgb", out=None, stream=None, slot: int = 0):
+        """img_u8: (N, H, W, 3) or (H, W, 3) torch.uint8 images on self.device, interleaved in `order` -> the super-resolved images at
+        a free size, (N, Ho, Wo, C) torch.uint8, size = (Ho, Wo), C the net's output channels (1 or 3; `order` also orders the 3).
+
+        forward_image followed by the fused resize export (libsesrq_resize.so, sesrq.resize) of the prediction this engine produces:
+        the anchored fp32 output of an anchor_add engine, the int8 output with the net's output domain otherwise.  The result is
+        Pillow's bicubic resize of image.export of that prediction, without the full-size bytes reaching memory.  out: a contiguous
+        uint8 tensor of the output shape to write into, refused before any launch when it is anything else.  All launches go to
+        `stream` (default: current), ordered as forward() orders them; give concurrent in-flight frames different slots."""
+        from . import image as imgmod, resize
+        b = self.bundle
+        if b.out_channels not in (1, 3):
+            raise ValueError(f"forward_resized: an 8-bit image has 1 or 3 channels; this net gives {b.out_channels}")
+        resize._order(order)
+        Ho, Wo = resize._size(size)
+        img = imgmod._images(img_u8, self.device)
+        N, H, W, _ = img.shape
+        r = b.pixel_shuffle
+        p = resize.plan(r * H, r * W, Ho, Wo, self.device)          # refuses the size pair before any launch
+        if out is not None:
+            resize.check_out(out, (N, Ho, Wo, b.out_channels), self.device, "forward_resized")
+        fp = self.anchor_add
+        q, y = self.forward_image(img, order=order, want_q=not fp, want_f=fp, stream=stream, slot=slot)
+        return resize.run(p, y if fp else q, None if fp else b.scale[b.L], None if fp else b.zero[b.L], order, out, stream)
+
     def forward_video(self, src, out=None, want_q: bool = False, stream=None, slot: int = 0):
         """src: a sesrq.video.Surface of N YUV 4:2:0 frames (NV12 or I420) on self.device -> the super-resolved frames as a Surface of
         r H x r W, r the net's PixelShuffle factor; with want_q also the net's luma: (surface, luma).

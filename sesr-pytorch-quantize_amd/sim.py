@@ -11,6 +11,7 @@ test.py produced (an ``output_pt`` directory) or from a bundle/fixture file.
     python sim.py --mflag 5 --params tests/golden/sesr_x4.params.npz --input tests/golden/rand_SR_Input_80x960.npy
     python sim.py --mflag 6 --params ... --input LR.png --gt HR.png --save-png SR.png      # 8-bit images (MFLAG 5 / 6)
     python sim.py --mflag 5 --params ... --input LR.png --colour --save-png SR.png         # the x4 luma net's output in colour
+    python sim.py --mflag 6 --params ... --input LR.png --out-size 1920x1080 --save-png OUT.png   # the output at a free size
     python sim.py --mflag 6 --params ... --hr HR.png --save-lr LR.png                      # the HR image alone: input and ground truth
     python sim.py --mflag 5 --params ... --yuv LR.yuv --size 960x540 --pix-fmt nv12 --save-yuv SR.yuv     # YUV 4:2:0 video in and out
     python sim.py --mflag 6 --params ... --yuv LR.yuv --size 1920x1080 --pix-fmt nv12 --save-yuv SR.yuv   # ... of the RGB net (YCbCr <-> RGB)
@@ -150,6 +151,9 @@ def main(argv=None):
     ap.add_argument("--order", choices=("rgb", "bgr"), default="rgb", help="byte order of uint8 .npy images (PNGs are read as RGB)")
     ap.add_argument("--save-png", help="write the output as an 8-bit PNG here (the reference's export: clip to [0, 1], * 255, "
                                        "truncate; MFLAG 6 the anchored output); frame k of a batch goes to <stem>_<k>.png")
+    ap.add_argument("--out-size", metavar="WxH", help="MFLAG 5 / 6 with --save-png: write the image at this size, not the net's -- the "
+                    "prediction resampled bicubically on the device (sesrq.resize: Pillow's 8-bit bicubic resize of the --save-png image, "
+                    "byte for byte; a downscale ratio above 4 is refused)")
     ap.add_argument("--colour", action="store_true", help="MFLAG 5 with an 8-bit LR image and --save-png: write the COLOUR image -- the "
                                                           "net's luma, the LR image's Cb / Cr upscaled bicubically, back to RGB "
                                                           "(sesrq.colour); without the flag the PNG is the grey luma, as the reference's")
@@ -220,6 +224,16 @@ def main(argv=None):
             raise SystemExit("sim.py: the integer path needs a HIP device (no CPU fallback)")
         return run_yuv(args, yuv, model, keep=argv is not None)
     as_image = uprofile is None and (args.hr is not None or is_image(args.input, args.image))
+    out_size = None
+    if args.out_size:
+        try:
+            wo, ho = (int(v) for v in args.out_size.lower().split("x"))
+            out_size = (ho, wo)
+        except ValueError:
+            raise SystemExit(f"sim.py: --out-size {args.out_size!r}: WxH, as 1920x1080") from None
+        if args.mflag not in (5, 6) or not args.save_png or args.colour or profile is not None:
+            raise SystemExit("sim.py: --out-size sizes the image --save-png writes for the super-resolution nets (--mflag 5 or 6, without "
+                             "--colour)")
     if args.colour and not (args.mflag == 5 and as_image and args.save_png):
         raise SystemExit("sim.py: --colour rebuilds colour around the luma net: it needs --mflag 5, an 8-bit LR image as --input "
                          "(.png, or a uint8 .npy with --image) and --save-png")
@@ -282,7 +296,7 @@ def main(argv=None):
     elif args.save_png and profile is not None:
         save_develop_png(args.save_png, gfake, profile, args.order)
     elif args.save_png:
-        save_png(args.save_png, gfake, inps, args.mflag)
+        save_png(args.save_png, gfake, inps, args.mflag, out_size)
     return gfake
 
 
@@ -627,11 +641,15 @@ def anchored(gfake, inps, mflag):
     return gfake + x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
 
 
-def save_png(path, gfake, inps, mflag):
+def save_png(path, gfake, inps, mflag, out_size=None):
     """The reference's PNG export (sim.py:163-169) on the device: clip to [0, 1], * 255 in fp32, truncate to uint8; PIL takes RGB
-    bytes, so no channel flip."""
-    from sesrq import image
-    u8 = image.export(anchored(gfake, inps, mflag), order="rgb").cpu().numpy()
+    bytes, so no channel flip.  out_size (rows, columns): those bytes resized bicubically in the same kernel (--out-size)."""
+    from sesrq import image, resize
+    pred = anchored(gfake, inps, mflag)
+    try:
+        u8 = (image.export(pred, order="rgb") if out_size is None else resize.export(pred, out_size, order="rgb")).cpu().numpy()
+    except ValueError as e:
+        raise SystemExit(f"sim.py: {e}") from None
     stem, ext = os.path.splitext(path)
     for k in range(u8.shape[0]):
         image.save_png(path if u8.shape[0] == 1 else f"{stem}_{k}{ext or '.png'}", u8[k])
