@@ -325,7 +325,7 @@ def evaluate(engine, frames, gts, mflag: int):
     return _evaluate(engine, mflag, zip(frames, gts), step)
 
 
-def evaluate_raw(engine, raws, gts_u16, mflag: int, fmt=None, noise=None):
+def evaluate_raw(engine, raws, gts_u16, mflag: int, fmt=None, noise=None, baseline=None):
     """The reference's MFLAG 1 ... 4 loop from raw frames to scores (test.py:30-55 with self_dataset.py TestDataset): per frame the
     12-bit RGGB raw frame is unpacked on the device into the net's q0 and run forward (Engine.forward_raw), its 16-bit RGB ground
     truth is mapped to / 4095 and clamped on the device (sesrq.raw.load_gt), and the int8 output is scored as evaluate() scores it.
@@ -339,12 +339,23 @@ def evaluate_raw(engine, raws, gts_u16, mflag: int, fmt=None, noise=None):
 
     noise: a sesrq.noise.NoiseModel -- the frames are clean and the model's shot and read noise is added on the device (the reference's
     TEST_RAW_ADD_NOISE).  The pass's first frame is the model's frame0 and consecutive frames get consecutive frame numbers, so the
-    scores follow from the model alone, whatever the batch split."""
+    scores follow from the model alone, whatever the batch split.
+
+    baseline: "malvar" or "bilinear" -- for MFLAG 2, 3, 4 the classical demosaic of the frame the net was given (the noisy one with
+    `noise`; Engine.forward_raw(baseline=...), sesrq.demosaic) is scored against the same ground truth, and the return is the pair
+    (the net's rows, the baseline's rows), both (frames, 3).  MFLAG 1 returns a mosaic, which a demosaic is no baseline of: refused."""
+    import torch
     from . import sensor
     form_of(mflag)
     if mflag not in RAW_MFLAGS:
         raise ValueError(f"MFLAG {mflag}: raw RGGB frames feed the denoise / demosaic nets (MFLAG 1, 2, 3, 4)")
     check_mosaic_format(mflag, fmt)
+    if baseline is not None:
+        from . import demosaic
+        demosaic.method_of(baseline)
+        if mflag == 1:
+            raise ValueError("MFLAG 1 (nr) is scored on the Bayer mosaic: a demosaic baseline belongs to MFLAG 2, 3, 4")
+    base_rows = []
     dev = engine.device
     if noise is not None:
         from . import noise as noisemod
@@ -352,14 +363,19 @@ def evaluate_raw(engine, raws, gts_u16, mflag: int, fmt=None, noise=None):
     done = [0]           # frames so far
 
     def step(r, g, fp32):
+        kw = {} if baseline is None else {"baseline": baseline}
         if noise is None:
-            q, _ = engine.forward_raw(_lib.host_tensor(r).to(dev, non_blocking=True), want_q=True, want_f=False, fmt=fmt)
+            q, *rest = engine.forward_raw(_lib.host_tensor(r).to(dev, non_blocking=True), want_q=True, want_f=False, fmt=fmt, **kw)
         else:
-            q, _ = engine.forward_raw(_lib.host_tensor(r).to(dev, non_blocking=True), want_q=True, want_f=False, fmt=fmt,
-                                      noise=noise.advance(done[0]))
+            q, *rest = engine.forward_raw(_lib.host_tensor(r).to(dev, non_blocking=True), want_q=True, want_f=False, fmt=fmt,
+                                          noise=noise.advance(done[0]), **kw)
             done[0] += q.shape[0]
-        return q, sensor.load_gt(g, fmt, dev)
-    return _evaluate(engine, mflag, zip(raws, gts_u16), step)
+        gt = sensor.load_gt(g, fmt, dev)
+        if baseline is not None:
+            base_rows.append(score(rest[1], gt, mflag))
+        return q, gt
+    res = _evaluate(engine, mflag, zip(raws, gts_u16), step)
+    return res if baseline is None else (res, torch.cat(base_rows).cpu().numpy())
 
 
 def evaluate_srgb(engine, images, profile, mflag: int, order: str = "rgb", fmt=None, noise=None):

@@ -181,6 +181,7 @@ def main(argv=None):
     add_video_flags(ap)
     add_develop_flags(ap)
     add_unprocess_flags(ap)
+    add_baseline_flags(ap)
     args = ap.parse_args(argv)
     uprofile = unprocess_profile(ap, args)
     profile = develop_profile(ap, args)
@@ -237,7 +238,8 @@ def main(argv=None):
     if args.colour and not (args.mflag == 5 and as_image and args.save_png):
         raise SystemExit("sim.py: --colour rebuilds colour around the luma net: it needs --mflag 5, an 8-bit LR image as --input "
                          "(.png, or a uint8 .npy with --image) and --save-png")
-    lr_u8 = hr_u8 = None
+    check_baseline_flags(args, profile)
+    lr_u8 = hr_u8 = base = None
     if not as_image and uprofile is None and not args.input.endswith(".raw"):
         inps = torch.load(args.input, weights_only=True, map_location="cpu") if args.input.endswith(".pt") else \
             torch.from_numpy(np.load(args.input))
@@ -264,6 +266,10 @@ def main(argv=None):
         else:                               # TEST_RAW_ADD_NOISE: shot and read noise added while the frame is unpacked
             from sesrq import noise
             _, inps = noise.apply(None, raw, fmt, noise_m, want_q=False, want_spread=True)
+        if args.baseline:                   # the classical demosaic of the frame the net is given (the noisy one with --add-noise)
+            from sesrq import demosaic
+            f = sensor.route(fmt)[0]
+            base = demosaic.run(raw, f, args.baseline) if noise_m is None else demosaic.run_spread(inps, f.cfa, args.baseline)
     elif as_image:                          # self_dataset_sr.py: uint8 LR image / 255 (MFLAG 5: the float64 luma) -> model(inps)
         from sesrq import image
         form = image.form_of(args.mflag)
@@ -291,6 +297,10 @@ def main(argv=None):
             from sesrq import image
             gts = image.load_gt(image.load_image(args.gt), args.mflag, gfake.device, order=args.order)
         score_against(args.gt, gfake, inps, args.mflag, gts=gts, fmt=fmt)
+        if base is not None:                # the baseline's score line under the net's
+            score_against(args.gt, base, inps, args.mflag, gts=gts, fmt=fmt, title=f"{args.baseline} demosaic baseline")
+    if args.save_baseline_png:
+        save_develop_png(args.save_baseline_png, base, profile, args.order)
     if args.save_png and args.colour:
         save_colour_png(args.save_png, gfake, lr_u8, args.order)
     elif args.save_png and profile is not None:
@@ -298,6 +308,23 @@ def main(argv=None):
     elif args.save_png:
         save_png(args.save_png, gfake, inps, args.mflag, out_size)
     return gfake
+
+
+def add_baseline_flags(ap):
+    """--baseline / --save-baseline-png: the classical demosaic of a *.raw input beside the raw nets' output (sesrq.demosaic)."""
+    ap.add_argument("--baseline", choices=("malvar", "bilinear"), default=None,
+                    help="MFLAG 2 / 3 / 4 with a *.raw input: also demosaic the frame the net is given (with --add-noise the noisy one) "
+                         "with the Malvar-He-Cutler or the bilinear filters on the device; with --gt its score line is printed under "
+                         "the net's")
+    ap.add_argument("--save-baseline-png", help="with --baseline and --develop: write the developed baseline image here")
+
+
+def check_baseline_flags(args, profile):
+    if args.save_baseline_png and not (args.baseline and profile is not None):
+        raise SystemExit("sim.py: --save-baseline-png writes the developed baseline: it needs --baseline and --develop")
+    if args.baseline and not (args.mflag in (2, 3, 4) and args.input and args.input.endswith(".raw")):
+        raise SystemExit("sim.py: --baseline is the classical demosaic beside a demosaic net: it needs --mflag 2, 3 or 4 and a *.raw file "
+                         "as --input (the output of 1, nr, is a mosaic)")
 
 
 def add_sensor_flags(ap):
@@ -684,10 +711,10 @@ def load_frames(path):
     return torch.load(path, weights_only=True, map_location="cpu") if path.endswith(".pt") else torch.from_numpy(np.load(path))
 
 
-def score_against(path, gfake, inps, mflag, gts=None, fmt=None):
+def score_against(path, gfake, inps, mflag, gts=None, fmt=None, title=None):
     """The reference's evaluation loop (test.py:141-183) on the device: anchor for MFLAG 6, clip, PSNR / SSIM per frame; prints each
     frame's PSNR and the mean line.  gts: the ground truth already formed (an 8-bit HR image's), else read from `path`.  Returns the
-    (N, 3) float64 host array of (mse, psnr, ssim)."""
+    (N, 3) float64 host array of (mse, psnr, ssim).  title: what the mean line names in place of the MFLAG's task (--baseline)."""
     from sesrq import quality
     if gts is None:
         gts = load_frames(path)
@@ -703,7 +730,7 @@ def score_against(path, gfake, inps, mflag, gts=None, fmt=None):
         print(float(psnr))
         totalpsnr += float(psnr)
         totalssim += float(ssim)
-    print(quality.TASKS[mflag] + ' mean psnr is: ', totalpsnr / len(res), ' ssim is: ', totalssim / len(res))
+    print((title or quality.TASKS[mflag]) + ' mean psnr is: ', totalpsnr / len(res), ' ssim is: ', totalssim / len(res))
     return res
 
 
