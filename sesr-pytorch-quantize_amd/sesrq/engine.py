@@ -336,7 +336,7 @@ class Engine:
     __call__ = forward
 
     def forward_raw(self, raw: torch.Tensor, want_q: bool = True, want_f: bool = True, out_q=None, out_f=None, stream=None,
-                    slot: int = 0, fmt=None, stride=None, width=None, noise=None, baseline=None):
+                    slot: int = 0, fmt=None, stride=None, width=None, noise=None, baseline=None, denoise=None):
         """raw: (N, 1, H, W) or (N, H, W) torch.uint16 12-bit RGGB frames on self.device -> (q int8 | None, y float32 | None).
 
         The frames are unpacked on the device (libsesrq_raw.so, sesrq.raw) into this net's q0 -- a per-(N, H, W, slot) buffer the
@@ -357,7 +357,14 @@ class Engine:
         baseline: "malvar" or "bilinear" -- additionally returns, as a third value, the classical demosaic (N, 3, H, W) fp32 of the
         frame the net was given (libsesrq_demosaic.so, sesrq.demosaic), enqueued on the same stream right behind the unpack:
         demosaic.run(raw, fmt, baseline), or with `noise` demosaic.run_spread of the noisy fp32 frame that same noisy unpack wrote.
-        Without it nothing changes."""
+        Without it nothing changes.
+
+        denoise: a sesrq.denoise.Params, or True for Params() -- additionally returns, as the LAST value, the classical denoise
+        (N, 3, H, W) fp32, a spread frame, of the frame the net was given (libsesrq_denoise.so, sesrq.denoise), enqueued on the same
+        stream right behind the unpack: denoise.run(raw, fmt, params), or with `noise` denoise.run_spread of the noisy fp32 frame.
+        Params without levels (and True) take the per-frame levels of the `noise` model; without `noise` that is a ValueError.  With
+        `baseline` as well, the baseline is demosaic.run_spread of the DENOISED frame -- denoise, then demosaic, the classical row of a
+        noisy demosaic net -- and the return is (q, y, base, den).  Without it nothing changes."""
         from . import sensor
         if self.bundle.in_channels != 3:
             raise ValueError(f"forward_raw: a raw RGGB frame feeds 3-channel nets; this one takes {self.bundle.in_channels}")
@@ -375,35 +382,51 @@ class Engine:
             from . import noise as noisemod
             noisemod._model(noise)
 
-        base = None
+        base = den = noisy = dn = None
+        if denoise is not None:
+            from . import denoise as denoisemod
+            dn = denoisemod.params_of(denoise)
+            if not dn.fixed and noise is None:
+                raise ValueError("forward_raw: denoise without noise levels -- give Params(shot=, read=), or noise= whose levels are taken")
         if baseline is not None:
             from . import demosaic
-            method, dfmt = demosaic.method_of(baseline), sensor.route(fmt)[0]
+            method = demosaic.method_of(baseline)
+        if baseline is not None or dn is not None:
+            dfmt = sensor.route(fmt)[0]
             with torch.cuda.device(self.device):
-                base = torch.empty((N, 3, H, W), dtype=torch.float32, device=self.device)
-                # the noisy fp32 frame the baseline is taken from: a narrow net's input buffer already is that frame
-                noisy = torch.empty_like(base) if noise is not None and not narrow else None
+                base = torch.empty((N, 3, H, W), dtype=torch.float32, device=self.device) if baseline is not None else None
+                den = torch.empty((N, 3, H, W), dtype=torch.float32, device=self.device) if dn is not None else None
+                # the noisy fp32 frame the two are taken from: a narrow net's input buffer already is that frame
+                noisy = torch.empty((N, 3, H, W), dtype=torch.float32, device=self.device) if noise is not None and not narrow else None
 
         def unpack(src, buf, st):
             spread = buf if narrow else None
-            if base is not None:
+            if base is not None or den is not None:
                 spread = noisy if noisy is not None else spread
-                for t in (base, noisy):
+                for t in (base, den, noisy):
                     if t is not None and st != torch.cuda.current_stream(self.device):
                         t.record_stream(st)
             args = (self.device, fmt, self.bundle.scale[0], self.bundle.zero[0], self.exact_div, src, W, S,
                     None if narrow else buf, spread, st)
             if noise is None:
                 sensor.launch(*args)
-                if base is not None:
-                    demosaic.launch(dfmt, method, src, W, S, base, st)
+                if den is not None:
+                    denoisemod.launch(dfmt, dn, src, W, S, den, st)
             else:
                 noisemod.launch(*args, noise)
-                if base is not None:
+                if den is not None:
+                    denoisemod.launch_spread(dfmt.cfa, dn, spread, den, st, denoisemod.model_levels(dn, noise, N, self.device, st))
+            if base is not None:
+                if den is not None:
+                    demosaic.launch_spread(dfmt.cfa, method, den, base, st)
+                elif noise is None:
+                    demosaic.launch(dfmt, method, src, W, S, base, st)
+                else:
                     demosaic.launch_spread(dfmt.cfa, method, spread, base, st)
         res = self._run(raw, _lib.F32 if narrow else _lib.I8, want_q, want_f, out_q if want_q else None, out_f if want_f else None,
                         stream, slot, (N, 3, H, W), unpack)
-        return res if baseline is None else (*res, base)
+        extra = [t for t in (base, den) if t is not None]
+        return (*res, *extra) if extra else res
 
     def forward_srgb(self, img_u8: torch.Tensor, profile, order: str = "rgb", fmt=None, noise=None, want_gt: bool = False,
                      want_q: bool = True, want_f: bool = True, out_q=None, out_f=None, stream=None, slot: int = 0):

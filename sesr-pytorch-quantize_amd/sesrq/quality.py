@@ -325,7 +325,7 @@ def evaluate(engine, frames, gts, mflag: int):
     return _evaluate(engine, mflag, zip(frames, gts), step)
 
 
-def evaluate_raw(engine, raws, gts_u16, mflag: int, fmt=None, noise=None, baseline=None):
+def evaluate_raw(engine, raws, gts_u16, mflag: int, fmt=None, noise=None, baseline=None, denoise=None):
     """The reference's MFLAG 1 ... 4 loop from raw frames to scores (test.py:30-55 with self_dataset.py TestDataset): per frame the
     12-bit RGGB raw frame is unpacked on the device into the net's q0 and run forward (Engine.forward_raw), its 16-bit RGB ground
     truth is mapped to / 4095 and clamped on the device (sesrq.raw.load_gt), and the int8 output is scored as evaluate() scores it.
@@ -343,7 +343,12 @@ def evaluate_raw(engine, raws, gts_u16, mflag: int, fmt=None, noise=None, baseli
 
     baseline: "malvar" or "bilinear" -- for MFLAG 2, 3, 4 the classical demosaic of the frame the net was given (the noisy one with
     `noise`; Engine.forward_raw(baseline=...), sesrq.demosaic) is scored against the same ground truth, and the return is the pair
-    (the net's rows, the baseline's rows), both (frames, 3).  MFLAG 1 returns a mosaic, which a demosaic is no baseline of: refused."""
+    (the net's rows, the baseline's rows), both (frames, 3).  MFLAG 1 returns a mosaic, which a demosaic is no baseline of: refused.
+
+    denoise: a sesrq.denoise.Params or True -- the classical denoiser (Engine.forward_raw(denoise=...), sesrq.denoise; levels from the
+    Params, or per frame from `noise`) runs on the frame the net was given.  MFLAG 1: the denoised frame itself is the baseline, scored
+    on the mosaic as the net's output is, and the return is the pair (the net's rows, the baseline's rows).  MFLAG 2, 3, 4: it needs
+    `baseline` too, which is then the demosaic of the denoised frame."""
     import torch
     from . import sensor
     form_of(mflag)
@@ -355,6 +360,11 @@ def evaluate_raw(engine, raws, gts_u16, mflag: int, fmt=None, noise=None, baseli
         demosaic.method_of(baseline)
         if mflag == 1:
             raise ValueError("MFLAG 1 (nr) is scored on the Bayer mosaic: a demosaic baseline belongs to MFLAG 2, 3, 4")
+    if denoise is not None:
+        from . import denoise as denoisemod
+        denoisemod.params_of(denoise)
+        if mflag != 1 and baseline is None:
+            raise ValueError(f"MFLAG {mflag} is scored on RGB frames: a denoised mosaic is a baseline only with baseline= (its demosaic)")
     base_rows = []
     dev = engine.device
     if noise is not None:
@@ -363,7 +373,7 @@ def evaluate_raw(engine, raws, gts_u16, mflag: int, fmt=None, noise=None, baseli
     done = [0]           # frames so far
 
     def step(r, g, fp32):
-        kw = {} if baseline is None else {"baseline": baseline}
+        kw = {k: v for k, v in (("baseline", baseline), ("denoise", denoise)) if v is not None}
         if noise is None:
             q, *rest = engine.forward_raw(_lib.host_tensor(r).to(dev, non_blocking=True), want_q=True, want_f=False, fmt=fmt, **kw)
         else:
@@ -371,11 +381,11 @@ def evaluate_raw(engine, raws, gts_u16, mflag: int, fmt=None, noise=None, baseli
                                           noise=noise.advance(done[0]), **kw)
             done[0] += q.shape[0]
         gt = sensor.load_gt(g, fmt, dev)
-        if baseline is not None:
+        if kw:                               # behind the fp32 output: the demosaic baseline, or for MFLAG 1 the denoised mosaic
             base_rows.append(score(rest[1], gt, mflag))
         return q, gt
     res = _evaluate(engine, mflag, zip(raws, gts_u16), step)
-    return res if baseline is None else (res, torch.cat(base_rows).cpu().numpy())
+    return res if not base_rows else (res, torch.cat(base_rows).cpu().numpy())
 
 
 def evaluate_srgb(engine, images, profile, mflag: int, order: str = "rgb", fmt=None, noise=None):

@@ -239,6 +239,7 @@ def main(argv=None):
         raise SystemExit("sim.py: --colour rebuilds colour around the luma net: it needs --mflag 5, an 8-bit LR image as --input "
                          "(.png, or a uint8 .npy with --image) and --save-png")
     check_baseline_flags(args, profile)
+    check_denoise_flags(args, noise_m)
     lr_u8 = hr_u8 = base = None
     if not as_image and uprofile is None and not args.input.endswith(".raw"):
         inps = torch.load(args.input, weights_only=True, map_location="cpu") if args.input.endswith(".pt") else \
@@ -270,6 +271,15 @@ def main(argv=None):
             from sesrq import demosaic
             f = sensor.route(fmt)[0]
             base = demosaic.run(raw, f, args.baseline) if noise_m is None else demosaic.run_spread(inps, f.cfa, args.baseline)
+        if args.denoise:                    # the classical denoiser on the same frame; a demosaic baseline is then taken from its output
+            from sesrq import denoise
+            f = sensor.route(fmt)[0]
+            try:
+                params, lv = denoise_params(args, noise_m, inps.shape[0])
+                den = denoise.run(raw, f, params) if noise_m is None else denoise.run_spread(inps, f.cfa, params, levels=lv)
+            except ValueError as e:
+                raise SystemExit(f"sim.py: {e}") from None
+            base = den if args.mflag == 1 else demosaic.run_spread(den, f.cfa, args.baseline)
     elif as_image:                          # self_dataset_sr.py: uint8 LR image / 255 (MFLAG 5: the float64 luma) -> model(inps)
         from sesrq import image
         form = image.form_of(args.mflag)
@@ -298,7 +308,9 @@ def main(argv=None):
             gts = image.load_gt(image.load_image(args.gt), args.mflag, gfake.device, order=args.order)
         score_against(args.gt, gfake, inps, args.mflag, gts=gts, fmt=fmt)
         if base is not None:                # the baseline's score line under the net's
-            score_against(args.gt, base, inps, args.mflag, gts=gts, fmt=fmt, title=f"{args.baseline} demosaic baseline")
+            title = f"{args.baseline} demosaic baseline" if not args.denoise else "nlm denoise baseline" if args.mflag == 1 else \
+                f"nlm + {args.baseline} baseline"
+            score_against(args.gt, base, inps, args.mflag, gts=gts, fmt=fmt, title=title)
     if args.save_baseline_png:
         save_develop_png(args.save_baseline_png, base, profile, args.order)
     if args.save_png and args.colour:
@@ -317,6 +329,40 @@ def add_baseline_flags(ap):
                          "with the Malvar-He-Cutler or the bilinear filters on the device; with --gt its score line is printed under "
                          "the net's")
     ap.add_argument("--save-baseline-png", help="with --baseline and --develop: write the developed baseline image here")
+    ap.add_argument("--denoise", action="store_true",
+                    help="MFLAG 1 ... 4 with a *.raw input: run the classical denoiser (Bayer non-local means, sesrq.denoise) on the frame the "
+                         "net is given.  MFLAG 1: with --gt its score line is printed under the net's; MFLAG 2 / 3 / 4 (with --baseline): "
+                         "the baseline becomes the demosaic of the denoised frame")
+    ap.add_argument("--denoise-strength", type=float, default=1.0, metavar="H", help="strength h of --denoise (default 1.0)")
+    ap.add_argument("--denoise-shot", type=float, default=None, metavar="S",
+                    help="shot level --denoise assumes (with --denoise-read; default: the levels of --add-noise)")
+    ap.add_argument("--denoise-read", type=float, default=None, metavar="R", help="read level --denoise assumes (with --denoise-shot)")
+
+
+def check_denoise_flags(args, noise_m):
+    if not args.denoise:
+        if args.denoise_shot is not None or args.denoise_read is not None or args.denoise_strength != 1.0:
+            raise SystemExit("sim.py: --denoise-strength, --denoise-shot and --denoise-read belong to --denoise")
+        return
+    if not (args.mflag in (1, 2, 3, 4) and args.input and args.input.endswith(".raw")):
+        raise SystemExit("sim.py: --denoise is the classical denoiser beside a raw net: it needs --mflag 1, 2, 3 or 4 and a *.raw file as --input")
+    if args.mflag != 1 and not args.baseline:
+        raise SystemExit("sim.py: --denoise beside a demosaic net (--mflag 2, 3, 4) is a baseline through its demosaic: give --baseline too")
+    if (args.denoise_shot is None) != (args.denoise_read is None):
+        raise SystemExit("sim.py: give both --denoise-shot and --denoise-read, or neither")
+    if args.denoise_shot is None and noise_m is None:
+        raise SystemExit("sim.py: --denoise needs noise levels: --denoise-shot and --denoise-read, or --add-noise, whose levels it takes")
+
+
+def denoise_params(args, noise_m, N):
+    """(the sesrq.denoise.Params of the --denoise flags, the device per-frame levels or None): without --denoise-shot / --denoise-read
+    the levels of --add-noise -- its fixed pair, or the pair it drew for each frame."""
+    from sesrq import denoise
+    if args.denoise_shot is not None:
+        return denoise.Params(args.denoise_shot, args.denoise_read, args.denoise_strength), None
+    if noise_m.fixed:
+        return denoise.Params(noise_m.shot, noise_m.read, args.denoise_strength), None
+    return denoise.Params(h=args.denoise_strength), torch.from_numpy(noise_m.levels(N)).cuda()
 
 
 def check_baseline_flags(args, profile):
